@@ -23,12 +23,23 @@ carried k on the device and emits its shard at the global bit offset, and ONE RC
 plus a stitch kernel reassemble the byte-exact stream on every rank, on a side stream that overlaps
 the decode of the local shard (libaec_amd/shard.py: DeviceShard).  No host round trip inside a step.
 
-Rank 0 prints one JSON line: metric/value (whole-job GB/s of input bytes through encode+decode),
-`roofline` for the dominant kernel (HIP-event time measured in this run; traffic from the committed
-PMC summary of exactly this configuration, else null), `cpu_baseline` (the reference libaec -- or
-the oracle port if oracle/_ref is absent -- on one host core over the WHOLE input, whose stream the
-GPU's is compared with byte for byte) and, unless --no-extras: `cpu_baseline_all_cores`, `decode_bare`
-(index pass + decode of the stream alone, no encoder side information), `abi_end_to_end` (pinned).
+Rank 0 prints one JSON line: metric/value (whole-job GB/s of input bytes through encode+decode) and
+ms_per_step.  A plain run does only what that figure needs: set up, one untimed encode + decode (the
+compressed size the timed decodes read, and a round-trip check), warm up, time --steps steps.
+
+With --full the line also carries what takes work of its own: `roofline` for the dominant kernel
+(HIP-event time per kernel over the timed steps; traffic from the committed PMC summary of exactly
+this configuration, else null), `cpu_baseline` (the reference libaec -- or the oracle port if
+oracle/_ref is absent -- on one host core over the WHOLE input, whose stream the GPU's is compared with
+byte for byte) and, unless --no-extras: `cpu_baseline_all_cores`, `decode_bare` (index pass + decode of
+the stream alone, no encoder side information), `abi_end_to_end` (pinned); with N > 1 also `comm` and
+the checks of the sharded path (see below).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed as DIR/<name>.npy
+(float32 / float64, under 64 MB in all): `stream` (compressed bytes), `decoded` (decoded bytes),
+`rsi_offsets` (the encoder's RSI start bits), `segment_table` (start bit, preceding sample per segment),
+`encode_result` and `decode_result`.  An array longer than its cap is a seeded sample of fixed positions
+(the same on every run with the same arguments), as are the inputs, so that two builds can be compared.
 """
 import argparse
 import ctypes as C
@@ -150,6 +161,18 @@ def cpu_model():
     return "unknown"
 
 
+def host_cores():
+    """Host cores this process may really use: its affinity, capped by a container's CPU quota."""
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            cores = max(1, min(cores, -(-int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    return cores
+
+
 def cpu_all_cores(host, seconds=3.0):
     """The reference on every host core: the input cut into contiguous RSI-aligned shards, one
     independent stream per core (the reference has no threading),
@@ -159,13 +182,7 @@ def cpu_all_cores(host, seconds=3.0):
     mt_so = os.path.join(ROOT, "oracle", "_build", "libaec_mt.so")
     if not helpers.have_ref() or not os.path.exists(mt_so):
         return None
-    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    try:                                   # a container's CPU quota caps what the threads really get
-        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-        if quota != "max":
-            cores = max(1, min(cores, -(-int(quota) // int(period))))
-    except (OSError, ValueError):
-        pass
+    cores = host_cores()
     rsi_bytes = RSI * BS * ((BPS + 7) // 8)
     per = min(64 << 20, host.size // cores) // rsi_bytes * rsi_bytes
     if per == 0:
@@ -229,6 +246,40 @@ def abi_end_to_end(host_sample):
                     "libaec.so.0: init, H2D, kernels (decode: + RSI index pass), D2H, end"}
 
 
+# elements kept per array (an array longer than this is sampled at seeded positions): 16.8 MB of float32 each for
+# the byte arrays, 16.8 MB and 8.4 MB of float64 for the tables -- at most 59 MB in all
+DUMP_CAP = {"stream": 4 << 20, "decoded": 4 << 20, "rsi_offsets": 2 << 20, "segment_table": 512 << 10}
+
+
+def dump_positions(n, cap):
+    """The fixed sample of an output of n elements: sorted distinct positions in [0, n), at most cap of them."""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(0x5EED).integers(0, n, size=cap, dtype=np.int64))
+
+
+def dump_outputs(out_dir, **arrays):
+    """Writes the device tensors `arrays` (name -> tensor or None) as out_dir/<name>.npy.  Bytes become float32,
+    tables and result records float64 (bit offsets stay exact below 2^53)."""
+    import torch
+    from libaec_amd import gpu
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        if name == "segment_table":              # SEG_ENTRY_DTYPE: (start bit, preceding sample) per segment
+            t = torch.stack([t.view(torch.int64)[0::2], t.view(torch.int32)[2::4].to(torch.int64) & 0xFFFFFFFF], dim=1)
+        elif name in ("encode_result", "decode_result"):
+            rec = t.cpu().numpy().view(gpu.ENC_RESULT_DTYPE if name == "encode_result" else gpu.DEC_RESULT_DTYPE)[0]
+            np.save(os.path.join(out_dir, name + ".npy"),
+                    np.array([float(rec[f]) for f in rec.dtype.names if f != "pad"], dtype=np.float64))
+            continue
+        if t.shape[0] > DUMP_CAP[name]:
+            t = t[torch.from_numpy(dump_positions(t.shape[0], DUMP_CAP[name])).to(t.device)]
+        a = t.to(torch.float32 if t.dtype == torch.uint8 else torch.float64).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n):
     """`bench.py --gpus N` outside torchrun: start the N ranks as a CHILD process (one rank per GPU, rendezvous on
     127.0.0.1) and hand its output and exit code on.  Nothing in this process has touched HIP at this point, and it
@@ -248,8 +299,14 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU reference and the "
+                         "byte-for-byte comparison with its stream, the extras (see --no-extras), per-kernel times "
+                         "and roofline, and with N > 1 the checks of the sharded path and the `comm` record")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's) to DIR/<name>.npy")
     ap.add_argument("--size-mib", type=int, default=0,
                     help="input bytes per GPU (MiB); default 4096 on one GPU (BASELINE config 2), 8192 per rank with "
                          "several (config 4: 64 GiB over 8 ranks)")
@@ -274,6 +331,8 @@ def main():
     ap.add_argument("--shard-path", action="store_true",
                     help="run the plan/exchange/emit/gather/stitch path even with one GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     global BPS, BS, RSI, FLAGS, KIND
@@ -301,7 +360,7 @@ def main():
     if not args.size_mib:
         args.size_mib = 4096 if world == 1 else 8192
     nbytes = args.size_mib << 20
-    threads = max(1, (os.cpu_count() or 8) // max(1, world))
+    threads = max(1, host_cores() // max(1, world))
     codec = gpu.Codec(BPS, BS, RSI, FLAGS)
     codec.reserve(nbytes)
     d_in = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -346,7 +405,7 @@ def main():
         assert torch.equal(d_dec[:nbytes], d_in), "round trip differs"
 
     cpu, exact = None, None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # One host core codes the WHOLE input with the reference (about 15-30 s; the 8-bit configuration,
         # four times slower per byte, a 1 GiB prefix) and EVERY byte of the GPU stream is compared with
         # what it produced (a prefix of whole RSIs codes to a prefix of the stream).
@@ -363,7 +422,7 @@ def main():
         exact = {"compared_bytes": ncmp, "of_stream_bytes": cbytes, "input_MiB": sample.size >> 20}
         del ref_np, enc_cpu
     extras = {}
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         extras["cpu_baseline_all_cores"] = cpu_all_cores(host)
         # ---- bare stream: no offset table, no segment table -- what a stream from another producer
         # looks like.  Index pass (speculative tables + walk) + lane-per-RSI decode, timed together.
@@ -397,15 +456,16 @@ def main():
         extras["abi_end_to_end"] = abi_end_to_end(host[: 256 << 20])
     del host
 
-    # achievable HBM rate beside the spec peak: a plain device copy of the same input (N read + N written)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    d_dec[:nbytes].copy_(d_in)
-    ev0.record()
-    for _ in range(3):
+    if args.full:
+        # achievable HBM rate beside the spec peak: a plain device copy of the same input (N read + N written)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         d_dec[:nbytes].copy_(d_in)
-    ev1.record()
-    torch.cuda.synchronize()
-    copy_gbps = 2 * nbytes * 3 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+        ev0.record()
+        for _ in range(3):
+            d_dec[:nbytes].copy_(d_in)
+        ev1.record()
+        torch.cuda.synchronize()
+        copy_gbps = 2 * nbytes * 3 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
 
     # ---- N > 1: ONE stream over all ranks (libaec_amd/shard.py): plan -> exchange 3 numbers ->
     # emit at the global bit offset -> one RCCL all-gather of the slices -> local stitch.  The
@@ -473,7 +533,7 @@ def main():
         decode_async(mine)
         torch.cuda.current_stream().wait_stream(comm)
 
-    if sharded:
+    if sharded and args.full:
         # correctness of the sharded configuration before timing it: local round trip, and on one
         # rank the stitched stream must be exactly the single-device stream
         one_step()
@@ -512,7 +572,7 @@ def main():
     # (VERDICT round 4, item 8): the process group's own answers, every rank's device, the size of the all-gather and a
     # checksum of the stitched stream that every rank must agree on
     comm_info = None
-    if world > 1:
+    if world > 1 and args.full:
         import hashlib
         props = torch.cuda.get_device_properties(dev)
         mine_dev = {"rank": rank, "device": torch.cuda.current_device(), "name": props.name,
@@ -539,16 +599,18 @@ def main():
                      "plan_exchange_bytes": 24 * world if sharded else 0,
                      "stitched": gathered[0]["stitched"]}
 
-    lib = gpu._lib()
-    lib.aec_gpu_profile.argtypes = [C.c_void_p, C.c_int]
-    lib.aec_gpu_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    if args.full:
+        lib = gpu._lib()
+        lib.aec_gpu_profile.argtypes = [C.c_void_p, C.c_int]
+        lib.aec_gpu_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     for _ in range(args.warmup):
         one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    lib.aec_gpu_profile(codec.ctx, 1)      # events only; nothing waits on them until the loop is over
+    if args.full:
+        lib.aec_gpu_profile(codec.ctx, 1)  # events only; nothing waits on them until the loop is over
     t0 = time.perf_counter()
     for _ in range(args.steps):
         one_step()
@@ -562,21 +624,29 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- per-kernel device time of the timed steps (HIP events recorded by the library, on the
-    # stream the kernels ran on, around every launch of the timed region; read only now)
-    ms = (C.c_float * 5)()
-    lib.aec_gpu_phase_ms(codec.ctx, ms)
-    lib.aec_gpu_profile(codec.ctx, 0)
-    phase = dict(zip(["analyze", "scan", "clear", "pack", "decode"], [float(x) for x in ms]))
+    if args.dump_outputs and rank == 0:
+        if overlap:
+            last = (step_no[0] - 1) & 1
+            stream, seg = outs[last][:cbytes], segs[last]
+        elif sharded:
+            stream, seg = d_stream[:int(d_total.cpu().item())], d_seg
+        else:
+            stream, seg = d_out[:cbytes], d_seg
+        dump_outputs(args.dump_outputs, stream=stream, decoded=None if enc_only else d_dec[:nbytes],
+                     rsi_offsets=d_off, segment_table=seg, encode_result=d_eres,
+                     decode_result=None if enc_only else d_dres)
+
+    if args.full:
+        # ---- per-kernel device time of the timed steps (HIP events recorded by the library, on the
+        # stream the kernels ran on, around every launch of the timed region; read only now)
+        ms = (C.c_float * 5)()
+        lib.aec_gpu_phase_ms(codec.ctx, ms)
+        lib.aec_gpu_profile(codec.ctx, 0)
+        phase = dict(zip(["analyze", "scan", "clear", "pack", "decode"], [float(x) for x in ms]))
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * nbytes / (elapsed / args.steps) / 1e9
-        algo = {"analyze": nbytes, "pack": nbytes + cbytes, "decode": nbytes + cbytes}
-        dom = max(algo, key=lambda k: phase[k])
-        achieved = algo[dom] / (phase[dom] * 1e-3) / 1e9
-        traffic = measured_traffic(f"k_{dom}", args.size_mib, args.config)
-        enc_ms = phase["analyze"] + phase["scan"] + phase["clear"] + phase["pack"]
         out = {
             "metric": "encode+decode GB/s (input bytes)",
             "value": round(value, 3),
@@ -601,20 +671,28 @@ def main():
                        "ratio": round(nbytes / cbytes, 3), "bit_exact_vs_cpu": exact,
                        "parallelism": (f"{world} rank(s), one bit-exact stream" if sharded
                                        else f"{world} independent shard stream(s)")},
-            "roofline": {"bound": "hbm", "kernel": f"k_{dom}", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic[0] if traffic else None,
-                         "traffic_source": traffic[1] if traffic else None,
-                         "algorithmic_bytes_per_launch": algo[dom], "kernel_ms": round(phase[dom], 4),
-                         "device_copy_GBps": round(copy_gbps, 1),
-                         "frac_of_device_copy": round(achieved / copy_gbps, 5)},
-            "cpu_baseline": cpu,
-            "phases_ms": {k: round(v, 4) for k, v in phase.items()},
-            "encode_GBps": round(nbytes / (enc_ms * 1e-3) / 1e9, 2),
-            "decode_GBps": round(nbytes / (phase["decode"] * 1e-3) / 1e9, 2),
-            "decode_note": "decode_GBps uses the encoder's segment table (side information next to the unchanged "
-                           "stream); decode_bare is the rate from the stream alone",
         }
+        if args.full:
+            algo = {"analyze": nbytes, "pack": nbytes + cbytes, "decode": nbytes + cbytes}
+            dom = max(algo, key=lambda k: phase[k])
+            achieved = algo[dom] / (phase[dom] * 1e-3) / 1e9
+            traffic = measured_traffic(f"k_{dom}", args.size_mib, args.config)
+            enc_ms = phase["analyze"] + phase["scan"] + phase["clear"] + phase["pack"]
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": f"k_{dom}", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "traffic": traffic[0] if traffic else None,
+                             "traffic_source": traffic[1] if traffic else None,
+                             "algorithmic_bytes_per_launch": algo[dom], "kernel_ms": round(phase[dom], 4),
+                             "device_copy_GBps": round(copy_gbps, 1),
+                             "frac_of_device_copy": round(achieved / copy_gbps, 5)},
+                "cpu_baseline": cpu,
+                "phases_ms": {k: round(v, 4) for k, v in phase.items()},
+                "encode_GBps": round(nbytes / (enc_ms * 1e-3) / 1e9, 2),
+                "decode_GBps": round(nbytes / (phase["decode"] * 1e-3) / 1e9, 2),
+                "decode_note": "decode_GBps uses the encoder's segment table (side information next to the unchanged "
+                               "stream); decode_bare is the rate from the stream alone",
+            })
         if comm_info:
             out["comm"] = comm_info
         out.update({k: v for k, v in extras.items() if v is not None})

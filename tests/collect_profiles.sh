@@ -6,13 +6,13 @@
 OUT=$PWD/gpurun_out/$1; R=$PWD
 mkdir -p $OUT
 for c in c2 c3 c5 typical; do
-  python3 bench.py --config $c > $OUT/bench_${c}_4GiB.json 2> $OUT/bench_${c}.err
+  python3 bench.py --full --config $c > $OUT/bench_${c}_4GiB.json 2> $OUT/bench_${c}.err
 done
-python3 bench.py --shard-path --no-extras > $OUT/bench_c2_4GiB_shard_path.json 2>> $OUT/bench_c2.err
-python3 bench.py --overlap --no-extras --no-cpu-baseline > $OUT/bench_c2_4GiB_overlap.json 2>> $OUT/bench_c2.err
+python3 bench.py --full --shard-path --no-extras > $OUT/bench_c2_4GiB_shard_path.json 2>> $OUT/bench_c2.err
+python3 bench.py --full --overlap --no-extras --no-cpu-baseline > $OUT/bench_c2_4GiB_overlap.json 2>> $OUT/bench_c2.err
 ( cd /tmp && export TMPDIR=/tmp
   for c in c2 c3 c5 typical; do
-    timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$c -- python3 $R/bench.py --config $c --no-cpu-baseline --no-extras > $OUT/bench_${c}_4GiB_under_rocprofv3.json 2> /dev/null
+    timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$c -- python3 $R/bench.py --full --config $c --no-cpu-baseline --no-extras > $OUT/bench_${c}_4GiB_under_rocprofv3.json 2> /dev/null
     f=$(find $OUT/stats_$c -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats_${c}_4GiB.csv
   done )
 for c in c2 c3 c5 typical; do

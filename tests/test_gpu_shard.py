@@ -157,7 +157,7 @@ def test_bench_sharded_path_with_ranks_sharing_one_gpu(world):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
            "--gpus", str(world), "--share-gpu", "--size-mib", "256", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
