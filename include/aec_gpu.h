@@ -143,6 +143,28 @@ AEC_GPU_API int aec_gpu_decode_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, 
                                      aec_gpu_dec_result *d_result, void *stream);
 
 /*
+ * Random access: decode bytes [pos, pos + size) of what the RSIs whose start bits (relative to d_in) are
+ * d_rsi_bit_offsets[0 .. n_offsets) decode to -- the bytes aec_buffer_decode of the whole stream puts there; exactly
+ * `size` bytes land at d_out and nothing outside them is written.  Only RSIs pos / R .. (pos + size - 1) / R
+ * (R = rsi * block_size * bytes per sample) are decoded, the last of them up to the block that holds the window's last
+ * byte.  An RSI of the window that is decoded whole and has an entry behind it must end exactly there (rounded up to a
+ * byte with AEC_PAD_RSI), else d_result says status 2 with bad_rsi = that RSI (numbered from entry 0); status 1: the
+ * input ends before the window does.  On either, the bytes at d_out are unspecified.  d_in as aec_gpu_decode_async;
+ * d_out any alignment.  A window that starts on an RSI and ends on a block, at a 16-byte aligned d_out, is decoded in
+ * place; any other goes through workspace of the context -- its whole blocks, then one copy of `size` bytes -- which
+ * is grown on demand as the index pass grows its tables: a call that grows it synchronises the device (hipMalloc);
+ * aec_gpu_held_bytes counts it, aec_gpu_trim releases it.  (The kernels store whole blocks, so this path holds the
+ * window's RSIs once more on the device; the libaec ABI's aec_decode_range only ever asks for windows that start on an
+ * RSI and end on a block, and copies the caller's bytes out of them.)
+ * RC_CONF_ERROR when the window needs an RSI beyond the table.  The host works the RSIs out from the arguments:
+ * nothing is read back from the device.
+ */
+AEC_GPU_API int aec_gpu_decode_range_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in,
+                                           size_t in_bytes, const uint64_t *d_rsi_bit_offsets, uint64_t n_offsets,
+                                           uint64_t pos, uint64_t size, void *d_out, aec_gpu_dec_result *d_result,
+                                           void *stream);
+
+/*
  * Segment-granular variant of the offset table.  After aec_gpu_set_segment_table(ctx, d_table) every
  * encode / emit call on ctx also fills d_table with aec_gpu_segment_count() entries (pass NULL to
  * stop).  aec_gpu_decode_segments_async decodes from such a table, one lane per segment.

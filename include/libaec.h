@@ -53,6 +53,7 @@ struct aec_stream {
 #define AEC_STREAM_ERROR (-2)
 #define AEC_DATA_ERROR (-3)
 #define AEC_MEM_ERROR (-4)
+#define AEC_RSI_OFFSETS_ERROR (-5)   /* libaec 1.1: offsets not enabled, or enabled too late */
 
 /* flush modes, reference src/libaec.h:141-149 */
 #define AEC_NO_FLUSH 0   /* more input may follow */
@@ -101,6 +102,60 @@ LIBAEC_API int aec_buffer_encode_batch(const struct aec_stream *params, size_t n
                                        const size_t *src_len, void *const *dst, size_t *dst_len, int *status);
 LIBAEC_API int aec_buffer_decode_batch(const struct aec_stream *params, size_t n, const void *const *src,
                                        const size_t *src_len, void *const *dst, size_t *dst_len, int *status);
+
+/*
+ * RSI offsets and random access: the entry points libaec 1.1 added (same names, arguments and return codes; SONAME
+ * still libaec.so.0).  An RSI (reference sample interval) is rsi blocks; an offset is a BIT position in the stream.
+ * Nothing here costs anything unless a caller enables offsets or calls aec_decode_range.
+ *
+ * Bit 0: for the encoder the first bit it wrote after aec_encode_init; for the decoder the first bit of the byte at
+ * next_in after aec_decode_init -- after aec_buffer_seek that is the byte the seek moved next_in to (so its table
+ * starts at offset % 8, like the stream's total_in, which the seek leaves alone).
+ *
+ * aec_encode_enable_offsets: after aec_encode_init, before the first aec_encode that takes input (later:
+ *   AEC_RSI_OFFSETS_ERROR).  Entry i is the start bit of RSI i's first coded data set.  The count is the number of
+ *   RSIs whose first block has been coded so far -- the library stages up to 1 MiB of input before it codes, so it can
+ *   lag the input; after AEC_FLUSH it is ceil(blocks / rsi).  AEC_PAD_RSI is ignored by the encoder, as by the
+ *   reference (nothing is padded).
+ * aec_decode_enable_offsets: after aec_decode_init (and aec_buffer_seek), before the first aec_decode.  Entry i is the
+ *   start bit of the i-th RSI whose first coded data set has been decoded (with AEC_PAD_RSI: its byte-aligned start).
+ *   For a complete stream the table equals the encoder's however the input was cut into calls.
+ * *_count_offsets / *_get_offsets: AEC_RSI_OFFSETS_ERROR on a state without offsets enabled (count also sets
+ *   *rsi_offsets_count = 0); get with a buffer of fewer than count entries: AEC_MEM_ERROR, nothing written.  The
+ *   tables stay readable until *_end.
+ * aec_buffer_seek: on a decoder state on which aec_decode has not run (else AEC_STREAM_ERROR).  Moves next_in forward
+ *   by offset / 8 and takes as much off avail_in; the next aec_decode starts at bit offset % 8 of that byte, as at an RSI
+ *   start.  total_in is unchanged.  AEC_MEM_ERROR, nothing changed, when the bit lies beyond the input.
+ * aec_decode_range(strm, offs, n, pos, size): strm from aec_decode_init, next_in / avail_in the stream from bit 0,
+ *   offs[0 .. n) its RSI start bits (the encoder's or the decoder's table).  Writes bytes [pos, pos + size) of what
+ *   aec_buffer_decode of the whole stream produces (byte counts: need not be sample-aligned) to next_out and advances
+ *   next_out / avail_out / total_out by size; next_in / avail_in / total_in stay as they are.  Any number of calls may
+ *   follow on one state, then aec_decode_end.  Only the RSIs the window touches are decoded -- the last of them up to
+ *   the block that holds byte pos + size - 1 -- and no index pass runs.  With R = rsi * block_size * bytes per sample:
+ *     size == 0                                                   AEC_OK, nothing written
+ *     pos / R >= n                                                AEC_DATA_ERROR, nothing written
+ *     avail_out < size                                            AEC_MEM_ERROR, nothing written
+ *     offs[pos / R .. min((pos + size - 1) / R + 1, n - 1)] not strictly increasing or not below 8 * avail_in
+ *                                                                 AEC_DATA_ERROR, nothing written (host-side check)
+ *     the window needs an RSI beyond the table                    AEC_DATA_ERROR, nothing written
+ *     aec_decode has run on this state                            AEC_STREAM_ERROR, nothing written
+ *     the stream ends before byte pos + size, or an RSI the window decodes whole does not end exactly at the next
+ *     entry (rounded up to a byte with AEC_PAD_RSI), where there is one: the table is not this stream's
+ *                                                                 AEC_DATA_ERROR; [next_out, next_out + size)
+ *                                                                 unspecified, next_out not advanced
+ *   Whatever the table says, no byte outside [next_out, next_out + size) is written and nothing beyond
+ *   next_in + avail_in is read.  A table that is wrong in a way the decoder cannot see (an entry that still lands on a
+ *   coded data set of the right kind, inside an RSI the window only decodes in part) gives wrong bytes, not an error.
+ */
+LIBAEC_API int aec_encode_enable_offsets(struct aec_stream *strm);
+LIBAEC_API int aec_encode_count_offsets(struct aec_stream *strm, size_t *rsi_offsets_count);
+LIBAEC_API int aec_encode_get_offsets(struct aec_stream *strm, size_t *rsi_offsets, size_t rsi_offsets_count);
+LIBAEC_API int aec_buffer_seek(struct aec_stream *strm, size_t offset);
+LIBAEC_API int aec_decode_enable_offsets(struct aec_stream *strm);
+LIBAEC_API int aec_decode_count_offsets(struct aec_stream *strm, size_t *rsi_offsets_count);
+LIBAEC_API int aec_decode_get_offsets(struct aec_stream *strm, size_t *rsi_offsets, size_t rsi_offsets_count);
+LIBAEC_API int aec_decode_range(struct aec_stream *strm, const size_t *rsi_offsets, size_t rsi_offsets_count,
+                                size_t pos, size_t size);
 
 #ifdef __cplusplus
 }

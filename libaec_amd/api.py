@@ -24,6 +24,8 @@ AEC_CONF_ERROR = -1
 AEC_STREAM_ERROR = -2
 AEC_DATA_ERROR = -3
 AEC_MEM_ERROR = -4
+# libaec 1.1 (include/libaec.h: RSI offsets and random access)
+AEC_RSI_OFFSETS_ERROR = -5
 # reference src/libaec.h:141-149
 AEC_NO_FLUSH = 0
 AEC_FLUSH = 1
@@ -96,6 +98,18 @@ def library():
             fn = getattr(lib, name)
             fn.restype = C.c_int
             fn.argtypes = [C.POINTER(AecStream), C.c_int]
+        sp, szp = C.POINTER(AecStream), C.POINTER(C.c_size_t)
+        for name, args in (("aec_encode_enable_offsets", [sp]), ("aec_decode_enable_offsets", [sp]),
+                           ("aec_encode_count_offsets", [sp, szp]), ("aec_decode_count_offsets", [sp, szp]),
+                           ("aec_encode_get_offsets", [sp, szp, C.c_size_t]),
+                           ("aec_decode_get_offsets", [sp, szp, C.c_size_t]),
+                           ("aec_buffer_seek", [sp, C.c_size_t]),
+                           ("aec_decode_range", [sp, szp, C.c_size_t, C.c_size_t, C.c_size_t])):
+            if not hasattr(lib, name):        # (AEC_AMD_LIB: a build from before the offsets API)
+                continue
+            fn = getattr(lib, name)
+            fn.restype = C.c_int
+            fn.argtypes = args
         _lib = lib
     return _lib
 
@@ -191,9 +205,72 @@ class _Stream:
             pass
 
 
+    # RSI offset tables (libaec 1.1)
+    _enable = _count = _get = None
+
+    def enable_offsets(self):
+        """aec_*_enable_offsets.  Returns the return code."""
+        return getattr(self.lib, self._enable)(C.byref(self.s))
+
+    def offsets(self):
+        """(rc, offsets as a numpy uint64 array) from aec_*_count_offsets / aec_*_get_offsets."""
+        n = C.c_size_t(0)
+        rc = getattr(self.lib, self._count)(C.byref(self.s), C.byref(n))
+        if rc != AEC_OK:
+            return rc, np.zeros(0, dtype=np.uint64)
+        out = (C.c_size_t * max(n.value, 1))()
+        rc = getattr(self.lib, self._get)(C.byref(self.s), out, n.value)
+        return rc, np.array(out[:n.value], dtype=np.uint64)
+
+
 class Encoder(_Stream):
     _init, _call, _end = "aec_encode_init", "aec_encode", "aec_encode_end"
+    _enable, _count, _get = "aec_encode_enable_offsets", "aec_encode_count_offsets", "aec_encode_get_offsets"
 
 
 class Decoder(_Stream):
     _init, _call, _end = "aec_decode_init", "aec_decode", "aec_decode_end"
+    _enable, _count, _get = "aec_decode_enable_offsets", "aec_decode_count_offsets", "aec_decode_get_offsets"
+
+    def buffer_seek(self, data, offset):
+        """aec_buffer_seek on `data` (kept for the next call): returns (rc, bytes skipped).  The next `call` must
+        pass the rest, data[skipped:]."""
+        a = _u8(data)
+        self._seek_keep = a
+        self.s.next_in, self.s.avail_in = a.ctypes.data, a.size
+        rc = self.lib.aec_buffer_seek(C.byref(self.s), int(offset))
+        return rc, a.size - self.s.avail_in
+
+
+def encode_with_offsets(data, bits_per_sample, block_size, rsi, flags, out_size=None):
+    """aec_buffer_encode with offsets enabled: returns (rc, encoded bytes, RSI start bits as numpy uint64)."""
+    a = _u8(data)
+    if out_size is None:
+        out_size = max_encoded_size(a.size, bits_per_sample, max(block_size, 1), flags)
+    enc = Encoder(bits_per_sample, block_size, rsi, flags)
+    rc = enc.enable_offsets()
+    if rc != AEC_OK:
+        return rc, b"", np.zeros(0, dtype=np.uint64)
+    rc, _, out = enc.call(a, int(out_size), AEC_FLUSH)
+    rc_o, offs = enc.offsets()
+    rc_e = enc.end()
+    return (rc or rc_o or rc_e), out, offs
+
+
+def decode_range(stream, offsets, pos, size, bits_per_sample, block_size, rsi, flags, out=None, state=None):
+    """aec_decode_range: bytes [pos, pos + size) of the decoded stream.  Returns (rc, bytes, aec_stream after the
+    call).  `out` (optional numpy uint8 array of at least `size` bytes) receives them; `state` (optional Decoder)
+    is used instead of a fresh one, so that many ranges run on one state."""
+    a = _u8(stream)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    dec = state if state is not None else Decoder(bits_per_sample, block_size, rsi, flags)
+    if out is None:
+        out = np.zeros(max(int(size), 1), dtype=np.uint8)
+    dec.s.next_in, dec.s.avail_in = a.ctypes.data, a.size
+    dec.s.next_out, dec.s.avail_out = out.ctypes.data, int(size)
+    rc = dec.lib.aec_decode_range(C.byref(dec.s), offs.ctypes.data_as(C.POINTER(C.c_size_t)), offs.size, int(pos),
+                                  int(size))
+    got = out[:int(size)].tobytes() if rc == AEC_OK else b""
+    if state is None:
+        dec.end()
+    return rc, got, dec.s

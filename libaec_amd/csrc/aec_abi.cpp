@@ -36,6 +36,7 @@
 #include "../../include/libaec.h"
 #include "aec_cfg.h"
 #include "aec_pool.h"
+#include "aec_tune.h"
 
 using namespace aec;
 
@@ -109,6 +110,7 @@ constexpr size_t kBacklogMax = (size_t)64 << 20;     // undecoded input held on 
 constexpr size_t kBounce = (size_t)256 << 10;        // pinned bounce buffer: first output bytes ride with the records
 constexpr size_t kPipeOut = (size_t)64 << 20;        // decode: output per batch where batches are pipelined (below)
 constexpr size_t kAsyncMin = (size_t)1 << 20;        // ... and the smallest copy-out that is worth the side stream
+constexpr size_t kRangeRsis = 2048;                  // aec_decode_range: RSIs per batch at least (below)
 
 }  // namespace
 
@@ -155,6 +157,12 @@ struct internal_state {
     bool more;                     // the last batch stopped at its RSI bound: decodable input remains
     bool launched;                 // at least one batch has run
     int sticky_error;
+
+    // RSI offset tables (include/libaec.h: aec_*_enable_offsets): absolute stream bits, kept only when enabled
+    bool offsets_on;
+    std::vector<uint64_t> offs;
+    uint64_t enc_bits;             // encoder: stream bits produced by the batches so far
+    bool took_input;               // encoder: an aec_encode call has taken input; decoder: aec_decode has run
 };
 
 namespace {
@@ -315,6 +323,9 @@ int init_common(struct aec_stream *strm, bool enc)
     s->more = false;
     s->launched = false;
     s->sticky_error = AEC_OK;
+    s->offsets_on = false;
+    s->enc_bits = 0;
+    s->took_input = false;
     s->ctx = nullptr;
     s->stream = nullptr;
     s->copy_stream = nullptr;
@@ -378,10 +389,17 @@ int encode_batch(internal_state *s, const uint8_t *data, size_t nbytes, struct a
     if (nbytes == 0) return AEC_OK;
     const size_t cap = aec_gpu_encode_bound(&s->prm, nbytes);
     if (!s->d_in.ensure(nbytes + 16) || !s->d_out.ensure(cap)) return AEC_FAIL(AEC_MEM_ERROR);
+    // (offsets enabled: the batch's RSI starts, relative to bit 0 of its first byte -- the open byte's bits included)
+    const uint64_t n_rsi = s->offsets_on ? aec_gpu_rsi_count(&s->prm, nbytes) : 0;
+    uint64_t *d_tbl = nullptr;
+    if (s->offsets_on) {
+        if (!s->d_off.ensure((n_rsi + 1) * 8)) return AEC_FAIL(AEC_MEM_ERROR);
+        d_tbl = static_cast<uint64_t *>(s->d_off.p);
+    }
     if (hipMemcpyAsync(s->d_in.p, data, nbytes, hipMemcpyHostToDevice, s->stream) != hipSuccess)
         return AEC_FAIL(AEC_MEM_ERROR);
     const int rc = aec_gpu_encode_async(s->ctx, &s->prm, s->d_in.p, nbytes, s->d_out.p, cap, s->part_bits,
-                                        s->k, nullptr, static_cast<aec_gpu_enc_result *>(s->d_res.p),
+                                        s->k, d_tbl, static_cast<aec_gpu_enc_result *>(s->d_res.p),
                                         s->stream);
     if (rc != RC_OK) return AEC_FAIL(rc);
     const uint8_t *d_bytes = static_cast<const uint8_t *>(s->d_out.p);
@@ -394,6 +412,15 @@ int encode_batch(internal_state *s, const uint8_t *data, size_t nbytes, struct a
         return AEC_FAIL(AEC_MEM_ERROR);
     const aec_gpu_enc_result res = *reinterpret_cast<aec_gpu_enc_result *>(s->h_res);
     if (res.overflow) return AEC_FAIL(AEC_MEM_ERROR);   // cannot happen: cap is the worst case
+    if (n_rsi) {
+        const size_t at = s->offs.size();
+        s->offs.resize(at + n_rsi);
+        if (hipMemcpy(s->offs.data() + at, d_tbl, n_rsi * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            return AEC_FAIL(AEC_MEM_ERROR);
+        const uint64_t origin = s->enc_bits - s->part_bits;     // stream bit of the batch's first byte
+        for (size_t i = at; i < at + n_rsi; i++) s->offs[i] += origin;
+    }
+    s->enc_bits += res.total_bits;
     const uint64_t bits = (uint64_t)s->part_bits + res.total_bits;
     const size_t whole = (size_t)(bits / 8), nb = (size_t)((bits + 7) / 8);
     // bytes [0, whole) are finished, byte `whole` (if nb > whole) is the new open byte
@@ -667,6 +694,16 @@ int decode_run(internal_state *s, struct aec_stream *strm)
         return AEC_DATA_ERROR;
     }
     if (res_rsi) s->rsi_bits_seen = (res_end - rsi_rel) / (res_rsi + (res_tail ? 1 : 0));
+    // offsets enabled: the RSIs of the batch whose first coded data set is decoded -- the whole ones, and the one it
+    // ends in -- in absolute bits; the first of them may be the one the batch in front ended in (counted once)
+    if (s->offsets_on && (res_rsi || res_tail)) {
+        std::vector<uint64_t> got(res_rsi + (res_tail ? 1 : 0));
+        if (res_rsi && hipMemcpy(got.data(), d_off, res_rsi * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            return AEC_FAIL(AEC_MEM_ERROR);
+        if (res_tail) got[res_rsi] = tail_start;
+        for (const uint64_t v : got)
+            if (s->offs.empty() || base_bits + v > s->offs.back()) s->offs.push_back(base_bits + v);
+    }
 
     // advance: the walker resumes behind the last complete coded data set
     s->walk_bit = base_bits + res_end;
@@ -711,6 +748,7 @@ int encode_call(struct aec_stream *strm, int flush)
     const size_t bytes = s->cfg.bytes;
     const size_t rsi_bytes = (size_t)s->cfg.rsi * s->cfg.bs * bytes;
     s->flush = flush;
+    if (strm->avail_in) s->took_input = true;
     strm->total_in += strm->avail_in;     // reference encode.c:919-920
     strm->total_out += strm->avail_out;
     const bool brought = strm->avail_in >= bytes;
@@ -785,6 +823,7 @@ int decode_call(struct aec_stream *strm, int flush)
 {
     internal_state *s = strm->state;
     const size_t bytes = s->cfg.bytes;
+    s->took_input = true;
     strm->total_in += strm->avail_in;     // reference decode.c:811-812
     strm->total_out += strm->avail_out;
     int rc = s->sticky_error;
@@ -1363,6 +1402,130 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
     return worst;
 }
 
+// ---- random access (include/libaec.h: aec_decode_range) -----------------------------------------------
+// The window's RSIs in batches of whole RSIs, kPipeOut of output each: per batch, the stream bytes from its first RSI's
+// start to the next table entry behind its last one go up with the batch's rebased table, aec_gpu_decode_range_async
+// decodes its blocks in place (from an RSI start to a block end), and the window's part of them goes to the caller's
+// buffer -- a small one with the result record (one synchronisation), a large one on the side stream beside the next
+// batch's kernels (the two output buffers alternate, as in decode_run).  No index pass: the table says where RSIs start.
+int decode_range_call(struct aec_stream *strm, const size_t *offs, size_t n, size_t pos, size_t size)
+{
+    internal_state *s = strm->state;
+    if (!s || s->encoder) return AEC_FAIL(AEC_STREAM_ERROR);
+    if (size == 0) return AEC_OK;
+    if (s->took_input) return AEC_FAIL(AEC_STREAM_ERROR);
+    const Cfg &c = s->cfg;
+    const size_t blk_bytes = (size_t)c.bs * c.bytes, rsi_bytes = (size_t)c.rsi * blk_bytes;
+    if (!offs || pos / rsi_bytes >= n) return AEC_FAIL(AEC_DATA_ERROR);
+    if (strm->avail_out < size) return AEC_FAIL(AEC_MEM_ERROR);
+    if (pos + size < pos) return AEC_FAIL(AEC_DATA_ERROR);
+    const size_t r0 = pos / rsi_bytes, r1 = (pos + size - 1) / rsi_bytes;
+    if (r1 >= n) return AEC_FAIL(AEC_DATA_ERROR);       // (the table ends in front of the window: the stream does too)
+    // the entries the window reads, and the one behind it: strictly increasing, inside the input
+    const uint64_t in_bits = (uint64_t)strm->avail_in * 8;
+    const size_t last = r1 + 1 < n ? r1 + 1 : n - 1;
+    for (size_t i = r0; i <= last; i++)
+        if (offs[i] >= in_bits || (i > r0 && offs[i] <= offs[i - 1])) return AEC_FAIL(AEC_DATA_ERROR);
+
+    // (at least kRangeRsis RSIs per batch: long RSIs -- 512 KiB of 32-bit output each -- are a wavefront each, and a
+    // batch of fewer than the chip holds at once leaves it part idle: k_decode_wave<32, 4> takes 244 VGPRs, 8 waves per
+    // CU, 2048 on 256 CUs, and one launch of them takes ~3.1 ms whether it has 512 RSIs or 2048 (profiles/r07: config 3,
+    // 1 GiB: 29.7 GB/s with batches of 512 RSIs, 34.6 with 1024, 39.2 with 2048).  AEC_RANGE_RSIS: the tuning build's
+    // knob for measuring it)
+    const size_t least = tune("AEC_RANGE_RSIS", (uint32_t)kRangeRsis);
+    const size_t per = kPipeOut / rsi_bytes > least ? kPipeOut / rsi_bytes : least;
+    aec_gpu_dec_result *d_dec = static_cast<aec_gpu_dec_result *>(s->d_res.p);
+    uint8_t *bounce = s->h_res + 256;
+    bool pending[2] = {false, false};
+    int rc = AEC_OK;
+    std::vector<uint64_t> tbl;
+    for (size_t ra = r0; ra <= r1 && rc == AEC_OK; ra += per) {
+        const size_t rb = ra + per - 1 < r1 ? ra + per - 1 : r1;
+        const bool next = rb + 1 < n;
+        const uint64_t first = (uint64_t)ra * rsi_bytes;
+        const uint64_t lo = pos > first ? pos : first;
+        const uint64_t hi = pos + size < (uint64_t)(rb + 1) * rsi_bytes ? pos + size : (uint64_t)(rb + 1) * rsi_bytes;
+        const uint64_t dev_size = (hi + blk_bytes - 1) / blk_bytes * blk_bytes - first;
+        // stream bytes of the batch: from its first RSI's word to a little behind the next entry (or the input's end)
+        const size_t from = (size_t)(offs[ra] / 8) & ~(size_t)3;
+        size_t to = next ? (size_t)(offs[rb + 1] / 8) + 8 : strm->avail_in;
+        if (to > strm->avail_in) to = strm->avail_in;
+        const size_t in_bytes = to - from;
+        tbl.resize(rb - ra + 1 + (next ? 1 : 0));
+        for (size_t i = 0; i < tbl.size(); i++) tbl[i] = offs[ra + i] - (uint64_t)from * 8;
+        DevBuf &obuf = s->out_sel ? s->d_out2 : s->d_out;
+        if (!s->d_in.ensure(in_bytes + 32) || !s->d_off.ensure(tbl.size() * 8) || !obuf.ensure(dev_size + 64)) {
+            rc = AEC_FAIL(AEC_MEM_ERROR);
+            break;
+        }
+        // (the copy that read this output buffer two batches ago must be through before the decoder writes it again)
+        if (pending[s->out_sel] && hipStreamWaitEvent(s->stream, s->ev_copied[s->out_sel], 0) != hipSuccess) {
+            rc = AEC_FAIL(AEC_MEM_ERROR);
+            break;
+        }
+        if (hipMemcpyAsync(s->d_in.p, strm->next_in + from, in_bytes, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+            hipMemcpyAsync(s->d_off.p, tbl.data(), tbl.size() * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess) {
+            rc = AEC_FAIL(AEC_MEM_ERROR);
+            break;
+        }
+        const int grc = aec_gpu_decode_range_async(s->ctx, &s->prm, s->d_in.p, in_bytes, static_cast<const uint64_t *>(s->d_off.p),
+                                                   tbl.size(), 0, dev_size, obuf.p, d_dec, s->stream);
+        if (grc != RC_OK) {
+            rc = AEC_FAIL(grc == RC_MEM_ERROR ? AEC_MEM_ERROR : AEC_DATA_ERROR);
+            break;
+        }
+        const uint8_t *d_bytes = static_cast<const uint8_t *>(obuf.p) + (lo - first);
+        const size_t len = (size_t)(hi - lo);
+        const bool small = len <= kBounce;
+        if (hipMemcpyAsync(s->h_res, d_dec, sizeof(aec_gpu_dec_result), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+            (small && hipMemcpyAsync(bounce, d_bytes, len, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+            hipStreamSynchronize(s->stream) != hipSuccess) {
+            rc = AEC_FAIL(AEC_MEM_ERROR);
+            break;
+        }
+        const aec_gpu_dec_result dec = *reinterpret_cast<const aec_gpu_dec_result *>(s->h_res);
+        if (dec.status != DEC_OK) {
+            if (trace_on())
+                fprintf(stderr, "libaec (MI355X): aec_decode_range: status %u at RSI %llu of the table\n", dec.status,
+                        (unsigned long long)(ra + dec.bad_rsi));
+            rc = AEC_DATA_ERROR;
+            break;
+        }
+        uint8_t *dst = strm->next_out + (lo - pos);
+        if (small) {
+            memcpy(dst, bounce, len);
+            continue;
+        }
+        bool async = true;
+        if (!s->copy_stream) async = hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking) == hipSuccess;
+        if (async && !s->ev_copied[s->out_sel])
+            async = hipEventCreateWithFlags(&s->ev_copied[s->out_sel], hipEventDisableTiming) == hipSuccess;
+        if (async) {
+            if (hipMemcpyAsync(dst, d_bytes, len, hipMemcpyDeviceToHost, s->copy_stream) != hipSuccess ||
+                hipEventRecord(s->ev_copied[s->out_sel], s->copy_stream) != hipSuccess) {
+                rc = AEC_FAIL(AEC_MEM_ERROR);
+                break;
+            }
+            pending[s->out_sel] = true;
+            s->out_sel ^= 1u;
+        } else {
+            (void)hipGetLastError();
+            if (hipMemcpy(dst, d_bytes, len, hipMemcpyDeviceToHost) != hipSuccess) {
+                rc = AEC_FAIL(AEC_MEM_ERROR);
+                break;
+            }
+        }
+    }
+    // (nothing of ours may still write the caller's buffer on return)
+    if ((pending[0] || pending[1]) && hipStreamSynchronize(s->copy_stream) != hipSuccess && rc == AEC_OK)
+        rc = AEC_FAIL(AEC_MEM_ERROR);
+    if (rc != AEC_OK) return rc;
+    strm->next_out += size;
+    strm->avail_out -= size;
+    strm->total_out += size;
+    return AEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1455,6 +1618,79 @@ int aec_decode_end(struct aec_stream *strm)
     free_state(strm->state);
     strm->state = nullptr;
     return AEC_OK;
+}
+
+int aec_encode_enable_offsets(struct aec_stream *strm)
+{
+    internal_state *s = strm->state;
+    if (!s || !s->encoder || s->took_input) return AEC_RSI_OFFSETS_ERROR;
+    s->offsets_on = true;
+    return AEC_OK;
+}
+
+int aec_decode_enable_offsets(struct aec_stream *strm)
+{
+    internal_state *s = strm->state;
+    if (!s || s->encoder || s->took_input) return AEC_RSI_OFFSETS_ERROR;
+    s->offsets_on = true;
+    return AEC_OK;
+}
+
+static int count_offsets(struct aec_stream *strm, bool encoder, size_t *count)
+{
+    internal_state *s = strm->state;
+    if (!s || s->encoder != encoder || !s->offsets_on) {
+        if (count) *count = 0;
+        return AEC_RSI_OFFSETS_ERROR;
+    }
+    if (!count) return AEC_MEM_ERROR;
+    *count = s->offs.size();
+    return AEC_OK;
+}
+
+static int get_offsets(struct aec_stream *strm, bool encoder, size_t *offsets, size_t count)
+{
+    internal_state *s = strm->state;
+    if (!s || s->encoder != encoder || !s->offsets_on) return AEC_RSI_OFFSETS_ERROR;
+    if (count < s->offs.size() || (!offsets && !s->offs.empty())) return AEC_MEM_ERROR;
+    for (size_t i = 0; i < s->offs.size(); i++) offsets[i] = (size_t)s->offs[i];
+    return AEC_OK;
+}
+
+int aec_encode_count_offsets(struct aec_stream *strm, size_t *rsi_offsets_count)
+{
+    return count_offsets(strm, true, rsi_offsets_count);
+}
+int aec_encode_get_offsets(struct aec_stream *strm, size_t *rsi_offsets, size_t rsi_offsets_count)
+{
+    return get_offsets(strm, true, rsi_offsets, rsi_offsets_count);
+}
+int aec_decode_count_offsets(struct aec_stream *strm, size_t *rsi_offsets_count)
+{
+    return count_offsets(strm, false, rsi_offsets_count);
+}
+int aec_decode_get_offsets(struct aec_stream *strm, size_t *rsi_offsets, size_t rsi_offsets_count)
+{
+    return get_offsets(strm, false, rsi_offsets, rsi_offsets_count);
+}
+
+int aec_buffer_seek(struct aec_stream *strm, size_t offset)
+{
+    internal_state *s = strm->state;
+    if (!s || s->encoder || s->took_input) return AEC_STREAM_ERROR;
+    if (offset / 8 >= strm->avail_in) return AEC_MEM_ERROR;     // (the bit lies beyond the input)
+    strm->next_in += offset / 8;
+    strm->avail_in -= offset / 8;
+    s->walk_bit = s->rsi_start_bit = offset % 8;             // (the first RSI starts at that bit of the byte)
+    return AEC_OK;
+}
+
+int aec_decode_range(struct aec_stream *strm, const size_t *rsi_offsets, size_t rsi_offsets_count, size_t pos,
+                     size_t size)
+{
+    try {
+        return decode_range_call(strm, rsi_offsets, rsi_offsets_count, pos, size);
+    } catch (const std::bad_alloc &) { return AEC_MEM_ERROR; }
 }
 
 int aec_buffer_decode(struct aec_stream *strm)

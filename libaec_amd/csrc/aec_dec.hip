@@ -66,6 +66,7 @@ struct DecLaunch {
 };
 template <int BS> void dec_part_bytes(bool seg, bool sums, const DecLaunch &a);      // k_decode<BS, ...>
 template <int BS> void dec_part_wave(const DecLaunch &a);                             // k_decode_wave<BS, ...>
+template <int BS> void dec_part_range(bool wave, const DecLaunch &a);                 // the WIN variants of both
 
 namespace {
 
@@ -353,7 +354,12 @@ __host__ __device__ constexpr uint32_t stg_row(int blk) { return blk == 8 ? (AEC
 // sides), so a lane parses its segment, sums the steps and records for which predecessors the running sum IS the
 // predictor (SegSum: lo <= predecessor - xmin <= hi); nothing is written to `out` or `res`.  k_seg_scan then
 // chains the sums along each RSI, and the second pass is this kernel with SEG alone.
-template <int BS, int BYTES, bool SEG, int kPend, bool SUMS = false>
+//
+// WIN (aec_gpu_decode_range_async: items are the RSIs of a window, rsi_off is the caller's table from the first of them
+// on): a lane that decoded its whole RSI also checks that it ends where the table says the next one starts -- where the
+// table has that entry: rsi_per_chunk (no batch in this mode) is 1 when it holds one behind the last item.  Items and
+// counts are the launch's: a window's last RSI is cut behind the block that holds its last byte (total_blocks).
+template <int BS, int BYTES, bool SEG, int kPend, bool SUMS = false, bool WIN = false>
 __global__ void __launch_bounds__(256, AEC_DEC_MINW)
 k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
          const uint64_t *__restrict__ rsi_off, const SegEntry *__restrict__ seg_table, uint64_t n_rsi,
@@ -363,6 +369,7 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
          const uint32_t *__restrict__ list, const uint32_t *__restrict__ list_cnt)
 {
     static_assert(!SUMS || (SEG && BS != 0), "the summing pass runs per segment on the templated block sizes");
+    static_assert(!WIN || (!SEG && !SUMS), "windows are tables of RSI starts");
     // item counts straight from the record the index pass left on the device (the grid was sized for
     // the most it could find): no host round trip between the two passes
     if (idx) {
@@ -719,6 +726,15 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
         }
         return;
     }
+    if constexpr (WIN) {
+        if (active && ok && nb == c.rsi && r + 1u < n_rsi + rsi_per_chunk) {
+            uint64_t e;
+            if constexpr (BS != 0) e = a0 * 32u + p;
+            else e = br.pos();
+            if (c.flags & F_PAD_RSI) e = (e + 7u) & ~7ull;
+            if (e != rsi_off[r + 1u]) report(res, DEC_DATA_ERROR, r, first_blk + nb - 1u);
+        }
+    }
     // The predictor state behind the LAST item of the batch, as the reference carries it (32 bits, not cut to the
     // sample width: on damaged streams it leaves the range): k_decode_partial continues from it.
     if (!SEG && active && (list ? first_blk + nb == total_blocks : r + 1 == n_rsi)) res->end_bit = x;
@@ -731,8 +747,8 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
 // decodes EVERY item of the batch again, one lane per item, bit by bit from the stream where it lies
 // (BitReader + parse_cds, the sequential reader the index pass and the emulator use): slow, but the answer for
 // any stream the format allows -- a foreign encoder that picks k = 0 for large residuals is within its rights.
-// Items and results as in k_decode (same tables, same output, same status record).
-template <bool SEG>
+// Items and results as in k_decode (same tables, same output, same status record; WIN: the same end check).
+template <bool SEG, bool WIN = false>
 __global__ void __launch_bounds__(64)
 k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
               const uint64_t *__restrict__ rsi_off, const SegEntry *__restrict__ seg_table, uint64_t n_rsi,
@@ -783,6 +799,7 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
         br.init(words, nwords, end_bit, start);
         uint32_t d[kMaxBlockSize];
         uint32_t zrun = 0;
+        bool whole = true;
         for (uint32_t bo = 0; bo < nb; bo++) {                    // (the sample-by-sample path of k_decode)
             bool rf = pp && b0 + bo == 0;
             if (zrun == 0) {
@@ -792,6 +809,7 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
                     report(res, st, r, first_blk + bo);
                     if (batch && st == DEC_DATA_ERROR)
                         atomicMax(&const_cast<DecResult *>(batch)[r / rsi_per_chunk].status, (uint32_t)DEC_DATA_ERROR);
+                    whole = false;
                     break;
                 }
                 if (nz) {
@@ -807,6 +825,12 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
             store_block_generic(dst, d, c, rf, x);
             dst += blk_bytes;
             if (rf) d[0] = 0;
+        }
+        if constexpr (WIN) {
+            if (whole && nb == c.rsi && r + 1u < n_rsi + rsi_per_chunk) {
+                const uint64_t e = (c.flags & F_PAD_RSI) ? (br.pos + 7u) & ~7ull : br.pos;
+                if (e != rsi_off[r + 1u]) report(res, DEC_DATA_ERROR, r, first_blk + nb - 1u);
+            }
         }
         // (as k_decode: the state k_decode_partial continues from)
         if (!SEG && (list ? first_blk + nb == total_blocks : r + 1 == n_rsi)) res->end_bit = x;
@@ -896,7 +920,7 @@ __device__ unsigned long long g_dw_prof[8];      // (diagnostics, AEC_DW_PROF=1:
 #define DW_T1(k) do { } while (0)
 #endif
 
-template <int BS, int BYTES>
+template <int BS, int BYTES, bool WIN = false>
 __global__ void __launch_bounds__(256)
 k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
               const uint64_t *__restrict__ rsi_off, uint64_t n_rsi, uint64_t total_blocks, uint8_t *__restrict__ out,
@@ -1302,6 +1326,13 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
         DW_T1(4);                      // (walk + decode + predictor + store)
         if (bad || fail_lane < 64u) break;
     }
+    // WIN: the end check of k_decode<WIN> (the walk has located every coded data set of the RSI: pos is its end)
+    if constexpr (WIN) {
+        if (lane == 0 && done_blocks == nb && nb == c.rsi && r + 1u < n_rsi + rsi_per_chunk) {
+            const uint64_t e = (c.flags & F_PAD_RSI) ? (pos + 7u) & ~7ull : pos;
+            if (e != rsi_off[r + 1u]) report(res, DEC_DATA_ERROR, r, first_blk + nb - 1u);
+        }
+    }
     // the predictor state behind the LAST item of the batch (k_decode_partial continues from it)
     if (lane == 0 && r + 1 == n_rsi) res->end_bit = pp ? xcarry : 0u;
 }
@@ -1582,7 +1613,55 @@ void dec_part_wave(const DecLaunch &a)
 #endif
 }
 
+// A window of RSIs (launch_decode_range): k_decode_wave<WIN> where launch_decode_any would take the wave kernel, else
+// k_decode<WIN> with the geometry of launch_decode_bytes; loads in flight: 4, which every templated block size takes
+// (one instantiation per container width instead of two or three).  The generic block sizes: the generic lane kernel.
+template <int BS>
+void dec_part_range(bool wave, const DecLaunch &a)
+{
+    const Cfg &c = *a.c;
+    if constexpr (BS == 0) {
+        (void)wave;
+        const DecGeom g = dec_geom(c, a.n_items, 0, 0u);
+        hipLaunchKernelGGL((k_decode<0, 0, false, 2, false, true>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, c,
+                           a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res,
+                           g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc, (SegSum *)nullptr,
+                           (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    } else if (wave) {
+        const uint32_t waves = 2;
+        const dim3 grid((uint32_t)((a.n_items + waves - 1) / waves)), block(64 * waves);
+        const size_t lds = (size_t)waves * dw_wave_words(c) * 4;
+#define AEC_WR(BY)                                                                                                      \
+        hipLaunchKernelGGL((k_decode_wave<BS, BY, true>), grid, block, lds, a.st, c, a.words, a.nwords, a.end_bit, a.rsi_off, \
+                           a.n_items, a.total_blocks, a.out, a.res, a.dump, a.idx, a.batch, a.rpc)
+        switch (c.bytes) {
+        case 1: AEC_WR(1); break;
+        case 2: AEC_WR(2); break;
+        case 3: AEC_WR(3); break;
+        default: AEC_WR(4); break;
+        }
+#undef AEC_WR
+    } else {
+        const uint32_t blk = (uint32_t)BS * c.bytes;
+        const uint64_t avg = a.total_blocks ? a.end_bit / a.total_blocks : 0;
+        const DecGeom g = dec_geom(c, a.n_items, avg, stg_on((int)blk) ? stg_row((int)blk) : 0u);
+#define AEC_LR(BY)                                                                                                      \
+        hipLaunchKernelGGL((k_decode<BS, BY, false, 4, false, true>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, c, \
+                           a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res,      \
+                           g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc, (SegSum *)nullptr,                   \
+                           (const uint32_t *)nullptr, (const uint32_t *)nullptr)
+        switch (c.bytes) {
+        case 1: AEC_LR(1); break;
+        case 2: AEC_LR(2); break;
+        case 3: AEC_LR(3); break;
+        default: AEC_LR(4); break;
+        }
+#undef AEC_LR
+    }
+}
+
 template void dec_part_bytes<AEC_DEC_PART>(bool, bool, const DecLaunch &);
+template void dec_part_range<AEC_DEC_PART>(bool, const DecLaunch &);
 #if AEC_DEC_PART != 0
 template void dec_part_wave<AEC_DEC_PART>(const DecLaunch &);
 #endif
@@ -1597,6 +1676,11 @@ extern template void dec_part_wave<8>(const DecLaunch &);
 extern template void dec_part_wave<16>(const DecLaunch &);
 extern template void dec_part_wave<32>(const DecLaunch &);
 extern template void dec_part_wave<64>(const DecLaunch &);
+extern template void dec_part_range<0>(bool, const DecLaunch &);
+extern template void dec_part_range<8>(bool, const DecLaunch &);
+extern template void dec_part_range<16>(bool, const DecLaunch &);
+extern template void dec_part_range<32>(bool, const DecLaunch &);
+extern template void dec_part_range<64>(bool, const DecLaunch &);
 
 static void dec_part_bytes_bs(uint32_t bs, bool seg, bool sums, const DecLaunch &a)
 {
@@ -1731,6 +1815,40 @@ bool launch_decode(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uin
 {
     return launch_decode_any<false>(c, d_in, in_bytes, d_rsi_off, nullptr, n_rsi, total_blocks, d_out, d_res, st,
                                     prof, d_idx, d_batch, rsi_per_chunk);
+}
+
+bool launch_decode_range(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off, uint64_t n_rsi,
+                         bool next_entry, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res, hipStream_t st,
+                         const PhaseEvents *prof)
+{
+    uint8_t *dump = dump_buffer();
+    if (!dump) return false;
+    hipLaunchKernelGGL(k_dec_result_init, dim3(1), dim3(1), 0, st, d_res);
+    if (n_rsi == 0) return true;
+    if (prof) (void)hipEventRecord(prof->ev[5], st);
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_in);
+    const uint64_t nwords = (in_bytes + 3) / 4;
+    const uint64_t end_bit = (uint64_t)in_bytes * 8;
+    const bool vec_ok = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+    const uint32_t bs = vec_ok ? c.bs : 0;
+    const uint32_t nxt = next_entry ? 1u : 0u;
+    const DecLaunch a{&c, words, nwords, end_bit, d_rsi_off, nullptr, n_rsi, total_blocks, d_out, d_res, st, dump, nullptr,
+                      nullptr, nxt, BareArgs()};
+    const bool wave = bs && dec_wave_wanted(c, n_rsi);
+    switch (bs) {
+    case 8: dec_part_range<8>(wave, a); break;
+    case 16: dec_part_range<16>(wave, a); break;
+    case 32: dec_part_range<32>(wave, a); break;
+    case 64: dec_part_range<64>(wave, a); break;
+    default: dec_part_range<0>(false, a); break;
+    }
+    if (prof) (void)hipEventRecord(prof->ev[6], st);
+    const uint64_t redo_waves = (n_rsi + 63) / 64;
+    hipLaunchKernelGGL((k_decode_redo<false, true>), dim3((uint32_t)(redo_waves < 2048 ? redo_waves : 2048)), dim3(64), 0, st,
+                       c, words, nwords, end_bit, d_rsi_off, (const SegEntry *)nullptr, n_rsi, total_blocks, d_out, d_res,
+                       (const DecResult *)nullptr, (const DecResult *)nullptr, nxt, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr);
+    return true;
 }
 
 void launch_decode_partial(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DecResult *d_idx, uint8_t *d_out,

@@ -46,6 +46,8 @@ struct aec_gpu_ctx {
     ShardCarry *carry;     // device record: what precedes this context's shard (emit_planned)
     void *fused;           // control block of the single-pass encoder (ticket, fail flag, look-back granules)
     size_t fused_bytes;
+    void *range_ws;        // whole blocks of a range decode whose window does not start on an RSI / end on a block
+    size_t range_ws_bytes;
 };
 static_assert(sizeof(aec_gpu_seg_entry) == sizeof(SegEntry), "segment table layout");
 
@@ -81,6 +83,8 @@ int aec_gpu_create(aec_gpu_ctx **out)
     ctx->carry = nullptr;
     ctx->fused = nullptr;
     ctx->fused_bytes = 0;
+    ctx->range_ws = nullptr;
+    ctx->range_ws_bytes = 0;
     ctx->enc_calls = ctx->dec_calls = 0;
     for (auto &set : ctx->ev)
         for (auto &e : set.ev) e = nullptr;
@@ -96,6 +100,7 @@ void aec_gpu_destroy(aec_gpu_ctx *ctx)
     if (ctx->dec_ws) (void)hipFree(ctx->dec_ws);
     if (ctx->carry) (void)hipFree(ctx->carry);
     if (ctx->fused) (void)hipFree(ctx->fused);
+    if (ctx->range_ws) (void)hipFree(ctx->range_ws);
     for (auto &set : ctx->ev)
         for (auto &e : set.ev)
             if (e) (void)hipEventDestroy(e);
@@ -271,6 +276,58 @@ int aec_gpu_decode_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *
     if (!launch_decode(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, n_rsi, total_blocks,
                        static_cast<uint8_t *>(d_out), reinterpret_cast<DecResult *>(d_result),
                        static_cast<hipStream_t>(stream), ctx->dec_events()))
+        return RC_MEM_ERROR;
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+}
+
+int aec_gpu_decode_range_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                               const uint64_t *d_rsi_bit_offsets, uint64_t n_offsets, uint64_t pos, uint64_t size,
+                               void *d_out, aec_gpu_dec_result *d_result, void *stream)
+{
+    Cfg c;
+    const int rc = cfg_from(p, 0, false, &c);
+    if (rc != RC_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_in) & 3u) return RC_CONF_ERROR;
+    const uint64_t blk_bytes = (uint64_t)c.bs * c.bytes, rsi_bytes = blk_bytes * c.rsi;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    DecResult *res = reinterpret_cast<DecResult *>(d_result);
+    (void)hipGetLastError();
+    if (size == 0) {
+        if (!launch_decode_range(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, 0, false, 0, nullptr,
+                                 res, st))
+            return RC_MEM_ERROR;
+        return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    }
+    if (pos + size < pos) return RC_CONF_ERROR;
+    // the RSIs the window needs, and its blocks from the first of them on: the last RSI ends behind the block that
+    // holds the window's last byte
+    const uint64_t r0 = pos / rsi_bytes, r1 = (pos + size - 1) / rsi_bytes;
+    if (r1 >= n_offsets) return RC_CONF_ERROR;
+    const uint64_t n_rsi = r1 - r0 + 1, first = r0 * rsi_bytes;
+    const uint64_t total_blocks = (pos + size - first + blk_bytes - 1) / blk_bytes;
+    // Whole blocks from the window's first RSI on land where the window's bytes go when the window starts on that
+    // RSI and ends on a block; else they go to the context's workspace and the window is copied out of it.
+    uint8_t *out = static_cast<uint8_t *>(d_out);
+    const bool direct = pos == first && size % blk_bytes == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+    if (!direct) {
+        const size_t need = (size_t)(total_blocks * blk_bytes);
+        if (ctx->range_ws_bytes < need) {
+            if (ctx->range_ws) (void)hipFree(ctx->range_ws);
+            ctx->range_ws = nullptr;
+            ctx->range_ws_bytes = 0;
+            const size_t want = (need + need / 4 + 255) & ~(size_t)255;
+            if (hipMalloc(&ctx->range_ws, want) != hipSuccess) {
+                (void)hipGetLastError();
+                return RC_MEM_ERROR;
+            }
+            ctx->range_ws_bytes = want;
+        }
+        out = static_cast<uint8_t *>(ctx->range_ws);
+    }
+    if (!launch_decode_range(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets + r0, n_rsi,
+                             r1 + 1 < n_offsets, total_blocks, out, res, st, ctx->dec_events()))
+        return RC_MEM_ERROR;
+    if (!direct && hipMemcpyAsync(d_out, out + (pos - first), (size_t)size, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return RC_MEM_ERROR;
     return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
 }
@@ -467,6 +524,11 @@ void aec_gpu_trim(aec_gpu_ctx *ctx, size_t keep_bytes)
         ctx->ws = nullptr;
         ctx->ws_bytes = 0;
     }
+    if (ctx->range_ws && ctx->range_ws_bytes > keep_bytes) {
+        (void)hipFree(ctx->range_ws);
+        ctx->range_ws = nullptr;
+        ctx->range_ws_bytes = 0;
+    }
     if (ctx->fused && ctx->fused_bytes > keep_bytes) {
         (void)hipFree(ctx->fused);
         ctx->fused = nullptr;
@@ -486,7 +548,7 @@ void aec_gpu_trim(aec_gpu_ctx *ctx, size_t keep_bytes)
 
 size_t aec_gpu_held_bytes(const aec_gpu_ctx *ctx)
 {
-    return ctx ? ctx->ws_bytes + ctx->fused_bytes + ctx->idx_ws_bytes + ctx->dec_ws_bytes : 0;
+    return ctx ? ctx->ws_bytes + ctx->fused_bytes + ctx->idx_ws_bytes + ctx->dec_ws_bytes + ctx->range_ws_bytes : 0;
 }
 
 int aec_gpu_index_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,

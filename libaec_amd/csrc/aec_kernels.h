@@ -120,6 +120,14 @@ bool launch_decode(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uin
                    hipStream_t stream, const PhaseEvents *prof = nullptr, const DecResult *d_idx = nullptr,
                    const DecResult *d_batch = nullptr, uint32_t rsi_per_chunk = 0);
 
+// The RSIs of a window (aec_gpu_decode_range_async): launch_decode for the n_rsi RSIs whose starts are
+// d_rsi_off[0 .. n_rsi), total_blocks of them (the last RSI cut behind the window's last block), with the WIN variants
+// of the kernels: a lane / wave that decodes its whole RSI checks that it ends at the next entry (rounded up to a byte
+// with AEC_PAD_RSI) -- entry n_rsi only when next_entry -- and reports DEC_DATA_ERROR at that RSI if not.
+bool launch_decode_range(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off, uint64_t n_rsi,
+                         bool next_entry, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res, hipStream_t stream,
+                         const PhaseEvents *prof = nullptr);
+
 // Samples of the coded data set the input ends in (single lane; see k_decode_partial): after
 // launch_decode with the same d_idx / d_out / d_res; their number is left in d_res->pad.
 void launch_decode_partial(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DecResult *d_idx,
