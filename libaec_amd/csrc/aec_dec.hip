@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "aec_kernels.h"
 #include "aec_lane.h"
@@ -48,25 +49,28 @@ struct BareArgs {
     uint64_t avg_hint = 0;         // bits per coded data set where the counts come from an index record
 };
 
-// The launch of one block size's kernels (defined in the object compiled with -DAEC_DEC_PART=BS, see the head of the file)
+// One launch of the decode kernels: what the host entry points fill in and the launchers of one block size's kernels
+// (defined in the object compiled with -DAEC_DEC_PART=BS, see the head of the file) turn into kernel arguments.
 struct DecLaunch {
-    const Cfg *c;
-    const uint32_t *words;
-    uint64_t nwords, end_bit;
-    const uint64_t *rsi_off;
-    const SegEntry *seg_table;
-    uint64_t n_items, total_blocks;
-    uint8_t *out;
-    DecResult *res;
-    hipStream_t st;
-    uint8_t *dump;
-    const DecResult *idx, *batch;
-    uint32_t rpc;
+    const Cfg *c = nullptr;
+    const uint32_t *words = nullptr;
+    uint64_t nwords = 0, end_bit = 0;
+    const uint64_t *rsi_off = nullptr;
+    const SegEntry *seg_table = nullptr;
+    uint64_t n_items = 0, total_blocks = 0;
+    uint8_t *out = nullptr;
+    DecResult *res = nullptr;
+    hipStream_t st = nullptr;
+    uint8_t *dump = nullptr;
+    const DecResult *idx = nullptr, *batch = nullptr;
+    uint32_t rpc = 0;              // RSIs per stream of a batch
+    bool win = false;              // the WIN variants of the kernels (no segments, no sums, no batch) ...
+    bool next_entry = false;       // ... whose table has an entry behind the last item: passed where a batch passes rpc
+    uint32_t rpc_arg() const { return win ? (next_entry ? 1u : 0u) : rpc; }
     BareArgs ba;
 };
 template <int BS> void dec_part_bytes(bool seg, bool sums, const DecLaunch &a);      // k_decode<BS, ...>
 template <int BS> void dec_part_wave(const DecLaunch &a);                             // k_decode_wave<BS, ...>
-template <int BS> void dec_part_range(bool wave, const DecLaunch &a);                 // the WIN variants of both
 
 namespace {
 
@@ -199,6 +203,71 @@ __device__ __forceinline__ void report(DecResult *res, uint32_t status, uint64_t
     atomicMax(&res->status, status);
     atomicMin(reinterpret_cast<unsigned long long *>(&res->bad_rsi), (unsigned long long)rsi);
     atomicMin(reinterpret_cast<unsigned long long *>(&res->tail_blocks), (unsigned long long)block);
+}
+
+// ---- what the decode kernels share: counts, items, error report, end check -----------------------------------
+// Item counts straight from the record the index pass left on the device (the grid was sized for the most it could
+// find): no host round trip between the two passes.
+template <bool SEG>
+__device__ __forceinline__ void dec_counts(const Cfg &c, const DecResult *idx, uint64_t &n_items, uint64_t &total_blocks)
+{
+    if (!idx) return;
+    const uint64_t whole = idx->n_rsi, tail = idx->tail_blocks;
+    n_items = whole + (tail ? 1u : 0u);
+    total_blocks = whole * c.rsi + tail;
+    if (SEG) n_items *= c.segs_per_rsi;               // (items are segments)
+}
+
+// Item r of k_decode_wave's launch (an RSI of a table or of a batch): nb blocks coded from bit `start`, block first_blk
+// of the output.  (k_decode and k_decode_redo keep their own text of this and of report_item, with the segment and list
+// cases: through the two their generated code moved -- k_decode's instruction counts, a VGPR of k_decode_redo<false, WIN>.)
+struct DecItem {
+    uint32_t nb;
+    uint64_t start, first_blk;
+};
+__device__ __forceinline__ DecItem dec_item(const Cfg &c, uint64_t r, uint64_t total_blocks, const uint64_t *__restrict__ rsi_off,
+                                            const DecResult *__restrict__ batch, uint32_t rsi_per_chunk)
+{
+    DecItem it;
+    if (batch) {
+        // batch of independent streams: stream s owns RSIs [s * rsi_per_chunk, (s + 1) * rsi_per_chunk) of
+        // the table and of the output; what its index pass found says how many of them hold blocks
+        const uint64_t sidx = r / rsi_per_chunk;
+        const uint32_t rin = (uint32_t)(r - sidx * rsi_per_chunk);
+        const uint64_t whole = batch[sidx].n_rsi, tail = batch[sidx].tail_blocks;
+        it.nb = rin < whole ? c.rsi : (rin == whole ? (uint32_t)tail : 0u);
+        it.start = it.nb ? rsi_off[r] : 0;
+    } else {
+        const uint64_t left = total_blocks - r * c.rsi;
+        it.nb = left > c.rsi ? c.rsi : (uint32_t)left;
+        it.start = rsi_off[r];
+    }
+    it.first_blk = r * c.rsi;
+    return it;
+}
+
+// report() for item r; in a batch of independent streams the stream's own record says so as well -- one overall
+// record names only the first bad RSI of the whole batch
+__device__ __forceinline__ void report_item(DecResult *res, const DecResult *batch, uint32_t rsi_per_chunk, uint32_t status,
+                                            uint64_t r, uint64_t block)
+{
+    report(res, status, r, block);
+    if (batch && status == DEC_DATA_ERROR)
+        atomicMax(&const_cast<DecResult *>(batch)[r / rsi_per_chunk].status, (uint32_t)DEC_DATA_ERROR);
+}
+
+// WIN (aec_gpu_decode_range_async: items are the RSIs of a window, rsi_off is the caller's table from the first of them
+// on): an item that decoded its whole RSI also checks that it ends (bit `end`, rounded up to a byte with AEC_PAD_RSI)
+// where the table says the next one starts -- where the table has that entry: next_entry (the launch's rsi_per_chunk,
+// there is no batch in this mode) is 1 when it holds one behind the last item.  Items and counts are the launch's: a
+// window's last RSI is cut behind the block that holds its last byte (total_blocks).
+__device__ __forceinline__ void win_end_check(const Cfg &c, DecResult *res, const uint64_t *__restrict__ rsi_off, uint64_t r,
+                                              uint64_t n_rsi, uint32_t next_entry, uint64_t end, uint64_t last_blk)
+{
+    if (r + 1u < n_rsi + next_entry) {
+        const uint64_t e = (c.flags & F_PAD_RSI) ? (end + 7u) & ~7ull : end;
+        if (e != rsi_off[r + 1u]) report(res, DEC_DATA_ERROR, r, last_blk);
+    }
 }
 
 // ---- compressed-stream staging ------------------------------------------------------------------
@@ -355,10 +424,8 @@ __host__ __device__ constexpr uint32_t stg_row(int blk) { return blk == 8 ? (AEC
 // predictor (SegSum: lo <= predecessor - xmin <= hi); nothing is written to `out` or `res`.  k_seg_scan then
 // chains the sums along each RSI, and the second pass is this kernel with SEG alone.
 //
-// WIN (aec_gpu_decode_range_async: items are the RSIs of a window, rsi_off is the caller's table from the first of them
-// on): a lane that decoded its whole RSI also checks that it ends where the table says the next one starts -- where the
-// table has that entry: rsi_per_chunk (no batch in this mode) is 1 when it holds one behind the last item.  Items and
-// counts are the launch's: a window's last RSI is cut behind the block that holds its last byte (total_blocks).
+// WIN: the RSIs of a window, with the end check that win_end_check() describes (this kernel keeps its own text of it and
+// of dec_counts: through the helpers its instruction counts moved, and it has no register to spare).
 template <int BS, int BYTES, bool SEG, int kPend, bool SUMS = false, bool WIN = false>
 __global__ void __launch_bounds__(256, AEC_DEC_MINW)
 k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
@@ -757,12 +824,7 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
               const uint32_t *__restrict__ list_cnt)
 {
     if (!(*reinterpret_cast<volatile uint32_t *>(&res->pad) & kDecRedo)) return;
-    if (idx) {
-        const uint64_t whole = idx->n_rsi, tail = idx->tail_blocks;
-        n_rsi = whole + (tail ? 1u : 0u);
-        total_blocks = whole * c.rsi + tail;
-        if (SEG) n_rsi *= c.segs_per_rsi;
-    }
+    dec_counts<SEG>(c, idx, n_rsi, total_blocks);
     if (!SEG && list) n_rsi = *list_cnt;
     const bool pp = c.flags & F_PREPROCESS;
     const size_t blk_bytes = (size_t)c.bs * c.bytes;
@@ -827,10 +889,7 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
             if (rf) d[0] = 0;
         }
         if constexpr (WIN) {
-            if (whole && nb == c.rsi && r + 1u < n_rsi + rsi_per_chunk) {
-                const uint64_t e = (c.flags & F_PAD_RSI) ? (br.pos + 7u) & ~7ull : br.pos;
-                if (e != rsi_off[r + 1u]) report(res, DEC_DATA_ERROR, r, first_blk + nb - 1u);
-            }
+            if (whole && nb == c.rsi) win_end_check(c, res, rsi_off, r, n_rsi, rsi_per_chunk, br.pos, first_blk + nb - 1u);
         }
         // (as k_decode: the state k_decode_partial continues from)
         if (!SEG && (list ? first_blk + nb == total_blocks : r + 1 == n_rsi)) res->end_bit = x;
@@ -861,7 +920,7 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
 //           data that stays inside the range, one more per clipping block otherwise: exactness never rests on the guess)
 //   store   a lane's block lies behind its neighbour's: whole lines per store instruction, no staging
 // Items, tables, result record and error reporting as k_decode<SEG = false> (no list mode); coded data sets longer than
-// the wave's window of the stream raise kDecRedo like a lane's ring does.  Chosen by launch_decode_any for few, long
+// the wave's window of the stream raise kDecRedo like a lane's ring does.  Chosen by launch_decode_items for few, long
 // enough RSIs (dec_wave_wanted).
 constexpr uint32_t kDwWin = 1024;          // words of the stream a wavefront stages in LDS
 constexpr uint32_t kDwPad = 72;            // zero words behind them (register window, peeks of decode_block)
@@ -928,11 +987,7 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
               const DecResult *__restrict__ batch, uint32_t rsi_per_chunk)
 {
     static_assert(BS == 8 || BS == 16 || BS == 32 || BS == 64, "templated block sizes");
-    if (idx) {
-        const uint64_t whole = idx->n_rsi, tail = idx->tail_blocks;
-        n_rsi = whole + (tail ? 1u : 0u);
-        total_blocks = whole * c.rsi + tail;
-    }
+    dec_counts<false>(c, idx, n_rsi, total_blocks);
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -943,20 +998,9 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
     const uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (r >= n_rsi) return;
     const bool pp = c.flags & F_PREPROCESS, sgn = c.flags & F_SIGNED;
-    uint32_t nb;
-    uint64_t start;
-    if (batch) {
-        const uint64_t sidx = r / rsi_per_chunk;
-        const uint32_t rin = (uint32_t)(r - sidx * rsi_per_chunk);
-        const uint64_t whole = batch[sidx].n_rsi, tail = batch[sidx].tail_blocks;
-        nb = rin < whole ? c.rsi : (rin == whole ? (uint32_t)tail : 0u);
-        start = nb ? rsi_off[r] : 0;
-    } else {
-        const uint64_t left = total_blocks - r * c.rsi;
-        nb = left > c.rsi ? c.rsi : (uint32_t)left;
-        start = rsi_off[r];
-    }
-    const uint64_t first_blk = r * c.rsi;
+    const DecItem it = dec_item(c, r, total_blocks, rsi_off, batch, rsi_per_chunk);
+    const uint32_t nb = it.nb;
+    const uint64_t start = it.start, first_blk = it.first_blk;
     constexpr uint32_t BLK = (uint32_t)BS * (uint32_t)BYTES;
     uint8_t *dst = out + (size_t)first_blk * BLK;
     const uint32_t maxbits = c.id_len + 1u + c.bps + c.bs * c.bps, idmax = (1u << c.id_len) - 1u;
@@ -1276,9 +1320,7 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
                 if (over) {
                     atomicOr(&res->pad, kDecRedo);
                 } else {
-                    report(res, st, r, first_blk + done_blocks + f);
-                    if (batch && st == DEC_DATA_ERROR)
-                        atomicMax(&const_cast<DecResult *>(batch)[r / rsi_per_chunk].status, (uint32_t)DEC_DATA_ERROR);
+                    report_item(res, batch, rsi_per_chunk, st, r, first_blk + done_blocks + f);
                 }
             }
         } else if (fail_lane < 64u) {
@@ -1328,10 +1370,8 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
     }
     // WIN: the end check of k_decode<WIN> (the walk has located every coded data set of the RSI: pos is its end)
     if constexpr (WIN) {
-        if (lane == 0 && done_blocks == nb && nb == c.rsi && r + 1u < n_rsi + rsi_per_chunk) {
-            const uint64_t e = (c.flags & F_PAD_RSI) ? (pos + 7u) & ~7ull : pos;
-            if (e != rsi_off[r + 1u]) report(res, DEC_DATA_ERROR, r, first_blk + nb - 1u);
-        }
+        if (lane == 0 && done_blocks == nb && nb == c.rsi)
+            win_end_check(c, res, rsi_off, r, n_rsi, rsi_per_chunk, pos, first_blk + nb - 1u);
     }
     // the predictor state behind the LAST item of the batch (k_decode_partial continues from it)
     if (lane == 0 && r + 1 == n_rsi) res->end_bit = pp ? xcarry : 0u;
@@ -1502,43 +1542,81 @@ DecGeom dec_geom(const Cfg &c, uint64_t n_rsi, uint64_t avg_cds_bits, uint32_t s
     return g;
 }
 
-template <int BS, bool SEG, bool SUMS = false>
-void launch_decode_bytes(const Cfg &c, const uint32_t *words, uint64_t nwords, uint64_t end_bit,
-                         const uint64_t *rsi_off, const SegEntry *seg_table, uint64_t n_rsi,
-                         uint64_t total_blocks, uint8_t *out, DecResult *res, hipStream_t st, uint8_t *dump,
-                         const DecResult *idx, const DecResult *batch, uint32_t rpc, const BareArgs &ba = BareArgs())
+// ---- DecLaunch -> kernel arguments: one place per kernel family ------------------------------------------------
+// (the kernels take their arguments one by one: __restrict__ on a kernel parameter is what tells the compiler that the
+// tables, the stream and the output do not alias, and members of a by-value struct lose it)
+template <int BS, int BYTES, bool SEG, int KP, bool SUMS, bool WIN>
+void go_lanes(const DecLaunch &a, const DecGeom &g)
 {
-    const uint32_t blk = (uint32_t)BS * c.bytes;
-    // (counts taken from the index record: the average coded data set is not known here unless the caller says
-    // so -- full ring)
-    const uint64_t avg = (total_blocks && !idx && !batch) ? end_bit / total_blocks : ba.avg_hint;
-    const DecGeom g = dec_geom(c, n_rsi, avg, (!SUMS && stg_on((int)blk)) ? stg_row((int)blk) : 0u);
-    const dim3 block(64 * g.waves), grid(g.grid);
-    // loads in flight per block iteration (see kPend): sized for the average coded data set where the caller
-    // knows it, for the worst case of large blocks where it does not
-    const uint32_t e_kp = tune("AEC_DEC_KP", 0);               // (diagnostic: force 2, 4 or 8)
-    // (measured: 2 up to the 256 bits per block they feed -- C3 at 247: 2.70 ms against 2.74 with 4 --, 8 for the
-    // 720 bits of typical.dat's blocks: 5.8 ms against 7.1 with 4 and 7.8 with 2)
-    int kp = BS >= 32 ? (avg == 0 || avg > 512 ? 8 : (avg > 256 ? 4 : 2)) : (avg > 256 ? 4 : 2);
-    if (e_kp) kp = e_kp >= 8 ? (BS >= 32 ? 8 : 4) : (e_kp >= 4 ? 4 : 2);
-#define AEC_GO2(B, KP)                                                                                  \
-    hipLaunchKernelGGL((k_decode<BS, B, SEG, KP, SUMS>), grid, block, g.lds_bytes, st, c, words, nwords, end_bit, \
-                       rsi_off, seg_table, n_rsi, total_blocks, out, res, g.ring_words, g.maxw, g.needw, dump, idx, batch, rpc, \
-                       ba.sums, ba.list, ba.list_cnt)
-#define AEC_GO(B)                                                                                   \
-    do {                                                                                            \
-        if (kp == 2) AEC_GO2(B, 2);                                                                 \
-        else if (kp == 4) AEC_GO2(B, 4);                                                            \
-        else if (BS >= 32) AEC_GO2(B, (BS >= 32 ? 8 : 4));                                          \
-    } while (0)
+    hipLaunchKernelGGL((k_decode<BS, BYTES, SEG, KP, SUMS, WIN>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c,
+                       a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res,
+                       g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc_arg(), a.ba.sums, a.ba.list, a.ba.list_cnt);
+}
+
+template <int BS, int BYTES, bool WIN>
+void go_wave(const DecLaunch &a, const DecGeom &g)
+{
+    hipLaunchKernelGGL((k_decode_wave<BS, BYTES, WIN>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c, a.words,
+                       a.nwords, a.end_bit, a.rsi_off, a.n_items, a.total_blocks, a.out, a.res, a.dump, a.idx, a.batch, a.rpc_arg());
+}
+
+template <bool SEG, bool WIN>
+void go_redo(const DecLaunch &a, const DecGeom &g)
+{
+    hipLaunchKernelGGL((k_decode_redo<SEG, WIN>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c, a.words, a.nwords,
+                       a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res, a.idx, a.batch, a.rpc_arg(),
+                       a.ba.list, a.ba.list_cnt);
+}
+
+// f(std::integral_constant<int, B>) for the container width B of the configuration
+template <class F>
+void with_container_bytes(const Cfg &c, F &&f)
+{
     switch (c.bytes) {
-    case 1: AEC_GO(1); break;
-    case 2: AEC_GO(2); break;
-    case 3: AEC_GO(3); break;
-    default: AEC_GO(4); break;
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 4>()); break;
     }
-#undef AEC_GO
-#undef AEC_GO2
+}
+
+// k_decode for the items of a launch.  A window (a.win) takes the geometry of any other launch and 4 loads in flight,
+// which every templated block size takes: one instantiation per container width instead of two or three.
+template <int BS, bool SEG, bool SUMS>
+void launch_lanes(const DecLaunch &a)
+{
+    const Cfg &c = *a.c;
+    [[maybe_unused]] constexpr bool kCanWin = !SEG && !SUMS;
+    if constexpr (BS == 0) {
+        // generic block sizes and containers: the sample-by-sample reader has no second attempt: full ring
+        const DecGeom g = dec_geom(c, a.n_items, 0, 0u);
+        if constexpr (kCanWin) {
+            if (a.win) return go_lanes<0, 0, false, 2, false, true>(a, g);
+        }
+        go_lanes<0, 0, SEG, 2, false, false>(a, g);
+    } else {
+        const uint32_t blk = (uint32_t)BS * c.bytes;
+        // (counts taken from the index record: the average coded data set is not known here unless the caller says
+        // so -- full ring)
+        const uint64_t avg = (a.total_blocks && !a.idx && !a.batch) ? a.end_bit / a.total_blocks : a.ba.avg_hint;
+        const DecGeom g = dec_geom(c, a.n_items, avg, (!SUMS && stg_on((int)blk)) ? stg_row((int)blk) : 0u);
+        // loads in flight per block iteration (see kPend): sized for the average coded data set where the caller
+        // knows it, for the worst case of large blocks where it does not
+        const uint32_t e_kp = tune("AEC_DEC_KP", 0);               // (diagnostic: force 2, 4 or 8)
+        // (measured: 2 up to the 256 bits per block they feed -- C3 at 247: 2.70 ms against 2.74 with 4 --, 8 for the
+        // 720 bits of typical.dat's blocks: 5.8 ms against 7.1 with 4 and 7.8 with 2)
+        int kp = BS >= 32 ? (avg == 0 || avg > 512 ? 8 : (avg > 256 ? 4 : 2)) : (avg > 256 ? 4 : 2);
+        if (e_kp) kp = e_kp >= 8 ? (BS >= 32 ? 8 : 4) : (e_kp >= 4 ? 4 : 2);
+        with_container_bytes(c, [&](auto by) {
+            constexpr int B = decltype(by)::value;
+            if constexpr (kCanWin) {
+                if (a.win) return go_lanes<BS, B, false, 4, false, true>(a, g);
+            }
+            if (kp == 2) go_lanes<BS, B, SEG, 2, SUMS, false>(a, g);
+            else if (kp == 4) go_lanes<BS, B, SEG, 4, SUMS, false>(a, g);
+            else if constexpr (BS >= 32) go_lanes<BS, B, SEG, 8, SUMS, false>(a, g);
+        });
+    }
 }
 
 }  // namespace
@@ -1548,43 +1626,21 @@ void launch_decode_bytes(const Cfg &c, const uint32_t *words, uint64_t nwords, u
 template <int BS>
 void dec_part_bytes(bool seg, bool sums, const DecLaunch &a)
 {
-    const Cfg &c = *a.c;
-    if constexpr (BS == 0) {
-        // generic block sizes and containers: the sample-by-sample reader has no second attempt: full ring
-        const DecGeom g = dec_geom(c, a.n_items, 0, 0u);
-        if (seg)
-            hipLaunchKernelGGL((k_decode<0, 0, true, 2>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, c, a.words, a.nwords,
-                               a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res, g.ring_words, g.maxw,
-                               g.needw, a.dump, a.idx, a.batch, a.rpc, (SegSum *)nullptr, (const uint32_t *)nullptr,
-                               (const uint32_t *)nullptr);
-        else
-            hipLaunchKernelGGL((k_decode<0, 0, false, 2>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, c, a.words, a.nwords,
-                               a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res, g.ring_words, g.maxw,
-                               g.needw, a.dump, a.idx, a.batch, a.rpc, (SegSum *)nullptr, (const uint32_t *)nullptr,
-                               (const uint32_t *)nullptr);
-    } else if (sums) {
-        launch_decode_bytes<BS, true, true>(c, a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks,
-                                            a.out, a.res, a.st, a.dump, a.idx, a.batch, a.rpc, a.ba);
-    } else if (seg) {
-        launch_decode_bytes<BS, true, false>(c, a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks,
-                                             a.out, a.res, a.st, a.dump, a.idx, a.batch, a.rpc, a.ba);
-    } else {
-        launch_decode_bytes<BS, false, false>(c, a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks,
-                                              a.out, a.res, a.st, a.dump, a.idx, a.batch, a.rpc, a.ba);
+    if constexpr (BS != 0) {
+        if (sums) return launch_lanes<BS, true, true>(a);
     }
+    if (seg) launch_lanes<BS, true, false>(a);
+    else launch_lanes<BS, false, false>(a);
 }
 
 template <int BS>
 void dec_part_wave(const DecLaunch &a)
 {
     const Cfg &c = *a.c;
-    constexpr int B = BS;
-    const uint32_t waves = 2;                            // (~24 KB of LDS per wavefront: six of them on a CU)
-    const dim3 grid((uint32_t)((a.n_items + waves - 1) / waves)), block(64 * waves);
-    const size_t lds = (size_t)waves * dw_wave_words(c) * 4;
-#define AEC_WV2(BY)                                                                                                     \
-    hipLaunchKernelGGL((k_decode_wave<B, BY>), grid, block, lds, a.st, c, a.words, a.nwords, a.end_bit, a.rsi_off, a.n_items, \
-                       a.total_blocks, a.out, a.res, a.dump, a.idx, a.batch, a.rpc)
+    DecGeom g = {};
+    g.waves = 2;                                         // (~24 KB of LDS per wavefront: six of them on a CU)
+    g.grid = (uint32_t)((a.n_items + g.waves - 1) / g.waves);
+    g.lds_bytes = (size_t)g.waves * dw_wave_words(c) * 4;
 #ifdef AEC_TUNING
     static const bool dw_prof = tune("AEC_DW_PROF", 0) != 0;
     if (dw_prof) {
@@ -1592,13 +1648,11 @@ void dec_part_wave(const DecLaunch &a)
         (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dw_prof), z, sizeof(z), 0, hipMemcpyHostToDevice, a.st);
     }
 #endif
-    switch (c.bytes) {
-    case 1: AEC_WV2(1); break;
-    case 2: AEC_WV2(2); break;
-    case 3: AEC_WV2(3); break;
-    default: AEC_WV2(4); break;
-    }
-#undef AEC_WV2
+    with_container_bytes(c, [&](auto by) {
+        constexpr int B = decltype(by)::value;
+        if (a.win) go_wave<BS, B, true>(a, g);
+        else go_wave<BS, B, false>(a, g);
+    });
 #ifdef AEC_TUNING
     if (dw_prof) {
         static int reports = 0;
@@ -1613,55 +1667,7 @@ void dec_part_wave(const DecLaunch &a)
 #endif
 }
 
-// A window of RSIs (launch_decode_range): k_decode_wave<WIN> where launch_decode_any would take the wave kernel, else
-// k_decode<WIN> with the geometry of launch_decode_bytes; loads in flight: 4, which every templated block size takes
-// (one instantiation per container width instead of two or three).  The generic block sizes: the generic lane kernel.
-template <int BS>
-void dec_part_range(bool wave, const DecLaunch &a)
-{
-    const Cfg &c = *a.c;
-    if constexpr (BS == 0) {
-        (void)wave;
-        const DecGeom g = dec_geom(c, a.n_items, 0, 0u);
-        hipLaunchKernelGGL((k_decode<0, 0, false, 2, false, true>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, c,
-                           a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res,
-                           g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc, (SegSum *)nullptr,
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-    } else if (wave) {
-        const uint32_t waves = 2;
-        const dim3 grid((uint32_t)((a.n_items + waves - 1) / waves)), block(64 * waves);
-        const size_t lds = (size_t)waves * dw_wave_words(c) * 4;
-#define AEC_WR(BY)                                                                                                      \
-        hipLaunchKernelGGL((k_decode_wave<BS, BY, true>), grid, block, lds, a.st, c, a.words, a.nwords, a.end_bit, a.rsi_off, \
-                           a.n_items, a.total_blocks, a.out, a.res, a.dump, a.idx, a.batch, a.rpc)
-        switch (c.bytes) {
-        case 1: AEC_WR(1); break;
-        case 2: AEC_WR(2); break;
-        case 3: AEC_WR(3); break;
-        default: AEC_WR(4); break;
-        }
-#undef AEC_WR
-    } else {
-        const uint32_t blk = (uint32_t)BS * c.bytes;
-        const uint64_t avg = a.total_blocks ? a.end_bit / a.total_blocks : 0;
-        const DecGeom g = dec_geom(c, a.n_items, avg, stg_on((int)blk) ? stg_row((int)blk) : 0u);
-#define AEC_LR(BY)                                                                                                      \
-        hipLaunchKernelGGL((k_decode<BS, BY, false, 4, false, true>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, c, \
-                           a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res,      \
-                           g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc, (SegSum *)nullptr,                   \
-                           (const uint32_t *)nullptr, (const uint32_t *)nullptr)
-        switch (c.bytes) {
-        case 1: AEC_LR(1); break;
-        case 2: AEC_LR(2); break;
-        case 3: AEC_LR(3); break;
-        default: AEC_LR(4); break;
-        }
-#undef AEC_LR
-    }
-}
-
 template void dec_part_bytes<AEC_DEC_PART>(bool, bool, const DecLaunch &);
-template void dec_part_range<AEC_DEC_PART>(bool, const DecLaunch &);
 #if AEC_DEC_PART != 0
 template void dec_part_wave<AEC_DEC_PART>(const DecLaunch &);
 #endif
@@ -1676,22 +1682,6 @@ extern template void dec_part_wave<8>(const DecLaunch &);
 extern template void dec_part_wave<16>(const DecLaunch &);
 extern template void dec_part_wave<32>(const DecLaunch &);
 extern template void dec_part_wave<64>(const DecLaunch &);
-extern template void dec_part_range<0>(bool, const DecLaunch &);
-extern template void dec_part_range<8>(bool, const DecLaunch &);
-extern template void dec_part_range<16>(bool, const DecLaunch &);
-extern template void dec_part_range<32>(bool, const DecLaunch &);
-extern template void dec_part_range<64>(bool, const DecLaunch &);
-
-static void dec_part_bytes_bs(uint32_t bs, bool seg, bool sums, const DecLaunch &a)
-{
-    switch (bs) {
-    case 8: dec_part_bytes<8>(seg, sums, a); break;
-    case 16: dec_part_bytes<16>(seg, sums, a); break;
-    case 32: dec_part_bytes<32>(seg, sums, a); break;
-    case 64: dec_part_bytes<64>(seg, sums, a); break;
-    default: dec_part_bytes<0>(seg, sums, a); break;
-    }
-}
 
 // Few RSIs, each long enough to keep a wavefront's lanes busy: a wavefront per RSI (k_decode_wave) instead of a lane.
 // A lane per RSI needs ~260 000 RSIs to fill the chip and takes as long as ONE RSI's serial chain however few there
@@ -1710,41 +1700,64 @@ static bool dec_wave_wanted(const Cfg &c, uint64_t n_items)
     return c.rsi >= least && n_items <= scaled;
 }
 
-template <bool SEG>
-static bool launch_decode_any(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off,
-                              const SegEntry *d_seg, uint64_t n_items, uint64_t total_blocks, uint8_t *d_out,
-                              DecResult *d_res, hipStream_t st, const PhaseEvents *prof,
-                              const DecResult *d_idx = nullptr, const DecResult *d_batch = nullptr, uint32_t rpc = 0)
+// The lane kernel (wave = false) or the wave kernel of block size bs for one launch (0: the generic lane kernel)
+static void launch_items(uint32_t bs, bool seg, bool sums, bool wave, const DecLaunch &a)
 {
-    uint8_t *dump = dump_buffer();
-    if (!dump) return false;
-    hipLaunchKernelGGL(k_dec_result_init, dim3(1), dim3(1), 0, st, d_res);
-    if (n_items == 0) return true;
-    if (prof) (void)hipEventRecord(prof->ev[5], st);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_in);
-    const uint64_t nwords = (in_bytes + 3) / 4;
-    const uint64_t end_bit = (uint64_t)in_bytes * 8;
-    // vector stores need 16-byte aligned blocks
-    const bool vec_ok = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
-    const uint32_t bs = vec_ok ? c.bs : 0;
-    DecLaunch a{&c, words, nwords, end_bit, d_rsi_off, d_seg, n_items, total_blocks, d_out, d_res, st, dump, d_idx, d_batch, rpc,
-                BareArgs()};
-    if (!SEG && bs && dec_wave_wanted(c, n_items)) {
-        switch (bs) {
-        case 8: dec_part_wave<8>(a); break;
-        case 16: dec_part_wave<16>(a); break;
-        case 32: dec_part_wave<32>(a); break;
-        default: dec_part_wave<64>(a); break;
-        }
-    } else {
-        dec_part_bytes_bs(bs, SEG, false, a);
+    switch (bs) {
+    case 8: wave ? dec_part_wave<8>(a) : dec_part_bytes<8>(seg, sums, a); break;
+    case 16: wave ? dec_part_wave<16>(a) : dec_part_bytes<16>(seg, sums, a); break;
+    case 32: wave ? dec_part_wave<32>(a) : dec_part_bytes<32>(seg, sums, a); break;
+    case 64: wave ? dec_part_wave<64>(a) : dec_part_bytes<64>(seg, sums, a); break;
+    default: dec_part_bytes<0>(seg, sums, a); break;
     }
+}
+
+// k_decode_redo behind the kernels of launch `a` (returns at once unless one of them raised kDecRedo)
+static void launch_redo(bool seg, const DecLaunch &a)
+{
+    const uint64_t waves = (a.n_items + 63) / 64;
+    DecGeom g = {};
+    g.waves = 1;
+    g.grid = (uint32_t)(waves < 2048 ? waves : 2048);
+    if (a.win) go_redo<false, true>(a, g);
+    else if (seg) go_redo<true, false>(a, g);
+    else go_redo<false, false>(a, g);
+}
+
+// What every decode call starts with: the stream as words, the buffer idle lanes store to, a fresh result record.
+static bool dec_begin(DecLaunch &a, const Cfg &c, const uint8_t *d_in, size_t in_bytes, DecResult *d_res, hipStream_t st)
+{
+    a.c = &c;
+    a.words = reinterpret_cast<const uint32_t *>(d_in);
+    a.nwords = (in_bytes + 3) / 4;
+    a.end_bit = (uint64_t)in_bytes * 8;
+    a.res = d_res;
+    a.st = st;
+    a.dump = dump_buffer();
+    if (!a.dump) return false;
+    hipLaunchKernelGGL(k_dec_result_init, dim3(1), dim3(1), 0, st, d_res);
+    return true;
+}
+
+// vector stores need 16-byte aligned blocks: the generic kernel (block size 0) takes the rest
+static uint32_t dec_block_size(const Cfg &c, const uint8_t *d_out)
+{
+    return (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 ? c.bs : 0u;
+}
+
+// The one host entry: `a` names the items (RSI starts in rsi_off or the encoder's segment table, counts, output, and
+// for a window a.win, with a.next_entry where the table has an entry behind the last item); the wave kernel where
+// dec_wave_wanted says so, the lane kernel else, k_decode_redo behind either.
+static bool launch_decode_items(const Cfg &c, const uint8_t *d_in, size_t in_bytes, bool seg, DecLaunch a, DecResult *d_res,
+                                hipStream_t st, const PhaseEvents *prof)
+{
+    if (!dec_begin(a, c, d_in, in_bytes, d_res, st)) return false;
+    if (a.n_items == 0) return true;
+    if (prof) (void)hipEventRecord(prof->ev[5], st);
+    const uint32_t bs = dec_block_size(c, a.out);
+    launch_items(bs, seg, false, !seg && bs && dec_wave_wanted(c, a.n_items), a);
     if (prof) (void)hipEventRecord(prof->ev[6], st);
-    // (behind the timed kernel: returns at once unless k_decode raised kDecRedo)
-    const uint64_t redo_waves = (n_items + 63) / 64;
-    hipLaunchKernelGGL((k_decode_redo<SEG>), dim3((uint32_t)(redo_waves < 2048 ? redo_waves : 2048)), dim3(64), 0, st, c,
-                       words, nwords, end_bit, d_rsi_off, d_seg, n_items, total_blocks, d_out, d_res, d_idx, d_batch, rpc,
-                       (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    launch_redo(seg, a);                                 // (behind the timed kernel)
     return true;
 }
 
@@ -1760,11 +1773,7 @@ k_seg_scan(const Cfg c, const uint64_t *__restrict__ rsi_off, const uint64_t *__
            const SegSum *__restrict__ sums, uint64_t n_rsi, uint64_t total_blocks, const DecResult *__restrict__ idx,
            SegEntry *__restrict__ table, uint32_t *__restrict__ list, uint32_t *__restrict__ list_cnt)
 {
-    if (idx) {
-        const uint64_t whole = idx->n_rsi, tail = idx->tail_blocks;
-        n_rsi = whole + (tail ? 1u : 0u);
-        total_blocks = whole * c.rsi + tail;
-    }
+    dec_counts<false>(c, idx, n_rsi, total_blocks);
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rsi) return;
     uint64_t left = total_blocks > r * c.rsi ? total_blocks - r * c.rsi : 0u;
@@ -1813,42 +1822,41 @@ bool launch_decode(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uin
                    uint64_t n_rsi, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res, hipStream_t st,
                    const PhaseEvents *prof, const DecResult *d_idx, const DecResult *d_batch, uint32_t rsi_per_chunk)
 {
-    return launch_decode_any<false>(c, d_in, in_bytes, d_rsi_off, nullptr, n_rsi, total_blocks, d_out, d_res, st,
-                                    prof, d_idx, d_batch, rsi_per_chunk);
+    DecLaunch a;
+    a.rsi_off = d_rsi_off;
+    a.n_items = n_rsi;
+    a.total_blocks = total_blocks;
+    a.out = d_out;
+    a.idx = d_idx;
+    a.batch = d_batch;
+    a.rpc = rsi_per_chunk;
+    return launch_decode_items(c, d_in, in_bytes, false, a, d_res, st, prof);
 }
 
 bool launch_decode_range(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off, uint64_t n_rsi,
                          bool next_entry, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res, hipStream_t st,
                          const PhaseEvents *prof)
 {
-    uint8_t *dump = dump_buffer();
-    if (!dump) return false;
-    hipLaunchKernelGGL(k_dec_result_init, dim3(1), dim3(1), 0, st, d_res);
-    if (n_rsi == 0) return true;
-    if (prof) (void)hipEventRecord(prof->ev[5], st);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_in);
-    const uint64_t nwords = (in_bytes + 3) / 4;
-    const uint64_t end_bit = (uint64_t)in_bytes * 8;
-    const bool vec_ok = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
-    const uint32_t bs = vec_ok ? c.bs : 0;
-    const uint32_t nxt = next_entry ? 1u : 0u;
-    const DecLaunch a{&c, words, nwords, end_bit, d_rsi_off, nullptr, n_rsi, total_blocks, d_out, d_res, st, dump, nullptr,
-                      nullptr, nxt, BareArgs()};
-    const bool wave = bs && dec_wave_wanted(c, n_rsi);
-    switch (bs) {
-    case 8: dec_part_range<8>(wave, a); break;
-    case 16: dec_part_range<16>(wave, a); break;
-    case 32: dec_part_range<32>(wave, a); break;
-    case 64: dec_part_range<64>(wave, a); break;
-    default: dec_part_range<0>(false, a); break;
-    }
-    if (prof) (void)hipEventRecord(prof->ev[6], st);
-    const uint64_t redo_waves = (n_rsi + 63) / 64;
-    hipLaunchKernelGGL((k_decode_redo<false, true>), dim3((uint32_t)(redo_waves < 2048 ? redo_waves : 2048)), dim3(64), 0, st,
-                       c, words, nwords, end_bit, d_rsi_off, (const SegEntry *)nullptr, n_rsi, total_blocks, d_out, d_res,
-                       (const DecResult *)nullptr, (const DecResult *)nullptr, nxt, (const uint32_t *)nullptr,
-                       (const uint32_t *)nullptr);
-    return true;
+    DecLaunch a;
+    a.rsi_off = d_rsi_off;
+    a.n_items = n_rsi;
+    a.total_blocks = total_blocks;
+    a.out = d_out;
+    a.win = true;
+    a.next_entry = next_entry;
+    return launch_decode_items(c, d_in, in_bytes, false, a, d_res, st, prof);
+}
+
+bool launch_decode_segments(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const SegEntry *d_seg_table,
+                            uint64_t n_seg, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res,
+                            hipStream_t st, const PhaseEvents *prof)
+{
+    DecLaunch a;
+    a.seg_table = d_seg_table;
+    a.n_items = n_seg;
+    a.total_blocks = total_blocks;
+    a.out = d_out;
+    return launch_decode_items(c, d_in, in_bytes, true, a, d_res, st, prof);
 }
 
 void launch_decode_partial(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DecResult *d_idx, uint8_t *d_out,
@@ -1858,7 +1866,6 @@ void launch_decode_partial(const Cfg &c, const uint8_t *d_in, size_t in_bytes, c
                        (uint64_t)((in_bytes + 3) / 4), (uint64_t)in_bytes * 8, d_idx, d_out, d_res);
 }
 
-// Workspace of launch_decode_bare for up to max_rsi RSIs: sums and table per segment, list per RSI, counter.
 bool decode_bare_supported(const Cfg &c)
 {
     // (from eight segments per RSI on: an RSI in which a sample comes within reach of the ends of the range falls
@@ -1867,12 +1874,22 @@ bool decode_bare_supported(const Cfg &c)
     return c.segs_per_rsi >= 8u && (c.bs == 8u || c.bs == 16u || c.bs == 32u || c.bs == 64u);
 }
 
-size_t decode_bare_workspace_bytes(const Cfg &c, uint64_t max_rsi)
+// Workspace of launch_decode_bare for up to n_rsi RSIs: sums and table per segment, list per RSI, counter (byte offsets)
+struct BareWs { size_t sums, table, list, list_cnt, bytes; };
+static BareWs bare_ws(const Cfg &c, uint64_t n_rsi)
 {
-    const uint64_t nseg = max_rsi * c.segs_per_rsi;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return up(nseg * sizeof(SegSum)) + up(nseg * sizeof(SegEntry)) + up(max_rsi * 4) + 256;
+    const uint64_t nseg = n_rsi * c.segs_per_rsi;
+    BareWs w;
+    w.sums = 0;
+    w.table = w.sums + up(nseg * sizeof(SegSum));
+    w.list = w.table + up(nseg * sizeof(SegEntry));
+    w.list_cnt = w.list + up(n_rsi * 4);
+    w.bytes = w.list_cnt + 256;
+    return w;
 }
+
+size_t decode_bare_workspace_bytes(const Cfg &c, uint64_t max_rsi) { return bare_ws(c, max_rsi).bytes; }
 
 // A bare stream whose index pass also found the segment starts (d_seg_bits[r * segs_per_rsi + j], ~0 = unknown):
 // summing pass, scan per RSI, one lane per segment for the RSIs that can be taken that way, one lane per RSI for
@@ -1882,64 +1899,44 @@ bool launch_decode_bare(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
                         DecResult *d_res, hipStream_t st, const PhaseEvents *prof, const DecResult *d_idx, void *d_ws,
                         size_t ws_bytes, uint64_t avg_cds_hint)
 {
-    const bool vec_ok = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
-    if (!decode_bare_supported(c) || !vec_ok || !d_seg_bits || !d_ws || ws_bytes < decode_bare_workspace_bytes(c, n_rsi))
+    const BareWs ws = bare_ws(c, n_rsi);
+    if (!decode_bare_supported(c) || !dec_block_size(c, d_out) || !d_seg_bits || !d_ws || ws_bytes < ws.bytes)
         return launch_decode(c, d_in, in_bytes, d_rsi_off, n_rsi, total_blocks, d_out, d_res, st, prof, d_idx);
-    uint8_t *dump = dump_buffer();
-    if (!dump) return false;
-    hipLaunchKernelGGL(k_dec_result_init, dim3(1), dim3(1), 0, st, d_res);
+    DecLaunch sum;
+    if (!dec_begin(sum, c, d_in, in_bytes, d_res, st)) return false;
     if (n_rsi == 0) return true;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const uint64_t n_items = n_rsi * c.segs_per_rsi;
     uint8_t *w = static_cast<uint8_t *>(d_ws);
-    SegSum *sums = reinterpret_cast<SegSum *>(w);
-    SegEntry *table = reinterpret_cast<SegEntry *>(w + up(n_items * sizeof(SegSum)));
-    uint32_t *list = reinterpret_cast<uint32_t *>(w + up(n_items * sizeof(SegSum)) + up(n_items * sizeof(SegEntry)));
-    uint32_t *list_cnt = list + ((up(n_rsi * 4)) / 4);
+    SegEntry *table = reinterpret_cast<SegEntry *>(w + ws.table);
+    uint32_t *list = reinterpret_cast<uint32_t *>(w + ws.list), *list_cnt = reinterpret_cast<uint32_t *>(w + ws.list_cnt);
     (void)hipMemsetAsync(list_cnt, 0, 4, st);
     if (prof) (void)hipEventRecord(prof->ev[5], st);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_in);
-    const uint64_t nwords = (in_bytes + 3) / 4;
-    const uint64_t end_bit = (uint64_t)in_bytes * 8;
-    BareArgs a_sum, a_seg, a_list;
-    a_sum.sums = sums;
-    a_list.list = list;
-    a_list.list_cnt = list_cnt;
-    a_sum.avg_hint = a_seg.avg_hint = a_list.avg_hint = avg_cds_hint;
-    // (summing pass over the segments, scan per RSI, a lane per segment, a lane per RSI of the list)
-    DecLaunch l{&c, words, nwords, end_bit, d_seg_bits, nullptr, n_items, total_blocks, nullptr, d_res, st, dump, d_idx, nullptr, 0u,
-                a_sum};
-    dec_part_bytes_bs(c.bs, true, true, l);
+    // the summing pass over the segments (items: the segment starts of the index pass, nothing written to the output)
+    sum.rsi_off = d_seg_bits;
+    sum.n_items = n_rsi * c.segs_per_rsi;
+    sum.total_blocks = total_blocks;
+    sum.idx = d_idx;
+    sum.ba.avg_hint = avg_cds_hint;
+    DecLaunch seg = sum, rest = sum;
+    sum.ba.sums = reinterpret_cast<SegSum *>(w + ws.sums);
+    // a lane per segment of the table the scan fills in
+    seg.rsi_off = nullptr;
+    seg.seg_table = table;
+    seg.out = d_out;
+    // a lane per RSI of the list
+    rest.rsi_off = d_rsi_off;
+    rest.n_items = n_rsi;
+    rest.out = d_out;
+    rest.ba.list = list;
+    rest.ba.list_cnt = list_cnt;
+    launch_items(c.bs, true, true, false, sum);
     hipLaunchKernelGGL(k_seg_scan, dim3((uint32_t)((n_rsi + 255) / 256)), dim3(256), 0, st, c, d_rsi_off, d_seg_bits,
-                       sums, n_rsi, total_blocks, d_idx, table, list, list_cnt);
-    l.rsi_off = nullptr;
-    l.seg_table = table;
-    l.out = d_out;
-    l.ba = a_seg;
-    dec_part_bytes_bs(c.bs, true, false, l);
-    l.rsi_off = d_rsi_off;
-    l.seg_table = nullptr;
-    l.n_items = n_rsi;
-    l.ba = a_list;
-    dec_part_bytes_bs(c.bs, false, false, l);
+                       sum.ba.sums, n_rsi, total_blocks, d_idx, table, list, list_cnt);
+    launch_items(c.bs, true, false, false, seg);
+    launch_items(c.bs, false, false, false, rest);
     if (prof) (void)hipEventRecord(prof->ev[6], st);
-    // (behind the timed kernels: return at once unless a k_decode raised kDecRedo)
-    const uint64_t w_seg = (n_items + 63) / 64, w_rsi = (n_rsi + 63) / 64;
-    hipLaunchKernelGGL((k_decode_redo<true>), dim3((uint32_t)(w_seg < 2048 ? w_seg : 2048)), dim3(64), 0, st, c, words,
-                       nwords, end_bit, (const uint64_t *)nullptr, table, n_items, total_blocks, d_out, d_res, d_idx,
-                       (const DecResult *)nullptr, 0u, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-    hipLaunchKernelGGL((k_decode_redo<false>), dim3((uint32_t)(w_rsi < 2048 ? w_rsi : 2048)), dim3(64), 0, st, c, words,
-                       nwords, end_bit, d_rsi_off, (const SegEntry *)nullptr, n_rsi, total_blocks, d_out, d_res, d_idx,
-                       (const DecResult *)nullptr, 0u, list, list_cnt);
+    launch_redo(true, seg);                              // (behind the timed kernels)
+    launch_redo(false, rest);
     return true;
-}
-
-bool launch_decode_segments(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const SegEntry *d_seg_table,
-                            uint64_t n_seg, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res,
-                            hipStream_t st, const PhaseEvents *prof)
-{
-    return launch_decode_any<true>(c, d_in, in_bytes, nullptr, d_seg_table, n_seg, total_blocks, d_out, d_res, st,
-                                   prof);
 }
 #endif      // AEC_DEC_PART
 
