@@ -207,6 +207,18 @@ AEC_GPU_API int aec_gpu_index_is_windowed(const aec_gpu_params *p, size_t in_byt
  * scheme 4 behind 1 and 2 for streams of moderate size, then the serial walk -- which this function does not tell.
  * start_block != 0: a walk that resumes inside an RSI.  Host arithmetic only; tests assert the path instead of a time. */
 AEC_GPU_API int aec_gpu_index_scheme(const aec_gpu_params *p, size_t in_bytes, uint64_t rsi_bits, unsigned int start_block);
+/* The whole CHAIN of schemes the index pass of such a stream enqueues one behind the other (a later scheme returns at once
+ * where one in front has delivered; their workspaces lie behind one another): the ids as above in schemes[0 .. return
+ * value), at most AEC_GPU_INDEX_STAGES.  The serial walk that schemes 1 and 4 enqueue behind themselves is not listed; 0
+ * stands for the serial walk alone or behind regions.  want_segments: a pass that leaves segment starts
+ * (aec_gpu_index_segments_async); piece: a pass after aec_gpu_set_index_piece; ws_bytes: the workspace on offer, 0 = what
+ * the pass asks for.  ws_asked: that size; ws_large: what it asks for when that cannot be had (without the every-bit
+ * scheme's tables); ws_used: what the stages of this chain occupy (all four outputs are required).  Host arithmetic
+ * only; -1 = invalid parameters or an output that is NULL. */
+#define AEC_GPU_INDEX_STAGES 6
+AEC_GPU_API int aec_gpu_index_plan(const aec_gpu_params *p, size_t in_bytes, uint64_t rsi_bits, unsigned int start_block,
+                                   int want_segments, int piece, size_t ws_bytes, int schemes[AEC_GPU_INDEX_STAGES],
+                                   size_t *ws_asked, size_t *ws_large, size_t *ws_used);
 /* The NEXT index pass on ctx (one pass only) is handed a piece of a stream of which the caller holds more: an RSI
  * that the window tables leave unresolved within stop_near_bits of the end of the piece -- they end there for lack
  * of look-ahead -- is not walked serially; the pass ends in front of it (n_rsi RSIs, tail_blocks 0, end_bit = its

@@ -517,6 +517,18 @@ int aec_gpu_index_scheme(const aec_gpu_params *p, size_t in_bytes, uint64_t rsi_
     return index_scheme(c, in_bytes, rsi_bits, start_block);
 }
 
+int aec_gpu_index_plan(const aec_gpu_params *p, size_t in_bytes, uint64_t rsi_bits, unsigned int start_block,
+                       int want_segments, int piece, size_t ws_bytes, int schemes[AEC_GPU_INDEX_STAGES], size_t *ws_asked,
+                       size_t *ws_large, size_t *ws_used)
+{
+    static_assert(AEC_GPU_INDEX_STAGES == kIdxMaxStages, "aec_gpu.h and aec_kernels.h disagree");
+    Cfg c;
+    if (!schemes || !ws_asked || !ws_large || !ws_used || cfg_from(p, 0, false, &c) != RC_OK) return -1;
+    *ws_asked = index_workspace_bytes(c, in_bytes, 0, rsi_bits);
+    *ws_large = index_workspace_bytes_large(c, in_bytes, 0, rsi_bits);
+    return index_plan(c, in_bytes, rsi_bits, start_block, want_segments != 0, piece != 0, ws_bytes, schemes, ws_used);
+}
+
 void aec_gpu_trim(aec_gpu_ctx *ctx, size_t keep_bytes)
 {
     if (ctx->ws && ctx->ws_bytes > keep_bytes) {

@@ -3100,6 +3100,7 @@ void allow_big_lds2()
 // the skipped chunks and the RSI starts inside all hops.
 // spans from which on the pipeline is worth a second set of tables (a quarter of a GB; below, e.g. for the
 // 256 MiB calls of the streaming ABI, one set is kept and the spans run behind one another)
+constexpr uint32_t kSparseSerialCap = 2048;     // (small_fallback_plan)
 constexpr uint64_t kS2PipeSpans = 4;
 
 // A side stream with its events, for the span pipeline below.  Created on first use, kept for the life of the process
@@ -3146,23 +3147,76 @@ void side_give(const SideStream &s)
     if (g_side_free) g_side_free->push_back(s);
 }
 
+// What a launch of the walker has beyond the walk itself (IdxWalk), filled by name; as it stands: the plain serial walk.
+struct IdxVary {
+    const uint32_t *skip_if = nullptr;
+    const uint64_t *chunk_off = nullptr;   // a batch: n_chunks + 1 byte offsets, a workgroup per stream
+    uint64_t n_chunks = 1, stop_near = 0;
+    IdxHop *hops = nullptr;                // the hops taken over the tables, for the expansion behind
+    IdxCarry *carry = nullptr;             // spans of tables: the walker's state between them
+    uint32_t hop_cap = 0, first = 1, last = 1, serial_cap = 0;
+    TwTables tw = {};                      // trunk tables ...
+    SparseTables s2 = {}, dense = {};      // ... or window tables
+    ChunkEntry *centry = nullptr;
+    uint32_t *batch_nhops = nullptr, *delivered = nullptr;
+};
+
+// the one place that spells k_index's arguments
+void go_index(const IdxWalk &w, const IdxVary &v)
+{
+    hipLaunchKernelGGL(k_index, dim3((uint32_t)v.n_chunks), dim3(64), 0, w.st, w.c, w.words, w.nwords, w.end_bit, w.start_bit,
+                       w.d_rsi_off, w.max_rsi, w.d_res, v.chunk_off, v.hops, v.hop_cap, v.carry, v.first, v.last, w.start_block,
+                       w.rsi_start, w.tail_slot, v.tw, v.centry, v.s2, v.batch_nhops, v.stop_near, v.skip_if, v.dense,
+                       v.serial_cap, v.delivered);
+}
+
+// The window tables of nwin windows from bit lo in the set of tables at tb (dense: the dense fallback's, behind them).
+SparseTables sparse_tables(const Sparse2Plan &p, const uint8_t *tb, uint64_t lo, uint32_t nwin, const uint32_t *skip_if,
+                           bool dense = false)
+{
+    const Spec2Geom &g = dense ? p.dg : p.g;
+    return {.bitmap = reinterpret_cast<const uint32_t *>(tb + (dense ? p.od_bitmap : p.o_bitmap)),
+            .pre = reinterpret_cast<const uint16_t *>(tb + (dense ? p.od_pre : p.o_pre)),
+            .rec = reinterpret_cast<const uint2 *>(tb + (dense ? p.od_rec : p.o_rec)),
+            .cpos = reinterpret_cast<const uint16_t *>(tb + (dense ? p.od_cpos : p.o_cpos)),
+            .ccnt = reinterpret_cast<const uint32_t *>(tb + (dense ? p.od_ccnt : p.o_ccnt)),
+            .lo = lo, .hi = lo + (uint64_t)nwin * g.core, .core = g.core, .cap = g.cap_core,
+            .wide = dense ? nullptr : reinterpret_cast<const uint4 *>(tb + p.o_wide), .wpc = dense ? 1u : p.wpc,
+            .skip_if = skip_if};
+}
+
+// the table kernel of a set of windows, a workgroup per window: k_spec4 or k_spec2 (the same arguments)
+void go_spec(bool v4, uint32_t nwin, size_t lds, hipStream_t ts, const IdxWalk &w, uint64_t lo, const Spec2Geom &geom,
+             const SparseTables &t, unsigned long long *prof, const uint64_t *starts, uint32_t nstarts, uint32_t *blist,
+             uint32_t *blist_cnt)
+{
+    uint32_t *bitmap = const_cast<uint32_t *>(t.bitmap), *ccnt = const_cast<uint32_t *>(t.ccnt);
+    uint16_t *pre = const_cast<uint16_t *>(t.pre), *cpos = const_cast<uint16_t *>(t.cpos);
+    if (v4)
+        hipLaunchKernelGGL(k_spec4, dim3(nwin), dim3(1024), lds, ts, w.c, w.words, w.nwords, w.end_bit, lo, w.start_bit, geom,
+                           bitmap, pre, const_cast<uint2 *>(t.rec), cpos, ccnt, prof, starts, nstarts, blist, blist_cnt);
+    else
+        hipLaunchKernelGGL(k_spec2, dim3(nwin), dim3(1024), lds, ts, w.c, w.words, w.nwords, w.end_bit, lo, w.start_bit, geom,
+                           bitmap, pre, const_cast<uint2 *>(t.rec), cpos, ccnt, prof, starts, nstarts, blist, blist_cnt);
+}
+
 // Spans of at most nwin_max windows.  With room for two sets of tables the spans are pipelined over two streams: the
 // table kernel of span s + 1 (k_spec2: all CUs) runs on a side stream beside the walkers of span s (k_wide, k_index,
 // k_rewalk, k_expand2: a few hundred wavefronts down to one, 16 % of the time of a span when they ran behind one another), ordered by
 // events; `st` has waited for everything the side stream did when the last walker is enqueued.
-void launch_index_sparse(const Cfg &c, const Sparse2Plan &p, const uint32_t *words, uint64_t nwords, uint64_t end_bit,
-                         uint64_t start_bit, uint64_t *d_rsi_off, uint64_t max_rsi, DecResult *d_res, hipStream_t st,
-                         uint8_t *base, size_t ws_bytes, uint32_t start_block, uint64_t rsi_start, uint32_t tail_slot,
-                         uint64_t stop_near, const uint32_t *skip_if = nullptr, uint32_t serial_cap = 0,
-                         uint32_t *delivered = nullptr)
+// skip_if, delivered: see k_index; with `delivered` the walker of a stream of one span may give it up (serial_cap).
+void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, size_t ws_bytes,
+                         const uint32_t *skip_if = nullptr, uint32_t *delivered = nullptr)
 {
+    const uint32_t serial_cap = delivered ? (uint32_t)tune("AEC_IDX_SPARSE_SERIAL_CAP", kSparseSerialCap) : 0u;
+    if (delivered) (void)hipMemsetAsync(delivered, 0, 4, w.st);
     allow_big_lds2();
     Spec2Geom geom = p.g, dgeom = p.dg;
     geom.skip_if = dgeom.skip_if = skip_if;
     IdxCarry *carry = reinterpret_cast<IdxCarry *>(base);
-    const uint64_t lo0 = start_bit / p.g.core * p.g.core;
+    const uint64_t lo0 = w.start_bit / p.g.core * p.g.core;
     const uint64_t span = (uint64_t)p.nwin_max * p.g.core;
-    const uint64_t nspans = (end_bit - lo0 + span - 1) / span;
+    const uint64_t nspans = (w.end_bit - lo0 + span - 1) / span;
     SideStream side;
     bool piped = nspans >= kS2PipeSpans && ws_bytes >= 2 * p.bytes && !spec2_prof_buffer(0, false);
 #ifdef AEC_TUNING
@@ -3170,31 +3224,19 @@ void launch_index_sparse(const Cfg &c, const Sparse2Plan &p, const uint32_t *wor
 #endif
     piped = piped && side_take(&side);
     if (piped) {
-        (void)hipEventRecord(side.start, st);                       // the input is whatever `st` has produced so far
+        (void)hipEventRecord(side.start, w.st);                       // the input is whatever `w.st` has produced so far
         (void)hipStreamWaitEvent(side.st, side.start, 0);
     }
     uint64_t si = 0;
-    for (uint64_t lo = lo0; lo < end_bit; lo += span, si++) {
-        const uint64_t bits = end_bit - lo < span ? end_bit - lo : span;
+    for (uint64_t lo = lo0; lo < w.end_bit; lo += span, si++) {
+        const uint64_t bits = w.end_bit - lo < span ? w.end_bit - lo : span;
         const uint32_t nwin = (uint32_t)((bits + p.g.core - 1) / p.g.core);
         const uint32_t nchunks = (nwin + p.wpc - 1) / p.wpc;
-        const bool first = lo == lo0, last = lo + span >= end_bit;
+        const bool first = lo == lo0, last = lo + span >= w.end_bit;
         const uint32_t set = piped ? (uint32_t)(si & 1u) : 0u;
         uint8_t *tb = base + (size_t)set * p.bytes;                  // (the carry record lives in set 0's header)
-        hipStream_t ts = piped ? side.st : st;                       // stream of the table kernels
-        SparseTables t;
-        t.bitmap = reinterpret_cast<const uint32_t *>(tb + p.o_bitmap);
-        t.pre = reinterpret_cast<const uint16_t *>(tb + p.o_pre);
-        t.rec = reinterpret_cast<const uint2 *>(tb + p.o_rec);
-        t.cpos = reinterpret_cast<const uint16_t *>(tb + p.o_cpos);
-        t.ccnt = reinterpret_cast<const uint32_t *>(tb + p.o_ccnt);
-        t.lo = lo;
-        t.hi = lo + (uint64_t)nwin * p.g.core;
-        t.core = p.g.core;
-        t.cap = p.g.cap_core;
-        t.wide = reinterpret_cast<const uint4 *>(tb + p.o_wide);
-        t.wpc = p.wpc;
-        t.skip_if = skip_if;
+        hipStream_t ts = piped ? side.st : w.st;                       // stream of the table kernels
+        SparseTables t = sparse_tables(p, tb, lo, nwin, skip_if);
         ChunkEntry *centry = reinterpret_cast<ChunkEntry *>(tb + p.o_centry);
         IdxHop *hops = reinterpret_cast<IdxHop *>(tb + p.o_hops);
         IdxHop *rhops = reinterpret_cast<IdxHop *>(tb + p.o_rhops);
@@ -3203,57 +3245,33 @@ void launch_index_sparse(const Cfg &c, const Sparse2Plan &p, const uint32_t *wor
         if (piped && si >= 2) (void)hipStreamWaitEvent(ts, side.done[set], 0);      // the walkers of span si - 2 are through
         uint32_t *blist = reinterpret_cast<uint32_t *>(tb + p.o_blist), *blist_cnt = reinterpret_cast<uint32_t *>(tb + 56);
         (void)hipMemsetAsync(blist_cnt, 0, 8, ts);                  // (+ the count of the dense windows' list at offset 60)
-        if (p.g.v4)
-            hipLaunchKernelGGL(k_spec4, dim3(nwin), dim3(1024), p.lds, ts, c, words, nwords, end_bit, lo, start_bit, geom,
-                               const_cast<uint32_t *>(t.bitmap), const_cast<uint16_t *>(t.pre), const_cast<uint2 *>(t.rec),
-                               const_cast<uint16_t *>(t.cpos), const_cast<uint32_t *>(t.ccnt), spec2_prof_buffer(nwin),
-                               (const uint64_t *)nullptr, 0u, blist, blist_cnt);
-        else
-            hipLaunchKernelGGL(k_spec2, dim3(nwin), dim3(1024), p.lds, ts, c, words, nwords, end_bit, lo, start_bit, geom,
-                               const_cast<uint32_t *>(t.bitmap), const_cast<uint16_t *>(t.pre), const_cast<uint2 *>(t.rec),
-                               const_cast<uint16_t *>(t.cpos), const_cast<uint32_t *>(t.ccnt), spec2_prof_buffer(nwin),
-                               (const uint64_t *)nullptr, 0u, blist, blist_cnt);
+        go_spec(p.g.v4 != 0, nwin, p.lds, ts, w, lo, geom, t, spec2_prof_buffer(nwin), nullptr, 0u, blist, blist_cnt);
         spec2_prof_report(nwin, ts, p.g.v4 != 0);
         SparseTables td{};
         if (p.dense) {
             const uint32_t dnwin = (uint32_t)(((uint64_t)nwin * p.g.core + p.dg.core - 1) / p.dg.core);
-            td.bitmap = reinterpret_cast<const uint32_t *>(tb + p.od_bitmap);
-            td.pre = reinterpret_cast<const uint16_t *>(tb + p.od_pre);
-            td.rec = reinterpret_cast<const uint2 *>(tb + p.od_rec);
-            td.cpos = reinterpret_cast<const uint16_t *>(tb + p.od_cpos);
-            td.ccnt = reinterpret_cast<const uint32_t *>(tb + p.od_ccnt);
-            td.lo = lo;
-            td.hi = lo + (uint64_t)dnwin * p.dg.core < t.hi ? lo + (uint64_t)dnwin * p.dg.core : t.hi;
-            td.core = p.dg.core;
-            td.cap = p.dg.cap_core;
-            td.wide = nullptr;
-            td.wpc = 1;
-            td.skip_if = skip_if;
+            td = sparse_tables(p, tb, lo, dnwin, skip_if, true);
+            if (td.hi > t.hi) td.hi = t.hi;
             uint32_t *dlist = reinterpret_cast<uint32_t *>(tb + p.od_list), *dcount = reinterpret_cast<uint32_t *>(tb + 60);
-            if (dnwin <= 1024u)
-                hipLaunchKernelGGL(k_spec4, dim3(dnwin), dim3(1024), p.dlds, ts, c, words, nwords, end_bit, lo, start_bit, dgeom,
-                                   const_cast<uint32_t *>(td.bitmap), const_cast<uint16_t *>(td.pre), const_cast<uint2 *>(td.rec),
-                                   const_cast<uint16_t *>(td.cpos), const_cast<uint32_t *>(td.ccnt), (unsigned long long *)nullptr,
-                                   (const uint64_t *)nullptr, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr,
-                                   (const uint32_t *)nullptr, t.ccnt, p.g.core, nwin);
-            else {
-            hipLaunchKernelGGL(k_dense_pick, dim3((dnwin + 255) / 256), dim3(256), 0, ts, t.ccnt, p.g.core, nwin, p.dg.core, dnwin,
-                               const_cast<uint32_t *>(td.ccnt), dlist, dcount, skip_if);
-            hipLaunchKernelGGL(k_spec4, dim3(dnwin < 512u ? dnwin : 512u), dim3(1024), p.dlds, ts, c, words, nwords, end_bit, lo,
-                               start_bit, dgeom, const_cast<uint32_t *>(td.bitmap), const_cast<uint16_t *>(td.pre),
+            // (few windows: each looks itself whether an ordinary window over its core gave up; else those are listed first)
+            const bool few = dnwin <= 1024u;
+            if (!few)
+                hipLaunchKernelGGL(k_dense_pick, dim3((dnwin + 255) / 256), dim3(256), 0, ts, t.ccnt, p.g.core, nwin, p.dg.core, dnwin,
+                                   const_cast<uint32_t *>(td.ccnt), dlist, dcount, skip_if);
+            hipLaunchKernelGGL(k_spec4, dim3(few ? dnwin : 512u), dim3(1024), p.dlds, ts, w.c, w.words, w.nwords, w.end_bit, lo,
+                               w.start_bit, dgeom, const_cast<uint32_t *>(td.bitmap), const_cast<uint16_t *>(td.pre),
                                const_cast<uint2 *>(td.rec), const_cast<uint16_t *>(td.cpos), const_cast<uint32_t *>(td.ccnt),
                                (unsigned long long *)nullptr, (const uint64_t *)nullptr, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                               (const uint32_t *)dlist, (const uint32_t *)dcount);
-            }
+                               few ? nullptr : dlist, few ? nullptr : dcount, few ? t.ccnt : nullptr, few ? p.g.core : 0u, few ? nwin : 0u);
         }
 #ifdef AEC_TUNING
         if (tune_set("AEC_S2_VERIFY")) {
             static uint32_t *d_bad = nullptr;
             if (!d_bad) (void)hipMalloc(reinterpret_cast<void **>(&d_bad), 8);
-            (void)hipMemsetAsync(d_bad, 0, 8, st);
-            hipLaunchKernelGGL(k_spec_verify, dim3(nwin), dim3(256), 0, st, c, TrStream{words, nwords, end_bit}, t, nwin, d_bad);
+            (void)hipMemsetAsync(d_bad, 0, 8, w.st);
+            hipLaunchKernelGGL(k_spec_verify, dim3(nwin), dim3(256), 0, w.st, w.c, TrStream{w.words, w.nwords, w.end_bit}, t, nwin, d_bad);
             uint32_t h[2] = {0, 0};
-            (void)hipStreamSynchronize(st);
+            (void)hipStreamSynchronize(w.st);
             (void)hipMemcpy(h, d_bad, 8, hipMemcpyDeviceToHost);
             uint32_t nb = 0;
             (void)hipMemcpy(&nb, blist_cnt, 4, hipMemcpyDeviceToHost);
@@ -3263,7 +3281,7 @@ void launch_index_sparse(const Cfg &c, const Sparse2Plan &p, const uint32_t *wor
 #endif
         if (piped) {
             (void)hipEventRecord(side.tab[set], ts);
-            (void)hipStreamWaitEvent(st, side.tab[set], 0);
+            (void)hipStreamWaitEvent(w.st, side.tab[set], 0);
         }
         // (a few windows only -- a chunk of an HDF5 dataset: the walker takes a lookup per window itself, which costs
         // what the chunk-level chase alone would, and five launches less)
@@ -3271,32 +3289,31 @@ void launch_index_sparse(const Cfg &c, const Sparse2Plan &p, const uint32_t *wor
         if (flat) t.wide = nullptr;
         // (the chunk-level chase has a few hundred wavefronts: with the walkers, beside the next span's k_spec2)
         if (!flat) {
-            (void)hipMemsetAsync(tb + p.o_wide, 0, (size_t)nchunks * p.g.cap_core * sizeof(uint4), st);
-            (void)hipMemsetAsync(centry, 0, (size_t)nchunks * sizeof(ChunkEntry), st);
+            (void)hipMemsetAsync(tb + p.o_wide, 0, (size_t)nchunks * p.g.cap_core * sizeof(uint4), w.st);
+            (void)hipMemsetAsync(centry, 0, (size_t)nchunks * sizeof(ChunkEntry), w.st);
         }
         if (tune("AEC_S2_BRIDGE", 1))
-            hipLaunchKernelGGL(k_bridge, dim3(1024), dim3(64), 0, st, c, words, nwords, end_bit, t,
+            hipLaunchKernelGGL(k_bridge, dim3(1024), dim3(64), 0, w.st, w.c, w.words, w.nwords, w.end_bit, t,
                                const_cast<uint2 *>(t.rec), blist, blist_cnt, carry, first ? 1u : 0u,
                                (uint32_t)tune("AEC_S2_BRIDGE_AFTER", kS2BridgeAfter));
         if (!flat)
-            hipLaunchKernelGGL(k_wide, dim3((p.g.cap_core + 255) / 256, nchunks), dim3(256), 0, st, t, nwin, end_bit,
+            hipLaunchKernelGGL(k_wide, dim3((p.g.cap_core + 255) / 256, nchunks), dim3(256), 0, w.st, t, nwin, w.end_bit,
                                const_cast<uint4 *>(t.wide));
-        hipLaunchKernelGGL(k_index, dim3(1), dim3(64), 0, st, c, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi,
-                           d_res, (const uint64_t *)nullptr, hops, hop_cap, carry, first ? 1u : 0u, last ? 1u : 0u,
-                           start_block, rsi_start, tail_slot, TwTables{}, centry, t, (uint32_t *)nullptr, last ? stop_near : 0ull,
-                           skip_if, td, (first && last) ? serial_cap : 0u, (first && last) ? delivered : (uint32_t *)nullptr);
+        go_index(w, {.skip_if = skip_if, .stop_near = last ? w.stop_near : 0, .hops = hops, .carry = carry, .hop_cap = hop_cap,
+                     .first = first, .last = last, .serial_cap = first && last ? serial_cap : 0, .s2 = t, .dense = td, .centry = centry,
+                     .delivered = first && last ? delivered : nullptr});
         if (!flat)
-            hipLaunchKernelGGL(k_rewalk, dim3((nchunks + 63) / 64), dim3(64), 0, st, t, nwin, nchunks, end_bit, centry, rhops,
-                               nhops, d_rsi_off);
-        hipLaunchKernelGGL(k_expand2, dim3((hop_cap + 255) / 256), dim3(256), 0, st, t, carry, hops,
-                           (const uint32_t *)nullptr, 0u, 0u, d_rsi_off);
+            hipLaunchKernelGGL(k_rewalk, dim3((nchunks + 63) / 64), dim3(64), 0, w.st, t, nwin, nchunks, w.end_bit, centry, rhops,
+                               nhops, w.d_rsi_off);
+        hipLaunchKernelGGL(k_expand2, dim3((hop_cap + 255) / 256), dim3(256), 0, w.st, t, carry, hops,
+                           (const uint32_t *)nullptr, 0u, 0u, w.d_rsi_off);
         if (!flat)
-            hipLaunchKernelGGL(k_expand2, dim3((nchunks * p.wpc * 2 + 255) / 256), dim3(256), 0, st, t, carry, rhops, nhops,
-                               nchunks, p.wpc * 2, d_rsi_off);
-        if (piped) (void)hipEventRecord(side.done[set], st);
+            hipLaunchKernelGGL(k_expand2, dim3((nchunks * p.wpc * 2 + 255) / 256), dim3(256), 0, w.st, t, carry, rhops, nhops,
+                               nchunks, p.wpc * 2, w.d_rsi_off);
+        if (piped) (void)hipEventRecord(side.done[set], w.st);
 #ifdef AEC_TUNING
         if (tune_set("AEC_IDX_STATS")) {                   // (diagnostics: synchronises)
-            (void)hipStreamSynchronize(st);
+            (void)hipStreamSynchronize(w.st);
             const int dbg = tune("AEC_IDX_STATS", 0) >= 2 ? 1 : 0;
             const hipError_t de = hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_serial), &dbg, sizeof(dbg));
             if (de != hipSuccess) fprintf(stderr, "g_dbg_serial: %s\n", hipGetErrorString(de));
@@ -3319,7 +3336,7 @@ void launch_index_sparse(const Cfg &c, const Sparse2Plan &p, const uint32_t *wor
                 uint32_t hist[32] = {0};
                 for (uint32_t v : bl) hist[(v >> 26) & 31u]++;
                 fprintf(stderr, "  headers of the listed hypotheses:");
-                for (uint32_t q = 0; q < (1u << c.id_len); q++) fprintf(stderr, " %u:%u", q, hist[q]);
+                for (uint32_t q = 0; q < (1u << w.c.id_len); q++) fprintf(stderr, " %u:%u", q, hist[q]);
                 fprintf(stderr, "\n");
             }
             fprintf(stderr, "window tables, span %llu: %u windows (%u gave up), candidates per window %.0f on average, %u at "
@@ -3568,25 +3585,22 @@ void allow_big_lds_walk()
     });
 }
 
-void launch_index_trunk(const Cfg &c, TrunkPlan p, const uint32_t *words, uint64_t nwords, uint64_t end_bit,
-                        uint64_t start_bit, uint64_t *d_rsi_off, uint64_t max_rsi, DecResult *d_res, hipStream_t st,
-                        uint8_t *base, uint32_t start_block, uint64_t rsi_start, uint32_t tail_slot, uint64_t *d_seg_bits,
-                        const uint32_t *skip_if = nullptr)
+void launch_index_trunk(const IdxWalk &w, TrunkPlan p, uint8_t *base, const uint32_t *skip_if = nullptr)
 {
     IdxCarry *carry = reinterpret_cast<IdxCarry *>(base);
-    const TrStream s{words, nwords, end_bit};
+    const TrStream s{w.words, w.nwords, w.end_bit};
     allow_big_lds_walk();
     (void)trunk_bytes(p, p.nwin_max);                     // offsets for the span size
-    const uint64_t lo0 = start_bit / p.L * p.L;
-    const uint64_t nwin_all = (end_bit - lo0) / p.L + 1;
+    const uint64_t lo0 = w.start_bit / p.L * p.L;
+    const uint64_t nwin_all = (w.end_bit - lo0) / p.L + 1;
     const bool one = nwin_all <= p.nwin_max;
     const uint32_t ncore_span = one ? (uint32_t)nwin_all : p.nwin_max - p.nlook;
-    for (uint64_t lo = lo0; lo <= end_bit; lo += (uint64_t)ncore_span * p.L) {
-        const uint64_t left = (end_bit - lo) / p.L + 1;
+    for (uint64_t lo = lo0; lo <= w.end_bit; lo += (uint64_t)ncore_span * p.L) {
+        const uint64_t left = (w.end_bit - lo) / p.L + 1;
         const bool first = lo == lo0, last = left <= ncore_span || one;
         TrGeom g{};
         g.lo = lo;
-        g.start_bit = start_bit;
+        g.start_bit = w.start_bit;
         g.L = p.L;
         g.lead = p.lead;
         g.ncap = p.ncap;
@@ -3621,27 +3635,27 @@ void launch_index_trunk(const Cfg &c, TrunkPlan p, const uint32_t *words, uint64
         // (... and where the regions are few: a wavefront's parse is mostly scalar work, and the one scalar unit of a CU
         // serves all its wavefronts -- measured on spans of 5167 regions: 4.5 ms against 6.1 for the lanes, whose time
         // is the latency of ONE region whatever their number)
-        const bool coop = tune("AEC_TR_COOP", nreg <= 6144u ? 1u : 0u) && c.id_len + 1u + c.bps + c.bs * c.bps + 128u <= 2048u;
+        const bool coop = tune("AEC_TR_COOP", nreg <= 6144u ? 1u : 0u) && w.c.id_len + 1u + w.c.bps + w.c.bs * w.c.bps + 128u <= 2048u;
         const uint32_t cgrid = nreg < 256u * 20u ? nreg : 256u * 20u;
         if (coop)
-            hipLaunchKernelGGL(k_trunk_coop, dim3(cgrid), dim3(64), 0, st, c, s, g, t, (const uint64_t *)nullptr, ex[0], 0u);
+            hipLaunchKernelGGL(k_trunk_coop, dim3(cgrid), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)nullptr, ex[0], 0u);
         else
-            hipLaunchKernelGGL(k_trunk, dim3((nreg + 63) / 64), dim3(64), 0, st, c, s, g, t, (const uint64_t *)nullptr, ex[0], 0u);
+            hipLaunchKernelGGL(k_trunk, dim3((nreg + 63) / 64), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)nullptr, ex[0], 0u);
         uint32_t cur = 0;
         for (uint32_t k = 0; k < p.passes; k++) {
             if (coop)
-                hipLaunchKernelGGL(k_trunk_coop, dim3(cgrid), dim3(64), 0, st, c, s, g, t, (const uint64_t *)ex[cur],
+                hipLaunchKernelGGL(k_trunk_coop, dim3(cgrid), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)ex[cur],
                                    ex[cur ^ 1u], 1u);
             else
-                hipLaunchKernelGGL(k_trunk, dim3((nreg + 63) / 64), dim3(64), 0, st, c, s, g, t, (const uint64_t *)ex[cur],
+                hipLaunchKernelGGL(k_trunk, dim3((nreg + 63) / 64), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)ex[cur],
                                    ex[cur ^ 1u], 1u);
             cur ^= 1u;
         }
         t.exit = ex[cur];
-        hipLaunchKernelGGL(k_trunk_scan, dim3(1), dim3(1024), 0, st, g, t);
-        hipLaunchKernelGGL(k_trunk, dim3((g.nwin + 63) / 64), dim3(64), 0, st, c, s, g, t, (const uint64_t *)nullptr,
+        hipLaunchKernelGGL(k_trunk_scan, dim3(1), dim3(1024), 0, w.st, g, t);
+        hipLaunchKernelGGL(k_trunk, dim3((g.nwin + 63) / 64), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)nullptr,
                            (uint64_t *)nullptr, 2u);
-        (void)hipMemsetAsync(t.pool_cnt, 0, 4, st);
+        (void)hipMemsetAsync(t.pool_cnt, 0, 4, w.st);
         const uint32_t ngroups = (g.ncore + p.wpw - 1) / p.wpw;
         CoLists ls{};
         if (p.co) {
@@ -3651,25 +3665,25 @@ void launch_index_trunk(const Cfg &c, TrunkPlan p, const uint32_t *words, uint64
             ls.qcap = p.co_qcap;
             ls.pcap = p.co_pcap;
             ls.over_plain = p.co_over;
-            (void)hipMemsetAsync(ls.counts, 0, 8, st);
+            (void)hipMemsetAsync(ls.counts, 0, 8, w.st);
             const uint32_t ng = (g.ncore + p.co_wpg - 1) / p.co_wpg;
             const size_t lds_wg = p.co_lds + sizeof(CoParked) * kCoPark + 64;          // (dynamic + the kernel's own)
             const uint32_t per_cu = (uint32_t)(160 * 1024 / lds_wg) ? (uint32_t)(160 * 1024 / lds_wg) : 1u;
             const uint32_t grid = ng < 256u * per_cu ? ng : 256u * per_cu;
-            hipLaunchKernelGGL(k_hyp_walk_co, dim3(grid), dim3(256), p.co_lds, st, c, s, g, t, p.co_wpg, p.co_margin, ng,
+            hipLaunchKernelGGL(k_hyp_walk_co, dim3(grid), dim3(256), p.co_lds, w.st, w.c, s, g, t, p.co_wpg, p.co_margin, ng,
                                p.co_shift, p.co_tmax, p.co_cap, ls, p.co_park);
             hipLaunchKernelGGL(k_hyp_walk_rest, dim3((p.co_qcap + 63) / 64 < 16384u ? (p.co_qcap + 63) / 64 : 16384u), dim3(64), 0,
-                               st, c, s, g, t, ls);
-            hipLaunchKernelGGL(k_hyp_defer, dim3(g.ncore), dim3(256), 0, st, c, g, t, ls);
+                               w.st, w.c, s, g, t, ls);
+            hipLaunchKernelGGL(k_hyp_defer, dim3(g.ncore), dim3(256), 0, w.st, w.c, g, t, ls);
         } else if (p.staged) {
             const uint32_t grid = ngroups < 256u ? ngroups : 256u;                           // (one workgroup per CU)
-            hipLaunchKernelGGL((k_hyp_walk<true>), dim3(grid), dim3(1024), p.lds, st, c, s, g, t, p.wpw, p.margin, ngroups);
+            hipLaunchKernelGGL((k_hyp_walk<true>), dim3(grid), dim3(1024), p.lds, w.st, w.c, s, g, t, p.wpw, p.margin, ngroups);
         } else {
-            hipLaunchKernelGGL(k_hyp_walk_mem, dim3(ngroups), dim3(64), 0, st, c, s, g, t, p.wpw);
+            hipLaunchKernelGGL(k_hyp_walk_mem, dim3(ngroups), dim3(64), 0, w.st, w.c, s, g, t, p.wpw);
         }
-        hipLaunchKernelGGL(k_hyp_land, dim3(g.ncore), dim3(256), 0, st, c, g, t);
+        hipLaunchKernelGGL(k_hyp_land, dim3(g.ncore), dim3(256), 0, w.st, w.c, g, t);
         if (p.co)
-            hipLaunchKernelGGL(k_hyp_walk_list, dim3(p.co_pcap < 2048u ? p.co_pcap : 2048u), dim3(64), 0, st, c, s, g, t, ls);
+            hipLaunchKernelGGL(k_hyp_walk_list, dim3(p.co_pcap < 2048u ? p.co_pcap : 2048u), dim3(64), 0, w.st, w.c, s, g, t, ls);
 
         const uint32_t nwin = g.ncore, nchunks = (nwin + p.wpc - 1) / p.wpc;
         TwTables sp;
@@ -3691,30 +3705,28 @@ void launch_index_trunk(const Cfg &c, TrunkPlan p, const uint32_t *words, uint64
         ChunkEntry *centry = reinterpret_cast<ChunkEntry *>(base + p.o_centry);
         IdxHop *hops = reinterpret_cast<IdxHop *>(base + p.o_hops);
         const uint32_t hop_cap = 2 * nwin + 8;
-        (void)hipMemsetAsync(centry, 0, (size_t)nchunks * sizeof(ChunkEntry), st);
-        hipLaunchKernelGGL(k_twide, dim3((p.wcap + 255) / 256, nchunks), dim3(256), 0, st, sp, nwin, end_bit,
+        (void)hipMemsetAsync(centry, 0, (size_t)nchunks * sizeof(ChunkEntry), w.st);
+        hipLaunchKernelGGL(k_twide, dim3((p.wcap + 255) / 256, nchunks), dim3(256), 0, w.st, sp, nwin, w.end_bit,
                            const_cast<uint4 *>(sp.wide));
-        hipLaunchKernelGGL(k_index, dim3(1), dim3(64), 0, st, c, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi,
-                           d_res, (const uint64_t *)nullptr, hops, hop_cap, carry, first ? 1u : 0u, last ? 1u : 0u,
-                           start_block, rsi_start, tail_slot, sp, centry, SparseTables{}, (uint32_t *)nullptr, (uint64_t)0,
-                           skip_if);
-        hipLaunchKernelGGL(k_trewalk, dim3((nchunks + 63) / 64), dim3(64), 0, st, c, sp, t, nwin, nchunks, end_bit, centry,
-                           d_rsi_off);
-        hipLaunchKernelGGL(k_texpand, dim3((hop_cap + 255) / 256), dim3(256), 0, st, c, sp, t, carry, hops, d_rsi_off);
-        if (d_seg_bits) {
+        go_index(w, {.skip_if = skip_if, .hops = hops, .carry = carry, .hop_cap = hop_cap, .first = first, .last = last,
+                     .tw = sp, .centry = centry});
+        hipLaunchKernelGGL(k_trewalk, dim3((nchunks + 63) / 64), dim3(64), 0, w.st, w.c, sp, t, nwin, nchunks, w.end_bit, centry,
+                           w.d_rsi_off);
+        hipLaunchKernelGGL(k_texpand, dim3((hop_cap + 255) / 256), dim3(256), 0, w.st, w.c, sp, t, carry, hops, w.d_rsi_off);
+        if (w.d_seg_bits) {
             // (at most one RSI per minimal coded RSI of the span; a wavefront each, the rest in turn)
-            const uint64_t most = (uint64_t)g.ncore * g.L / ((uint64_t)c.segs_per_rsi * (c.id_len + 2u)) + 2u;
+            const uint64_t most = (uint64_t)g.ncore * g.L / ((uint64_t)w.c.segs_per_rsi * (w.c.id_len + 2u)) + 2u;
             const uint32_t gmax = tune("AEC_TR_SEG_GRID", 4096u);
             const uint32_t grid = (uint32_t)(most < gmax ? most : gmax);
-            hipLaunchKernelGGL(k_seg_starts, dim3(grid), dim3(64), 0, st, c, s, g, t, d_rsi_off, carry, d_res, d_seg_bits,
-                               max_rsi + 1u);
+            hipLaunchKernelGGL(k_seg_starts, dim3(grid), dim3(64), 0, w.st, w.c, s, g, t, w.d_rsi_off, carry, w.d_res,
+                               w.d_seg_bits, w.max_rsi + 1u);
         }
         if (last) break;
     }
 #ifdef AEC_TUNING
     if (tune_set("AEC_IDX_STATS")) {                       // (diagnostics: synchronises)
         IdxCarry h{};
-        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(w.st);
         const int dbg = tune("AEC_IDX_STATS", 0) >= 2 ? 1 : 0;
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_serial), &dbg, sizeof(dbg));
         (void)hipMemcpy(&h, carry, sizeof(h), hipMemcpyDeviceToHost);
@@ -4944,12 +4956,11 @@ static LockPlan lock_plan_alt(const Cfg &c, uint64_t total_bits, uint64_t rsi_bi
     return l0;
 }
 
-void launch_index_locked(const Cfg &c, const LockPlan &p, const uint32_t *words, uint64_t nwords, uint64_t end_bit,
-                         uint64_t start_bit, uint64_t *d_rsi_off, uint64_t max_rsi, DecResult *d_res, hipStream_t st,
-                         uint8_t *base, uint32_t start_block, uint64_t rsi_start, uint32_t tail_slot,
-                         bool serial_fallback = true, const uint32_t *skip_if = nullptr)
+// final: nothing is enqueued behind, whatever was not delivered is the serial walker's, which returns at once otherwise
+void launch_index_locked(const IdxWalk &w, const LockPlan &p, uint8_t *base, bool final = true,
+                         const uint32_t *skip_if = nullptr)
 {
-    const TrStream s{words, nwords, end_bit};
+    const TrStream s{w.words, w.nwords, w.end_bit};
     LockTables t{};
     t.flags = reinterpret_cast<uint32_t *>(base + p.o_flags);
     t.entry = reinterpret_cast<LkState *>(base + p.o_entry);
@@ -4964,27 +4975,27 @@ void launch_index_locked(const Cfg &c, const LockPlan &p, const uint32_t *words,
     t.coop = p.coop;
     t.mode = p.mode;
     t.skip_if = skip_if;
-    t.lo = start_bit;
-    (void)hipMemsetAsync(t.flags, 0, 64, st);
+    t.lo = w.start_bit;
+    (void)hipMemsetAsync(t.flags, 0, 64, w.st);
     // a wavefront per region (k_lock_*_w) -- unless the parameters are beyond its tables' look-ahead
     const bool wave = p.mode == 1u ||
-                      (tune("AEC_IDX_LOCK_WAVE", 1) != 0 && c.id_len + 1u + c.bps + c.bs * c.bps <= (kSwLookWords - 2u) * 32u);
+                      (tune("AEC_IDX_LOCK_WAVE", 1) != 0 && w.c.id_len + 1u + w.c.bps + w.c.bs * w.c.bps <= (kSwLookWords - 2u) * 32u);
     const uint32_t wpw = 4;                                             // wavefronts per workgroup
     const size_t wlds = (size_t)wpw * kSwWaveWords * 4;
     if (wave) {
         LkState *ex[2] = {t.exit0, t.exit1};
         if (p.nreg > 1 && p.mode == 1u)
-            hipLaunchKernelGGL(k_lock_guess_p, dim3(p.nreg - 1), dim3(64), (size_t)sw_wave_words(kLpPiece) * 4, st, c, s, t, p.back);
+            hipLaunchKernelGGL(k_lock_guess_p, dim3(p.nreg - 1), dim3(64), (size_t)sw_wave_words(kLpPiece) * 4, w.st, w.c, s, t, p.back);
         else if (p.nreg > 1)
-            hipLaunchKernelGGL(k_lock_guess_w, dim3((p.nreg - 1 + wpw - 1) / wpw), dim3(64 * wpw), wlds, st, c, s, t);
+            hipLaunchKernelGGL(k_lock_guess_w, dim3((p.nreg - 1 + wpw - 1) / wpw), dim3(64 * wpw), wlds, w.st, w.c, s, t);
         const uint32_t wg = (p.nreg + wpw - 1) / wpw;
         LkState *en[2] = {t.entry, reinterpret_cast<LkState *>(base + p.o_entry1)};
-        hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, st, c, s, t, (const LkState *)nullptr, ex[0], en[0], 0u,
-                           start_bit, start_block);
-        if (p.mode == 1u) hipLaunchKernelGGL(k_lock_judge, dim3(1), dim3(1024), 0, st, t, (const LkState *)ex[0]);
+        hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)nullptr, ex[0], en[0], 0u,
+                           w.start_bit, w.start_block);
+        if (p.mode == 1u) hipLaunchKernelGGL(k_lock_judge, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[0]);
 #ifdef AEC_TUNING
         if (tune_set("AEC_IDX_DUMP")) {                    // (diagnostics: the guesses against the exits in front)
-            (void)hipStreamSynchronize(st);
+            (void)hipStreamSynchronize(w.st);
             std::vector<LkState> en0(p.nreg), ex0(p.nreg);
             (void)hipMemcpy(en0.data(), en[0], p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
             (void)hipMemcpy(ex0.data(), ex[0], p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
@@ -4994,7 +5005,7 @@ void launch_index_locked(const Cfg &c, const LockPlan &p, const uint32_t *words,
                 if (!mis && r > 6) continue;
                 shown++;
                 fprintf(stderr, "  region %u (from bit %llu): guess (%llu, %u) | exit in front (%llu, %u, st %u)%s\n", r,
-                        (unsigned long long)(start_bit + (uint64_t)r * p.region_bits), (unsigned long long)en0[r].pos, en0[r].b,
+                        (unsigned long long)(w.start_bit + (uint64_t)r * p.region_bits), (unsigned long long)en0[r].pos, en0[r].b,
                         (unsigned long long)ex0[r - 1].pos, ex0[r - 1].b, ex0[r - 1].st, mis ? "  <-- differ" : "");
             }
         }
@@ -5009,18 +5020,18 @@ void launch_index_locked(const Cfg &c, const LockPlan &p, const uint32_t *words,
         const uint32_t passes = tune("AEC_IDX_LOCK_PASSES", p.mode == 1u ? 8u : p.nreg <= 256u ? 4u : 16u);
         for (uint32_t k = 0; k < passes; k++) {
             t.entry = en[cur];
-            hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, st, c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u],
-                               en[cur ^ 1u], 1u, start_bit, start_block);
+            hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u],
+                               en[cur ^ 1u], 1u, w.start_bit, w.start_block);
             cur ^= 1u;
         }
         t.entry = en[cur];
-        hipLaunchKernelGGL(k_lock_fix_w, dim3(1), dim3(64), (size_t)kSwWaveWords * 4, st, c, s, t, ex[cur]);
-        hipLaunchKernelGGL(k_lock_scan, dim3(1), dim3(1024), 0, st, t, (const LkState *)ex[cur]);
-        hipLaunchKernelGGL(k_lock_fill_w, dim3(wg), dim3(64 * wpw), wlds, st, c, s, t, (const LkState *)ex[cur], words, nwords,
-                           d_rsi_off, max_rsi, d_res, tail_slot, rsi_start, start_block);
+        hipLaunchKernelGGL(k_lock_fix_w, dim3(1), dim3(64), (size_t)kSwWaveWords * 4, w.st, w.c, s, t, ex[cur]);
+        hipLaunchKernelGGL(k_lock_scan, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[cur]);
+        hipLaunchKernelGGL(k_lock_fill_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)ex[cur], w.words, w.nwords,
+                           w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, w.rsi_start, w.start_block);
 #ifdef AEC_TUNING
         if (tune_set("AEC_IDX_STATS")) {                   // (diagnostics: synchronises)
-            (void)hipStreamSynchronize(st);
+            (void)hipStreamSynchronize(w.st);
             uint32_t fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             (void)hipMemcpy(fl, t.flags, 32, hipMemcpyDeviceToHost);
             std::vector<LkState> en(p.nreg), exs(p.nreg);
@@ -5045,35 +5056,31 @@ void launch_index_locked(const Cfg &c, const LockPlan &p, const uint32_t *words,
                     "after repairs: %u\n", p.mode, p.nreg, p.region_bits, fl[0], fl[1], fl[2], fl[3], fl[4], mism);
         }
 #endif
-        if (skip_if) hipLaunchKernelGGL(k_lock_merge, dim3(1), dim3(1), 0, st, t.flags, skip_if);
-        if (!serial_fallback) return;                      // (the caller enqueues the trunk behind, skipped if this delivered)
-        hipLaunchKernelGGL(k_index, dim3(1), dim3(64), 0, st, c, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res,
-                           (const uint64_t *)nullptr, (IdxHop *)nullptr, 0u, (IdxCarry *)nullptr, 1u, 1u, start_block, rsi_start,
-                           tail_slot, TwTables{}, (ChunkEntry *)nullptr, SparseTables{}, (uint32_t *)nullptr, (uint64_t)0,
-                           (const uint32_t *)t.flags);
+        if (skip_if) hipLaunchKernelGGL(k_lock_merge, dim3(1), dim3(1), 0, w.st, t.flags, skip_if);
+        if (final) go_index(w, {.skip_if = t.flags});    // (else the next scheme is enqueued behind, skipped if this delivered)
         return;
     }
     if (p.nreg > 1)
-        hipLaunchKernelGGL(k_lock_guess, dim3(p.nreg - 1 < 65536u ? p.nreg - 1 : 65536u), dim3(64), 0, st, c, s, t);
+        hipLaunchKernelGGL(k_lock_guess, dim3(p.nreg - 1 < 65536u ? p.nreg - 1 : 65536u), dim3(64), 0, w.st, w.c, s, t);
     const uint32_t wgrid = (p.nreg + 63) / 64;
     LkState *ex[2] = {t.exit0, t.exit1};
-    hipLaunchKernelGGL(k_lock_walk, dim3(wgrid), dim3(64), 0, st, c, s, t, (const LkState *)nullptr, ex[0], 0u, start_bit,
-                       start_block);
+    hipLaunchKernelGGL(k_lock_walk, dim3(wgrid), dim3(64), 0, w.st, w.c, s, t, (const LkState *)nullptr, ex[0], 0u, w.start_bit,
+                       w.start_block);
     uint32_t cur = 0;
     // (a stretch of k regions with wrong guesses -- incompressible data, where a chain needs far longer to lock -- takes
     // k passes; a pass with nothing to repair is a few microseconds)
     const uint32_t passes = tune("AEC_IDX_LOCK_PASSES", 48);
     for (uint32_t k = 0; k < passes; k++) {
-        hipLaunchKernelGGL(k_lock_walk, dim3(wgrid), dim3(64), 0, st, c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u], 1u,
-                           start_bit, start_block);
+        hipLaunchKernelGGL(k_lock_walk, dim3(wgrid), dim3(64), 0, w.st, w.c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u], 1u,
+                           w.start_bit, w.start_block);
         cur ^= 1u;
     }
-    hipLaunchKernelGGL(k_lock_scan, dim3(1), dim3(1024), 0, st, t, (const LkState *)ex[cur]);
-    hipLaunchKernelGGL(k_lock_fill, dim3(wgrid), dim3(64), 0, st, c, s, t, (const LkState *)ex[cur], words, nwords, d_rsi_off,
-                       max_rsi, d_res, tail_slot, rsi_start, start_block);
+    hipLaunchKernelGGL(k_lock_scan, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[cur]);
+    hipLaunchKernelGGL(k_lock_fill, dim3(wgrid), dim3(64), 0, w.st, w.c, s, t, (const LkState *)ex[cur], w.words, w.nwords,
+                       w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, w.rsi_start, w.start_block);
 #ifdef AEC_TUNING
     if (tune_set("AEC_IDX_STATS")) {                       // (diagnostics: synchronises)
-        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(w.st);
         uint32_t fl[4] = {0, 0, 0, 0};
         (void)hipMemcpy(fl, t.flags, 16, hipMemcpyDeviceToHost);
         std::vector<LkState> en(p.nreg), exs(p.nreg);
@@ -5090,13 +5097,8 @@ void launch_index_locked(const Cfg &c, const LockPlan &p, const uint32_t *words,
                 fl[1], fl[2], mism, ended, refused);
     }
 #endif
-    if (skip_if) hipLaunchKernelGGL(k_lock_merge, dim3(1), dim3(1), 0, st, t.flags, skip_if);
-    if (!serial_fallback) return;
-    // whatever was not delivered: the serial walker, which returns at once otherwise
-    hipLaunchKernelGGL(k_index, dim3(1), dim3(64), 0, st, c, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res,
-                       (const uint64_t *)nullptr, (IdxHop *)nullptr, 0u, (IdxCarry *)nullptr, 1u, 1u, start_block, rsi_start,
-                       tail_slot, TwTables{}, (ChunkEntry *)nullptr, SparseTables{}, (uint32_t *)nullptr, (uint64_t)0,
-                       (const uint32_t *)t.flags);
+    if (skip_if) hipLaunchKernelGGL(k_lock_merge, dim3(1), dim3(1), 0, w.st, t.flags, skip_if);
+    if (final) go_index(w, {.skip_if = t.flags});
 }
 
 // ---- small streams: EVERY bit parsed, the chain of RSI starts by pointer doubling ---------------------------------
@@ -5404,20 +5406,17 @@ __global__ void k_small_begin(uint32_t *flags, SmCursor *cur, uint64_t start_bit
     cur->pad = 0u;
 }
 
-static void launch_index_small(const Cfg &c, const SmallPlan &p, const uint32_t *words, uint64_t nwords, uint64_t end_bit,
-                               uint64_t start_bit, uint64_t *d_rsi_off, uint64_t max_rsi, DecResult *d_res, hipStream_t st,
-                               uint8_t *base, uint64_t rsi_start, uint32_t tail_slot, uint32_t start_block = 0,
-                               const uint32_t *skip_if = nullptr)
+static void launch_index_small(const IdxWalk &w, const SmallPlan &p, uint8_t *base, const uint32_t *skip_if = nullptr)
 {
-    const TrStream s{words, nwords, end_bit};
+    const TrStream s{w.words, w.nwords, w.end_bit};
     uint32_t *flags = reinterpret_cast<uint32_t *>(base + p.o_flags);
     SmCursor *cur = reinterpret_cast<SmCursor *>(base + p.o_flags + 64);
     uint16_t *e0 = reinterpret_cast<uint16_t *>(base + p.o_e0), *e1 = reinterpret_cast<uint16_t *>(base + p.o_e1);
     uint32_t *j[2] = {reinterpret_cast<uint32_t *>(base + p.o_ja), reinterpret_cast<uint32_t *>(base + p.o_jb)};
     uint32_t *sidx = reinterpret_cast<uint32_t *>(base + p.o_s);
     uint32_t *hop = reinterpret_cast<uint32_t *>(base + p.o_h), *hop2 = reinterpret_cast<uint32_t *>(base + p.o_h2);
-    hipLaunchKernelGGL(k_small_begin, dim3(1), dim3(1), 0, st, flags, cur, start_bit, rsi_start, start_block, d_rsi_off, max_rsi,
-                       skip_if);
+    hipLaunchKernelGGL(k_small_begin, dim3(1), dim3(1), 0, w.st, flags, cur, w.start_bit, w.rsi_start, w.start_block, w.d_rsi_off,
+                       w.max_rsi, skip_if);
     // (capped only where the scheme is enqueued as a fallback: a workgroup per 256 bits, retiring as it goes, is 10 - 18 %
     // faster than striding ones where the scheme does run -- 1 MiB streams: 0.37 against 0.47 ms)
     auto capped = [&](uint32_t g, uint32_t most) { return (!skip_if || g < most) ? g : most; };
@@ -5425,32 +5424,29 @@ static void launch_index_small(const Cfg &c, const SmallPlan &p, const uint32_t 
     const uint32_t rgrid = (p.nbits + 1u + kSmRsiWg - 1u) / kSmRsiWg;
     const uint32_t sgrid = capped((p.scap + kSmRsiWg - 1u) / kSmRsiWg > rgrid ? (p.scap + kSmRsiWg - 1u) / kSmRsiWg : rgrid, kSmGrid / 4u);
     for (uint32_t piece = 0; piece < p.npieces; piece++) {
-        hipLaunchKernelGGL(k_small_parse, dim3(grid), dim3(256), 0, st, c, s, (const SmCursor *)cur, p.nbits, e0, e1);
+        hipLaunchKernelGGL(k_small_parse, dim3(grid), dim3(256), 0, w.st, w.c, s, (const SmCursor *)cur, p.nbits, e0, e1);
         if (p.hops)
-            hipLaunchKernelGGL(k_small_hop, dim3(grid), dim3(256), 0, st, c, (const SmCursor *)cur, end_bit, p.nbits,
+            hipLaunchKernelGGL(k_small_hop, dim3(grid), dim3(256), 0, w.st, w.c, (const SmCursor *)cur, w.end_bit, p.nbits,
                                (const uint16_t *)e0, hop);
         if (p.hops > 1u)
-            hipLaunchKernelGGL(k_small_hop2, dim3(grid), dim3(256), 0, st, (const SmCursor *)cur, end_bit, p.nbits,
+            hipLaunchKernelGGL(k_small_hop2, dim3(grid), dim3(256), 0, w.st, (const SmCursor *)cur, w.end_bit, p.nbits,
                                (const uint32_t *)hop, hop2);
-        hipLaunchKernelGGL(k_small_rsi, dim3(sgrid), dim3(kSmRsiWg), 0, st, c, (const SmCursor *)cur, end_bit, p.nbits,
+        hipLaunchKernelGGL(k_small_rsi, dim3(sgrid), dim3(kSmRsiWg), 0, w.st, w.c, (const SmCursor *)cur, w.end_bit, p.nbits,
                            (const uint16_t *)e0, (const uint16_t *)e1, (const uint32_t *)(p.hops ? hop : nullptr),
-                           (const uint32_t *)(p.hops > 1u ? hop2 : nullptr), j[0], sidx, p.scap, start_block);
+                           (const uint32_t *)(p.hops > 1u ? hop2 : nullptr), j[0], sidx, p.scap, w.start_block);
         for (uint32_t k = 0; k < p.levels; k++) {
             const uint32_t quarter = 1u << (2u * k), last = k + 1u == p.levels ? 1u : 0u;
             const uint32_t gq = capped((quarter + 255u) / 256u, kSmGrid);
             const uint32_t g = last ? gq : (gq > grid ? gq : grid);
-            hipLaunchKernelGGL(k_small_double, dim3(g), dim3(256), 0, st, (const SmCursor *)cur, end_bit, p.nbits,
+            hipLaunchKernelGGL(k_small_double, dim3(g), dim3(256), 0, w.st, (const SmCursor *)cur, w.end_bit, p.nbits,
                                (const uint32_t *)j[k & 1u], j[(k & 1u) ^ 1u], sidx, quarter, p.scap, last);
         }
         if (tune("AEC_IDX_SMALL_FINISH", 1))
-            hipLaunchKernelGGL(k_small_finish, dim3(1), dim3(1024), 0, st, c, s, cur, p.nbits, (const uint32_t *)sidx, p.scap, words,
-                               nwords, d_rsi_off, max_rsi, d_res, tail_slot, flags, start_block);
+            hipLaunchKernelGGL(k_small_finish, dim3(1), dim3(1024), 0, w.st, w.c, s, cur, p.nbits, (const uint32_t *)sidx, p.scap, w.words,
+                               w.nwords, w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, flags, w.start_block);
     }
     // whatever was not delivered: the serial walker, which returns at once otherwise
-    hipLaunchKernelGGL(k_index, dim3(1), dim3(64), 0, st, c, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res,
-                       (const uint64_t *)nullptr, (IdxHop *)nullptr, 0u, (IdxCarry *)nullptr, 1u, 1u, start_block, rsi_start, tail_slot,
-                       TwTables{}, (ChunkEntry *)nullptr, SparseTables{}, (uint32_t *)nullptr, (uint64_t)0,
-                       (const uint32_t *)flags);
+    go_index(w, {.skip_if = flags});
 }
 
 }  // namespace
@@ -5476,7 +5472,6 @@ static void idx_tuning_sync()
 //  * behind the window tables of a stream of one piece (2^24 bits), whose walker gives up after kSparseSerialCap blocks
 //    walked serially (k_index: serial_cap).
 // 256 bytes in front of its workspace hold the flag "the scheme in front has delivered".
-constexpr uint32_t kSparseSerialCap = 2048;
 static SmallPlan small_fallback_plan(const Cfg &c, uint64_t total_bits, uint64_t max_rsi, uint32_t start_block,
                                      uint64_t rsi_bits_hint, bool behind_tables)
 {
@@ -5490,52 +5485,146 @@ static SmallPlan small_fallback_plan(const Cfg &c, uint64_t total_bits, uint64_t
     return small_plan(c, total_bits, max_rsi, start_block, rsi_bits_hint, true);
 }
 
-int index_scheme(const Cfg &c, size_t in_bytes, uint64_t rsi_bits_hint, uint32_t start_block)
+// ---- the chain: which schemes an index pass enqueues, one behind the other, and where in the workspace ----------------
+// index_chain states the cascade ONCE: launch_index, index_scheme, index_plan and the two workspace sizes read its list.
+enum : int { IDX_SERIAL = 0, IDX_LOCKED = 1, IDX_TABLES = 2, IDX_TRUNK = 3, IDX_EVERY_BIT = 4, IDX_REGIONS = 5 };
+constexpr size_t kNoFlag = ~(size_t)0, kWsAsk = ~(size_t)0;
+
+struct IdxStage {
+    int scheme;
+    size_t off, bytes;               // its part of the workspace
+    size_t skip_off;                 // the flag it waits on (kNoFlag: none): != 0 there = a stage in front has delivered
+    union { SmallPlan sm; RegionPlan rg; LockPlan lk; Sparse2Plan sp; TrunkPlan tr; };       // the plan of its scheme
+};
+struct IdxChain {
+    uint32_t n;
+    IdxStage s[kIdxMaxStages];
+    size_t bytes;                    // extent of the stages in the workspace
+};
+
+// What the caller of a pass brings, filled by name.  As it stands: what the sizing assumes -- a plain pass over a whole
+// stream from an RSI start, no workspace yet.
+struct IdxOpt {
+    uint32_t start_block = 0;
+    uint64_t max_rsi = 1ull << 62;
+    bool segments = false;           // the pass is to leave segment starts (d_seg_bits): schemes 4 and 1 deliver none
+    bool piece = false;              // a piece of a longer stream (stop_near): no every-bit scheme, first or as a fallback
+    size_t ws_bytes = kWsAsk;        // what is on offer (what does not fit is left out); kWsAsk: laid out as the sizing always has
+    bool every_bit_first = true;     // (the sizing also wants the chain there would be without it)
+};
+
+IdxChain index_chain(const Cfg &c, size_t in_bytes, uint64_t start_bit, uint64_t hint, const IdxOpt &o = {})
 {
-    const uint64_t bits = (uint64_t)in_bytes * 8;
-    if (!bits) return 0;
-    if (small_plan(c, bits, 1ull << 62, start_block, rsi_bits_hint).ok) return 4;
-    if (region_plan(c, bits, rsi_bits_hint, false).ok) return 5;
-    if (lock_plan(c, bits, rsi_bits_hint, start_block).ok) return 1;
-    if (sparse2_plan(c, bits, rsi_bits_hint).ok) return 2;
-    return trunk_plan(c, bits, rsi_bits_hint, 0).ok ? 3 : 0;
+    IdxChain ch{};
+    const uint64_t end_bit = (uint64_t)in_bytes * 8, bits = start_bit < end_bit ? end_bit - start_bit : 0;
+    size_t used = 0, flag = kNoFlag;                       // workspace taken; the flag of the last stage so far
+    const size_t ws = o.ws_bytes;
+    const bool ask = ws == kWsAsk;
+    auto fits = [&](size_t need) { return ws - used >= need; };
+    // (raises: where in its part a stage says that it delivered -- the flag the stages behind it wait on)
+    auto push = [&](int scheme, size_t bytes, size_t raises = kNoFlag) -> IdxStage & {
+        ch.s[ch.n] = IdxStage{scheme, used, bytes, flag, {}};
+        if (raises != kNoFlag) flag = used + raises;
+        ch.bytes = used += bytes;
+        return ch.s[ch.n++];
+    };
+    if (!bits || !ws) {
+        push(IDX_SERIAL, 0);
+        return ch;
+    }
+    // a small stream (a chunk of a dataset): every bit parsed, the RSI starts by pointer doubling -- alone
+    const bool alone = o.every_bit_first && !o.segments && !o.piece;
+    const SmallPlan sm = alone ? small_plan(c, bits, o.max_rsi, o.start_block, hint) : SmallPlan{};
+    if (sm.ok && fits(sm.bytes)) {
+        push(IDX_EVERY_BIT, sm.bytes).sm = sm;
+        return ch;
+    }
+    // a large stream: regions walked from guessed entries, the schemes below behind them (sizing: with room for the segment
+    // starts wherever the decoder takes them, though the rest of the chain is that of a pass without them; want_segments
+    // only adds that room to .bytes, never changes .ok: index_scheme, which asked without it, names the same first scheme)
+    const RegionPlan rp = region_plan(c, bits, hint, ask ? decode_bare_supported(c) : o.segments);
+    if (rp.ok && fits(rp.bytes)) push(IDX_REGIONS, rp.bytes, rp.o_flags).rg = rp;
+    const LockPlan lp = o.segments ? LockPlan{} : lock_plan(c, bits, hint, o.start_block);
+    if (lp.ok && fits(lp.bytes)) {
+        push(IDX_LOCKED, lp.bytes, lp.o_flags).lk = lp;
+        if (lp.mode == 0u) return ch;
+        // Entries by plausibility, the exact machinery of the phase-locked scheme behind them -- and behind that, for the
+        // streams whose options say nothing, what would have run without: the every-bit scheme piece by piece (256 bytes
+        // in front of its tables: small_fallback_plan), else the 64 agreeing chains where RSIs are short, then the trunk.
+        // (The sizing asks for the first alone where it applies; a piece of a longer stream, or a workspace smaller than
+        // asked for, takes what fits of the second list.)
+        const SmallPlan fb = o.piece ? SmallPlan{} : small_fallback_plan(c, bits, o.max_rsi, o.start_block, hint, false);
+        if (fb.ok && fits(256 + fb.bytes)) {
+            used += 256;
+            push(IDX_EVERY_BIT, fb.bytes).sm = fb;
+            return ch;
+        }
+        const LockPlan l0 = lock_plan_alt(c, bits, hint, o.start_block);
+        const bool have0 = l0.ok && fits(l0.bytes);
+        const TrunkPlan tp = trunk_plan(c, bits, hint, ask ? 0 : ws - used - (have0 ? l0.bytes : 0));
+        if (have0) push(IDX_LOCKED, l0.bytes, l0.o_flags).lk = l0;
+        if (tp.ok) push(IDX_TRUNK, tp.bytes).tr = tp;
+        return ch;
+    }
+    // Low-entropy streams whose RSIs fit a window: candidates and RSI hypotheses per window (k_spec2)
+    const Sparse2Plan sp = sparse2_plan(c, bits, hint);
+    if (sp.ok) {
+        // One span of tables of a stream nothing ran in front of: the walker may give the stream up (serial_cap), the
+        // every-bit scheme behind takes it then; the 256 bytes between the two hold the walker's word that it delivered.
+        // (The sizing has never looked at the regions in front: kept.  The one-span test cannot fail here: a span is all
+        // the stream's windows or kS2SuperWindows of 8192 bits and more, the fallback's streams are shorter.)
+        static_assert(kSmMaxBits + kS2WindowBits <= kS2SuperWindows * 8192ull, "the every-bit fallback's streams fit a span");
+        const uint64_t span = (uint64_t)sp.nwin_max * sp.g.core, reach = bits + (ask ? 0 : start_bit % sp.g.core);
+        const bool behind = !o.piece && (flag == kNoFlag || ask);
+        const SmallPlan fb = behind ? small_fallback_plan(c, bits, o.max_rsi, o.start_block, hint, true) : SmallPlan{};
+        if (fb.ok && fits(sp.bytes + 256 + fb.bytes) && reach <= span) {
+            push(IDX_TABLES, sp.bytes, sp.bytes).sp = sp;
+            used += 256;
+            push(IDX_EVERY_BIT, fb.bytes).sm = fb;
+            return ch;
+        }
+        // (many spans of windows: two sets of tables, so that the spans can be pipelined -- launch_index_sparse)
+        const bool two = reach > (kS2PipeSpans - 1) * span && fits(2 * sp.bytes);
+        if (fits(sp.bytes)) {
+            push(IDX_TABLES, two ? 2 * sp.bytes : sp.bytes).sp = sp;
+            return ch;
+        }
+    }
+    // everything else: the trunk with as many windows per span as the workspace holds, else the serial walk alone
+    const TrunkPlan tp = ws > used ? trunk_plan(c, bits, hint, ask ? 0 : ws - used) : TrunkPlan{};
+    if (tp.ok) push(IDX_TRUNK, tp.bytes).tr = tp;
+    else push(IDX_SERIAL, 0);
+    return ch;
 }
 
-
-size_t index_workspace_bytes(const Cfg &c, size_t in_bytes, uint64_t start_bit, uint64_t rsi_bits_hint)
+int index_scheme(const Cfg &c, size_t in_bytes, uint64_t rsi_bits_hint, uint32_t start_block)
 {
-    const uint64_t end_bit = (uint64_t)in_bytes * 8;
-    if (start_bit >= end_bit) return 0;
-    // (a small stream: the brute-force scheme for a walk from an RSI start, the others for one that resumes inside)
-    const SmallPlan sm = small_plan(c, end_bit - start_bit, 1ull << 62, 0u, rsi_bits_hint);
-    // (the regions in front of whatever would run without them)
-    const RegionPlan rp = region_plan(c, end_bit - start_bit, rsi_bits_hint, decode_bare_supported(c));
-    const size_t rest = index_workspace_bytes_large(c, in_bytes, start_bit, rsi_bits_hint) + (rp.ok ? rp.bytes : 0);
-    return sm.ok && sm.bytes > rest ? sm.bytes : rest;
+    return index_chain(c, in_bytes, 0, rsi_bits_hint, {.start_block = start_block}).s[0].scheme;
 }
 
 size_t index_workspace_bytes_large(const Cfg &c, size_t in_bytes, uint64_t start_bit, uint64_t rsi_bits_hint)
 {
-    const uint64_t end_bit = (uint64_t)in_bytes * 8;
-    if (start_bit >= end_bit) return 0;
-    const LockPlan lp = lock_plan(c, end_bit - start_bit, rsi_bits_hint, 0u);
-    if (lp.ok && lp.mode == 0u) return lp.bytes;
-    if (lp.ok) {                                           // (mode 1: + what runs behind it for the streams it abandons)
-        const SmallPlan fb = small_fallback_plan(c, end_bit - start_bit, 1ull << 62, 0u, rsi_bits_hint, false);
-        if (fb.ok) return lp.bytes + 256 + fb.bytes;
-        const LockPlan l0 = lock_plan_alt(c, end_bit - start_bit, rsi_bits_hint, 0u);
-        const TrunkPlan tp = trunk_plan(c, end_bit - start_bit, rsi_bits_hint, 0);
-        return lp.bytes + (l0.ok ? l0.bytes : 0) + (tp.ok ? tp.bytes : 0);
-    }
-    const Sparse2Plan sp = sparse2_plan(c, end_bit - start_bit, rsi_bits_hint);
-    if (sp.ok) {
-        // (many spans of windows: two sets of tables, so that the spans can be pipelined -- launch_index_sparse)
-        const uint64_t span = (uint64_t)sp.nwin_max * sp.g.core;
-        const SmallPlan fb = small_fallback_plan(c, end_bit - start_bit, 1ull << 62, 0u, rsi_bits_hint, true);
-        return (end_bit - start_bit > (kS2PipeSpans - 1) * span ? 2 * sp.bytes : sp.bytes) + (fb.ok ? 256 + fb.bytes : 0);
-    }
-    const TrunkPlan p = trunk_plan(c, end_bit - start_bit, rsi_bits_hint, 0);
-    return p.ok ? p.bytes : 0;
+    const IdxChain ch = index_chain(c, in_bytes, start_bit, rsi_bits_hint, {.every_bit_first = false});
+    return ch.bytes - (ch.s[0].scheme == IDX_REGIONS ? ch.s[0].bytes : 0);
+}
+
+// (a small stream: the every-bit scheme for a walk from an RSI start, the others for one that resumes inside -- the larger)
+size_t index_workspace_bytes(const Cfg &c, size_t in_bytes, uint64_t start_bit, uint64_t rsi_bits_hint)
+{
+    const size_t first = index_chain(c, in_bytes, start_bit, rsi_bits_hint).bytes;
+    const size_t rest = index_chain(c, in_bytes, start_bit, rsi_bits_hint, {.every_bit_first = false}).bytes;
+    return first > rest ? first : rest;
+}
+
+int index_plan(const Cfg &c, size_t in_bytes, uint64_t rsi_bits_hint, uint32_t start_block, bool want_segments, bool piece,
+               size_t ws_bytes, int ids[kIdxMaxStages], size_t *used)
+{
+    const IdxOpt o{.start_block = start_block, .segments = want_segments && decode_bare_supported(c), .piece = piece,
+                   .ws_bytes = ws_bytes ? ws_bytes : index_workspace_bytes(c, in_bytes, 0, rsi_bits_hint)};
+    const IdxChain ch = index_chain(c, in_bytes, 0, rsi_bits_hint, o);
+    for (uint32_t i = 0; i < ch.n; i++) ids[i] = ch.s[i].scheme;
+    *used = ch.bytes;
+    return (int)ch.n;
 }
 
 bool launch_index(const Cfg &c, const uint8_t *d_in, size_t in_bytes, uint64_t start_bit,
@@ -5543,115 +5632,31 @@ bool launch_index(const Cfg &c, const uint8_t *d_in, size_t in_bytes, uint64_t s
                   void *d_ws, size_t ws_bytes, uint64_t rsi_bits_hint, uint32_t start_block, uint64_t rsi_start,
                   uint32_t tail_slot, uint64_t *d_seg_bits, uint64_t stop_near)
 {
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_in);
-    const uint64_t nwords = (in_bytes + 3) / 4, end_bit = (uint64_t)in_bytes * 8;
+    const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, start_bit,
+                    d_rsi_off, max_rsi, d_res, st, start_block, tail_slot, rsi_start, d_seg_bits, stop_near};
     idx_tuning_sync();
-    // Low-entropy streams whose RSIs fit a window: candidates and RSI hypotheses per window (k_spec2); everything
-    // else: the trunk.
-    // a small stream (a chunk of a dataset): every bit parsed, the RSI starts by pointer doubling
-    if (d_ws && ws_bytes && start_bit < end_bit && !d_seg_bits && !stop_near) {
-        const SmallPlan sm = small_plan(c, end_bit - start_bit, max_rsi, start_block, rsi_bits_hint);
-        if (sm.ok && ws_bytes >= sm.bytes) {
-            launch_index_small(c, sm, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st,
-                               static_cast<uint8_t *>(d_ws), rsi_start, tail_slot, start_block);
-            return false;
-        }
-    }
-    // a large stream: regions walked from guessed entries; the schemes below are enqueued behind and return at once
-    // where it has delivered
-    const uint32_t *done = nullptr;
+    const IdxOpt o{.start_block = start_block, .max_rsi = max_rsi, .segments = d_seg_bits != nullptr, .piece = stop_near != 0,
+                   .ws_bytes = d_ws ? ws_bytes : 0};
+    const IdxChain ch = index_chain(c, in_bytes, start_bit, rsi_bits_hint, o);
+    uint8_t *base = static_cast<uint8_t *>(d_ws);
+    auto flag_at = [&](size_t off) { return off == kNoFlag ? nullptr : reinterpret_cast<uint32_t *>(base + off); };
+    // (segment starts come from the regions and the trunk; what neither delivers stays ~0: decoded by one lane each)
     bool segs_filled = false;
-    if (d_ws && ws_bytes && start_bit < end_bit) {
-        const RegionPlan rp = region_plan(c, end_bit - start_bit, rsi_bits_hint, d_seg_bits != nullptr);
-        if (rp.ok && ws_bytes >= rp.bytes) {
-            done = launch_index_regions(c, rp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st,
-                                        static_cast<uint8_t *>(d_ws), start_block, rsi_start, tail_slot, d_seg_bits);
-            d_ws = static_cast<uint8_t *>(d_ws) + rp.bytes;
-            ws_bytes -= rp.bytes;
-            segs_filled = d_seg_bits != nullptr;
+    for (uint32_t i = 0; i < ch.n; i++) {
+        const IdxStage &s = ch.s[i];
+        const uint32_t *skip_if = flag_at(s.skip_off);
+        uint32_t *delivered = (s.scheme == IDX_TABLES && i + 1 < ch.n) ? flag_at(s.off + s.bytes) : nullptr;
+        switch (s.scheme) {
+        case IDX_EVERY_BIT: launch_index_small(w, s.sm, base + s.off, skip_if); break;
+        case IDX_REGIONS: launch_index_regions(w, s.rg, base + s.off, skip_if); break;
+        case IDX_LOCKED: launch_index_locked(w, s.lk, base + s.off, i + 1 == ch.n, skip_if); break;
+        case IDX_TABLES: launch_index_sparse(w, s.sp, base + s.off, s.bytes, skip_if, delivered); break;
+        case IDX_TRUNK: launch_index_trunk(w, s.tr, base + s.off, skip_if); break;
+        default: go_index(w, {.skip_if = skip_if}); break;
         }
+        segs_filled = segs_filled || s.scheme == IDX_REGIONS || s.scheme == IDX_TRUNK;
     }
-    if (d_ws && ws_bytes && start_bit < end_bit && !d_seg_bits) {
-        const LockPlan lp = lock_plan(c, end_bit - start_bit, rsi_bits_hint, start_block);
-        if (lp.ok && lp.mode == 0u && ws_bytes >= lp.bytes) {
-            launch_index_locked(c, lp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st,
-                                static_cast<uint8_t *>(d_ws), start_block, rsi_start, tail_slot, true, done);
-            return false;
-        }
-        if (lp.ok && lp.mode == 1u && ws_bytes >= lp.bytes) {
-            // entries by plausibility, the exact machinery of the phase-locked scheme behind them -- and behind that, for
-            // the streams whose options say nothing, what would have run without: the 64 agreeing chains where RSIs are
-            // short, then the trunk; every kernel of a later scheme returns at once if the stream has been delivered
-            uint8_t *wb = static_cast<uint8_t *>(d_ws);
-            size_t used = lp.bytes;
-            // (streams of up to 2^28 bits: the every-bit scheme piece by piece in place of both -- small_fallback_plan)
-            const SmallPlan fb = stop_near ? SmallPlan{}
-                                           : small_fallback_plan(c, end_bit - start_bit, max_rsi, start_block, rsi_bits_hint, false);
-            if (fb.ok && ws_bytes >= used + 256 + fb.bytes) {
-                launch_index_locked(c, lp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb, start_block,
-                                    rsi_start, tail_slot, false, done);
-                launch_index_small(c, fb, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb + used + 256,
-                                   rsi_start, tail_slot, start_block, reinterpret_cast<const uint32_t *>(wb + lp.o_flags));
-                return false;
-            }
-            const LockPlan l0 = lock_plan_alt(c, end_bit - start_bit, rsi_bits_hint, start_block);
-            const bool have0 = l0.ok && ws_bytes >= used + l0.bytes;
-            const size_t off0 = used;
-            if (have0) used += l0.bytes;
-            const TrunkPlan tp = trunk_plan(c, end_bit - start_bit, rsi_bits_hint, ws_bytes - used);
-            launch_index_locked(c, lp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb, start_block,
-                                rsi_start, tail_slot, !tp.ok && !have0, done);
-            done = reinterpret_cast<const uint32_t *>(wb + lp.o_flags);
-            if (have0) {
-                launch_index_locked(c, l0, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb + off0,
-                                    start_block, rsi_start, tail_slot, !tp.ok, done);
-                done = reinterpret_cast<const uint32_t *>(wb + off0 + l0.o_flags);
-            }
-            if (tp.ok)
-                launch_index_trunk(c, tp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb + used,
-                                   start_block, rsi_start, tail_slot, nullptr, done);
-            return false;
-        }
-    }
-    if (d_ws && ws_bytes && start_bit < end_bit) {
-        const Sparse2Plan sp = sparse2_plan(c, end_bit - start_bit, rsi_bits_hint);
-        const SmallPlan fb = (sp.ok && !stop_near && !done)
-                                 ? small_fallback_plan(c, end_bit - start_bit, max_rsi, start_block, rsi_bits_hint, true)
-                                 : SmallPlan{};
-        if (sp.ok && fb.ok && ws_bytes >= sp.bytes + 256 + fb.bytes &&
-            end_bit - start_bit / sp.g.core * sp.g.core <= (uint64_t)sp.nwin_max * sp.g.core) {
-            // (one span of tables: the walker may give the stream up, the every-bit scheme behind it takes it then)
-            uint8_t *wb = static_cast<uint8_t *>(d_ws);
-            uint32_t *delivered = reinterpret_cast<uint32_t *>(wb + sp.bytes);
-            (void)hipMemsetAsync(delivered, 0, 4, st);
-            launch_index_sparse(c, sp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb, sp.bytes,
-                                start_block, rsi_start, tail_slot, 0ull, nullptr, (uint32_t)tune("AEC_IDX_SPARSE_SERIAL_CAP", kSparseSerialCap),
-                                delivered);
-            launch_index_small(c, fb, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st, wb + sp.bytes + 256,
-                               rsi_start, tail_slot, start_block, delivered);
-            return segs_filled;
-        }
-        if (sp.ok && ws_bytes >= sp.bytes) {
-            launch_index_sparse(c, sp, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st,
-                                static_cast<uint8_t *>(d_ws), ws_bytes, start_block, rsi_start, tail_slot, stop_near, done);
-            // (segment starts the regions did not deliver stay ~0: such RSIs are decoded by one lane each)
-            return segs_filled;
-        }
-    }
-    TrunkPlan p{};
-    if (d_ws && ws_bytes && start_bit < end_bit) p = trunk_plan(c, end_bit - start_bit, rsi_bits_hint, ws_bytes);
-    if (!p.ok) {                                       // serial walk only
-        hipLaunchKernelGGL(k_index, dim3(1), dim3(64), 0, st, c, words, nwords, end_bit, start_bit, d_rsi_off,
-                           max_rsi, d_res, (const uint64_t *)nullptr, (IdxHop *)nullptr, 0u, (IdxCarry *)nullptr, 1u,
-                           1u, start_block, rsi_start, tail_slot, TwTables{}, (ChunkEntry *)nullptr, SparseTables{},
-                           (uint32_t *)nullptr, (uint64_t)0, done);
-        return segs_filled;
-    }
-    // (segment starts: the caller has set the table to ~0; the RSI the walk resumes in has none -- its first
-    // blocks lie in front of the walk)
-    launch_index_trunk(c, p, words, nwords, end_bit, start_bit, d_rsi_off, max_rsi, d_res, st,
-                       static_cast<uint8_t *>(d_ws), start_block, rsi_start, tail_slot, d_seg_bits, done);
-    return d_seg_bits != nullptr;
+    return d_seg_bits != nullptr && segs_filled;
 }
 
 // Batch over the window tables: how many hops a stream of max_chunk_bytes may take, and the workspace
@@ -5683,48 +5688,27 @@ void launch_index_batch(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
 {
     if (n_chunks == 0) return;
     idx_tuning_sync();
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_in);
-    const uint64_t nwords = (in_bytes + 3) / 4, end_bit = (uint64_t)in_bytes * 8;
+    // (every stream a walk of its own from its first bit: rsi_per_chunk offsets and a result record each)
+    const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, 0, d_rsi_off,
+                    rsi_per_chunk, d_res, st, 0u, 0u, 0, nullptr, 0};
     const size_t need = d_ws ? index_batch_workspace_bytes(c, in_bytes, n_chunks, max_chunk_bytes, rsi_bits_hint) : 0;
     if (!need || ws_bytes < need) {
-        hipLaunchKernelGGL(k_index, dim3((uint32_t)n_chunks), dim3(64), 0, st, c, words, nwords, end_bit, (uint64_t)0,
-                           d_rsi_off, rsi_per_chunk, d_res, d_chunk_off, (IdxHop *)nullptr, 0u, (IdxCarry *)nullptr, 1u,
-                           1u, 0u, (uint64_t)0, 0u, TwTables{}, (ChunkEntry *)nullptr, SparseTables{});
+        go_index(w, {.chunk_off = d_chunk_off, .n_chunks = n_chunks});
         return;
     }
     allow_big_lds2();
-    const Sparse2Plan p = sparse2_plan(c, end_bit, rsi_bits_hint);
+    const Sparse2Plan p = sparse2_plan(c, w.end_bit, rsi_bits_hint);
     uint8_t *base = static_cast<uint8_t *>(d_ws);
-    const uint32_t nwin = (uint32_t)((end_bit + p.g.core - 1) / p.g.core);
-    SparseTables t;
-    t.bitmap = reinterpret_cast<const uint32_t *>(base + p.o_bitmap);
-    t.pre = reinterpret_cast<const uint16_t *>(base + p.o_pre);
-    t.rec = reinterpret_cast<const uint2 *>(base + p.o_rec);
-    t.cpos = reinterpret_cast<const uint16_t *>(base + p.o_cpos);
-    t.ccnt = reinterpret_cast<const uint32_t *>(base + p.o_ccnt);
-    t.lo = 0;
-    t.hi = (uint64_t)nwin * p.g.core;
-    t.core = p.g.core;
-    t.cap = p.g.cap_core;
+    const uint32_t nwin = (uint32_t)((w.end_bit + p.g.core - 1) / p.g.core);
+    SparseTables t = sparse_tables(p, base, 0, nwin, nullptr);
     t.wide = nullptr;
-    t.wpc = p.wpc;
     const uint32_t hop_cap = batch_hop_cap(p, max_chunk_bytes);
     IdxHop *hops = reinterpret_cast<IdxHop *>(base + p.bytes);
     uint32_t *nhops = reinterpret_cast<uint32_t *>(base + p.bytes +
                                                    (((size_t)n_chunks * hop_cap * sizeof(IdxHop) + 255) & ~(size_t)255));
-    if (p.g.v4)
-        hipLaunchKernelGGL(k_spec4, dim3(nwin), dim3(1024), p.lds, st, c, words, nwords, end_bit, (uint64_t)0, (uint64_t)0, p.g,
-                           const_cast<uint32_t *>(t.bitmap), const_cast<uint16_t *>(t.pre), const_cast<uint2 *>(t.rec),
-                           const_cast<uint16_t *>(t.cpos), const_cast<uint32_t *>(t.ccnt), (unsigned long long *)nullptr,
-                           d_chunk_off, (uint32_t)n_chunks);
-    else
-        hipLaunchKernelGGL(k_spec2, dim3(nwin), dim3(1024), p.lds, st, c, words, nwords, end_bit, (uint64_t)0, (uint64_t)0, p.g,
-                           const_cast<uint32_t *>(t.bitmap), const_cast<uint16_t *>(t.pre), const_cast<uint2 *>(t.rec),
-                           const_cast<uint16_t *>(t.cpos), const_cast<uint32_t *>(t.ccnt), (unsigned long long *)nullptr,
-                           d_chunk_off, (uint32_t)n_chunks);
-    hipLaunchKernelGGL(k_index, dim3((uint32_t)n_chunks), dim3(64), 0, st, c, words, nwords, end_bit, (uint64_t)0, d_rsi_off,
-                       rsi_per_chunk, d_res, d_chunk_off, hops, hop_cap, (IdxCarry *)nullptr, 1u, 1u, 0u, (uint64_t)0, 0u,
-                       TwTables{}, (ChunkEntry *)nullptr, t, nhops);
+    go_spec(p.g.v4 != 0, nwin, p.lds, st, w, 0, p.g, t, nullptr, d_chunk_off, (uint32_t)n_chunks, nullptr, nullptr);
+    go_index(w, {.chunk_off = d_chunk_off, .n_chunks = n_chunks, .hops = hops, .hop_cap = hop_cap, .s2 = t,
+                 .batch_nhops = nhops});
     hipLaunchKernelGGL(k_expand2, dim3((uint32_t)(((uint64_t)n_chunks * hop_cap + 255) / 256)), dim3(256), 0, st, t,
                        (const IdxCarry *)nullptr, hops, nhops, (uint32_t)n_chunks, hop_cap, d_rsi_off, rsi_per_chunk);
 }

@@ -156,17 +156,25 @@ bool launch_decode_bare(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
 // workspace (index_workspace_bytes() says how much is wanted, 0 = this input takes the serial walk alone;
 // less than that means more, smaller spans) the walk hops over the trunk tables built by all CUs (aec_idx.hip).
 // rsi_bits_hint: estimate of the coded size of one RSI (0 = unknown); it sizes burn-in, regions and records.
+// The two sizes, index_scheme and index_plan below read the chain index_chain builds (aec_idx.hip), as launch_index does.
 size_t index_workspace_bytes(const Cfg &c, size_t in_bytes, uint64_t start_bit, uint64_t rsi_bits_hint);
 // ... without the every-bit scheme's tables (8 .. 16 bytes per bit of a small stream): what to ask for when the full
 // size cannot be had -- launch_index takes whatever scheme the workspace it is given has room for
 size_t index_workspace_bytes_large(const Cfg &c, size_t in_bytes, uint64_t start_bit, uint64_t rsi_bits_hint);
 bool index_is_windowed(const Cfg &c, size_t in_bytes, uint64_t rsi_bits_hint);
-// the scheme launch_index takes with the workspace index_workspace_bytes asks for: 0 serial walk, 1 phase-locked
+// the FIRST scheme launch_index takes with the workspace index_workspace_bytes asks for: 0 serial walk, 1 phase-locked
 // chains, 2 window tables, 3 trunk, 4 every bit parsed (small streams), 5 regions walked from guessed entries (large
 // streams; what it does not deliver is left to the scheme this function would name without it).  It describes the plain
 // index pass (aec_gpu_index_async / aec_gpu_index_resume_async): with segment starts (d_seg_bits) or as a piece of a
 // longer stream (stop_near) launch_index skips schemes 4 and 1, which deliver neither.
 int index_scheme(const Cfg &c, size_t in_bytes, uint64_t rsi_bits_hint, uint32_t start_block);
+// The CHAIN launch_index enqueues: the scheme ids in order (a later one returns at once where one in front has delivered;
+// the serial walk that schemes 1 and 4 enqueue behind themselves is not listed, 0 stands for the serial walk alone).
+// want_segments / piece: the pass gets d_seg_bits / stop_near (below); ws_bytes: the workspace on offer, 0 = what
+// index_workspace_bytes asks for.  Returns the number of ids (at most kIdxMaxStages); *used: the extent of the stages.
+constexpr int kIdxMaxStages = 6;
+int index_plan(const Cfg &c, size_t in_bytes, uint64_t rsi_bits_hint, uint32_t start_block, bool want_segments, bool piece,
+               size_t ws_bytes, int ids[kIdxMaxStages], size_t *used);
 // d_seg_bits (optional; (max_rsi + 1) * segs_per_rsi entries, set to ~0 by the caller): where the index runs over
 // the trunk tables it also leaves the start bit of every segment of the RSIs it finds (launch_decode_bare); the
 // return value says whether it did.
@@ -179,10 +187,22 @@ bool launch_index(const Cfg &c, const uint8_t *d_in, size_t in_bytes, uint64_t s
                   uint32_t start_block = 0, uint64_t rsi_start = 0, uint32_t tail_slot = 0,
                   uint64_t *d_seg_bits = nullptr, uint64_t stop_near = 0);
 
+// One walk of an index pass: the stream, where the walk begins and where its results go.  launch_index fills it once and
+// every scheme's launcher takes it with its plan and its part of the workspace (launch_index_*(walk, plan, ws, ...)).
+struct IdxWalk {
+    Cfg c;
+    const uint32_t *words;
+    uint64_t nwords, end_bit, start_bit, *d_rsi_off, max_rsi;
+    DecResult *d_res;
+    hipStream_t st;
+    uint32_t start_block, tail_slot;
+    uint64_t rsi_start, *d_seg_bits, stop_near;
+};
+
 // The region index (aec_region.hip): large preprocessed streams -- a lane per region guesses the first RSI start behind
 // the region's first bit from the options around it, lanes walk the regions from their entries, every entry is checked
-// against the walk in front and mended; delivers only if all agree.  Returns the device flag that is != 0 once the
-// stream has been delivered (the skip_if of the schemes enqueued behind).
+// against the walk in front and mended; delivers only if all agree.  The word at ws + o_flags is != 0 once the stream has
+// been delivered (the skip_if of the schemes enqueued behind).
 struct RegionPlan {
     bool ok;
     uint32_t nreg, budget, passes, avg_cds, K;
@@ -190,10 +210,7 @@ struct RegionPlan {
     size_t o_flags, o_found, o_entry[2], o_exit[2], o_cnt[2], o_base, o_list, o_slist, bytes;
 };
 RegionPlan region_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, bool want_segments);
-const uint32_t *launch_index_regions(const Cfg &c, const RegionPlan &p, const uint32_t *words, uint64_t nwords,
-                                     uint64_t end_bit, uint64_t start_bit, uint64_t *d_rsi_off, uint64_t max_rsi,
-                                     DecResult *d_res, hipStream_t st, uint8_t *base, uint32_t start_block, uint64_t rsi_start,
-                                     uint32_t tail_slot, uint64_t *d_seg_bits, const uint32_t *skip_if = nullptr);
+void launch_index_regions(const IdxWalk &w, const RegionPlan &p, uint8_t *ws, const uint32_t *skip_if = nullptr);
 
 // Index pass over many independent streams stored in one buffer (e.g. the chunks of an HDF5
 // dataset): stream s occupies bytes [chunk_off[s], chunk_off[s+1]) (chunk_off 4-byte aligned values,

@@ -538,12 +538,9 @@ RegionPlan region_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint
     return p;
 }
 
-const uint32_t *launch_index_regions(const Cfg &c, const RegionPlan &p, const uint32_t *words, uint64_t nwords, uint64_t end_bit,
-                                     uint64_t start_bit, uint64_t *d_rsi_off, uint64_t max_rsi, DecResult *d_res, hipStream_t st,
-                                     uint8_t *base, uint32_t start_block, uint64_t rsi_start, uint32_t tail_slot,
-                                     uint64_t *d_seg_bits, const uint32_t *skip_if)
+void launch_index_regions(const IdxWalk &w, const RegionPlan &p, uint8_t *base, const uint32_t *skip_if)
 {
-    const TrStream s{words, nwords, end_bit};
+    const TrStream s{w.words, w.nwords, w.end_bit};
     RgTables t{};
     t.flags = reinterpret_cast<uint32_t *>(base + p.o_flags);
     t.found = reinterpret_cast<RgEntry *>(base + p.o_found);
@@ -554,39 +551,39 @@ const uint32_t *launch_index_regions(const Cfg &c, const RegionPlan &p, const ui
     }
     t.base = reinterpret_cast<uint64_t *>(base + p.o_base);
     t.list = reinterpret_cast<uint64_t *>(base + p.o_list);
-    t.slist = (d_seg_bits && p.o_slist != p.bytes) ? reinterpret_cast<uint64_t *>(base + p.o_slist) : nullptr;
+    t.slist = (w.d_seg_bits && p.o_slist != p.bytes) ? reinterpret_cast<uint64_t *>(base + p.o_slist) : nullptr;
     t.K = p.K;
     t.nreg = p.nreg;
     t.budget = p.budget;
     t.period = rg_ring_period(p.avg_cds);
     t.region_bits = p.region_bits;
-    t.lo = start_bit;
+    t.lo = w.start_bit;
     t.max_walk = 16u * p.region_bits;
     t.skip_if = skip_if;
-    (void)hipMemsetAsync(t.flags, 0, 64, st);
+    (void)hipMemsetAsync(t.flags, 0, 64, w.st);
     const uint32_t wg = (p.nreg + 63u) / 64u;
     const uint32_t gwg = wg < 2560u ? wg : 2560u;        // (the guesses come from a queue: as many wavefronts as the chip holds)
     const bool small_ring = p.avg_cds <= (uint32_t)tune("AEC_IDX_REGION_RING32", 32);
-    hipLaunchKernelGGL(k_rg_guess, dim3(gwg), dim3(64), rg_lds_bytes(64u), st, c, s, t);
-    hipLaunchKernelGGL(k_rg_link, dim3((p.nreg + 255u) / 256u), dim3(256), 0, st, t, start_bit, start_block);
-    hipLaunchKernelGGL(k_rg_judge, dim3(1), dim3(1), 0, st, t);
-    if (small_ring) hipLaunchKernelGGL(k_rg_walk<32u>, dim3(wg), dim3(64), rg_lds_bytes(32u), st, c, s, t);
-    else hipLaunchKernelGGL(k_rg_walk<64u>, dim3(wg), dim3(64), rg_lds_bytes(64u), st, c, s, t);
+    hipLaunchKernelGGL(k_rg_guess, dim3(gwg), dim3(64), rg_lds_bytes(64u), w.st, w.c, s, t);
+    hipLaunchKernelGGL(k_rg_link, dim3((p.nreg + 255u) / 256u), dim3(256), 0, w.st, t, w.start_bit, w.start_block);
+    hipLaunchKernelGGL(k_rg_judge, dim3(1), dim3(1), 0, w.st, t);
+    if (small_ring) hipLaunchKernelGGL(k_rg_walk<32u>, dim3(wg), dim3(64), rg_lds_bytes(32u), w.st, w.c, s, t);
+    else hipLaunchKernelGGL(k_rg_walk<64u>, dim3(wg), dim3(64), rg_lds_bytes(64u), w.st, w.c, s, t);
     uint32_t cur = 0;
     for (uint32_t k = 0; k < p.passes; k++) {
-        if (small_ring) hipLaunchKernelGGL(k_rg_mend<32u>, dim3(wg), dim3(64), rg_lds_bytes(32u), st, c, s, t, cur);
-        else hipLaunchKernelGGL(k_rg_mend<64u>, dim3(wg), dim3(64), rg_lds_bytes(64u), st, c, s, t, cur);
+        if (small_ring) hipLaunchKernelGGL(k_rg_mend<32u>, dim3(wg), dim3(64), rg_lds_bytes(32u), w.st, w.c, s, t, cur);
+        else hipLaunchKernelGGL(k_rg_mend<64u>, dim3(wg), dim3(64), rg_lds_bytes(64u), w.st, w.c, s, t, cur);
         cur ^= 1u;
     }
-    hipLaunchKernelGGL(k_rg_prep, dim3(1), dim3(1), 0, st, t);
-    hipLaunchKernelGGL(k_rg_check, dim3((p.nreg + 255u) / 256u), dim3(256), 0, st, t, cur);
-    hipLaunchKernelGGL(k_rg_sums, dim3(wg), dim3(64), 0, st, t, cur);
-    hipLaunchKernelGGL(k_rg_scan, dim3(1), dim3(1024), 0, st, t, cur);
-    hipLaunchKernelGGL(k_rg_fill, dim3(wg), dim3(64), rg_lds_bytes(64u), st, c, s, t, cur, d_rsi_off, max_rsi, d_res, tail_slot, rsi_start,
-                       start_block, d_seg_bits);
+    hipLaunchKernelGGL(k_rg_prep, dim3(1), dim3(1), 0, w.st, t);
+    hipLaunchKernelGGL(k_rg_check, dim3((p.nreg + 255u) / 256u), dim3(256), 0, w.st, t, cur);
+    hipLaunchKernelGGL(k_rg_sums, dim3(wg), dim3(64), 0, w.st, t, cur);
+    hipLaunchKernelGGL(k_rg_scan, dim3(1), dim3(1024), 0, w.st, t, cur);
+    hipLaunchKernelGGL(k_rg_fill, dim3(wg), dim3(64), rg_lds_bytes(64u), w.st, w.c, s, t, cur, w.d_rsi_off, w.max_rsi, w.d_res,
+                       w.tail_slot, w.rsi_start, w.start_block, w.d_seg_bits);
 #ifdef AEC_TUNING
     if (tune_set("AEC_IDX_STATS")) {                       // (diagnostics: synchronises)
-        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(w.st);
         uint32_t fl[8] = {0};
         (void)hipMemcpy(fl, t.flags, 32, hipMemcpyDeviceToHost);
         std::vector<RgEntry> fo(p.nreg), en(p.nreg);
@@ -606,7 +603,6 @@ const uint32_t *launch_index_regions(const Cfg &c, const RegionPlan &p, const ui
                 (unsigned long long)p.region_bits, p.budget, found, fl[4], mism, fl[5], fl[0], fl[1], fl[2], fl[3]);
     }
 #endif
-    return t.flags;
 }
 
 }  // namespace aec

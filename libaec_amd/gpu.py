@@ -80,6 +80,9 @@ def _lib():
         lib.aec_gpu_index_segments_async.argtypes = [vp, pp, vp, sz, u64, C.c_uint, u64, vp, vp, u64, vp, vp]
         lib.aec_gpu_index_scheme.restype = C.c_int
         lib.aec_gpu_index_scheme.argtypes = [pp, sz, u64, C.c_uint]
+        lib.aec_gpu_index_plan.restype = C.c_int
+        lib.aec_gpu_index_plan.argtypes = [pp, sz, u64, C.c_uint, C.c_int, C.c_int, sz, C.POINTER(C.c_int),
+                                           C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         lib.aec_gpu_decode_bare_async.restype = C.c_int
         lib.aec_gpu_decode_bare_async.argtypes = [vp, pp, vp, sz, vp, vp, u64, u64, vp, vp, vp, vp]
         _bound = True
@@ -107,6 +110,20 @@ def index_scheme(bits_per_sample, block_size, rsi, flags, in_bytes, rsi_bits=0, 
     """aec_gpu_index_scheme: which scheme the index pass of such a stream takes (index into INDEX_SCHEMES)."""
     p = Params(bits_per_sample, block_size, rsi, flags)
     return _lib().aec_gpu_index_scheme(C.byref(p), in_bytes, rsi_bits, start_block)
+
+
+def index_plan(bits_per_sample, block_size, rsi, flags, in_bytes, rsi_bits=0, start_block=0, want_segments=False,
+               piece=False, ws_bytes=0):
+    """aec_gpu_index_plan: the chain of schemes the index pass of such a stream enqueues (indices into INDEX_SCHEMES), the
+    workspace the pass asks for, what it asks for without the every-bit scheme's tables, what the chain occupies."""
+    p = Params(bits_per_sample, block_size, rsi, flags)
+    ids = (C.c_int * 6)()
+    asked, large, used = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    n = _lib().aec_gpu_index_plan(C.byref(p), in_bytes, rsi_bits, start_block, int(want_segments), int(piece), ws_bytes,
+                                  ids, C.byref(asked), C.byref(large), C.byref(used))
+    if n < 0:
+        raise ValueError("invalid stream parameters")
+    return list(ids[:n]), asked.value, large.value, used.value
 
 
 class Codec:

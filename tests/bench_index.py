@@ -67,11 +67,14 @@ def main():
             print(f"{args.config} {mib} MiB: index + segment starts {e[0].elapsed_time(e[1]):.3f} ms, decode "
                   f"{e[1].elapsed_time(e[2]):.3f} ms", flush=True)
         res = d_res.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[0]
+        # (the hint aec_gpu_index_async derives for the pass above: input bits / max_rsi, which is nr + 1 there)
+        chain = gpu.index_plan(bps, bs, rsi, flags, cbytes, cbytes * 8 // (nr + 1))[0]
         ok = bool(torch.equal(d_idx[:nr], d_off[:nr])) and int(res["n_rsi"]) == nr and int(res["end_bit"]) == bits
         print(f"{args.config} {mib} MiB: index {dt * 1e3:.3f} ms = {n / dt / 1e9:.3f} GB/s decoded-equivalent "
               f"({cbytes / dt / 1e9:.3f} GB/s of stream), n_rsi {int(res['n_rsi'])}/{nr}, "
               f"status {int(res['status'])}, offsets {'OK' if ok else 'MISMATCH'}; the context holds "
-              f"{held(codec) / 2 ** 20:.0f} MiB (index tables and workspaces)", flush=True)
+              f"{held(codec) / 2 ** 20:.0f} MiB (index tables and workspaces of the chain "
+              f"{' -> '.join(gpu.INDEX_SCHEMES[i] for i in chain)})", flush=True)
         assert ok
 
 
