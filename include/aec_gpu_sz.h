@@ -1,0 +1,102 @@
+/*
+ * aec_gpu_sz.h -- SZIP chunks that stay on the device.
+ *
+ * szlib.h (SZ_BufftoBuffCompress / SZ_BufftoBuffDecompress) takes host buffers and marshals them on the host; the
+ * coder underneath (aec_gpu.h) is device-resident.  These entry points are the layer between the two for a caller
+ * whose chunks live in HBM (an HDF5 VOL / filter): what the reference's shim does around its one coder call
+ * (reference src/sz_compat.c:39-108, 134-166, 208-261) as kernels --
+ *   byte planes     32- and 64-bit pixels are coded as 4 / 8 planes of bytes, plane after plane;
+ *   line padding    every scan line becomes one RSI: a line that is not a whole number of blocks, and a partial
+ *                   last line, are padded with the last pixel (SZ_NN_OPTION_MASK) or with zero;
+ *   un-padding      the reverse after decoding.
+ * All pointers marked d_ are HIP device pointers; every call only ENQUEUES work on `stream` (a hipStream_t passed as
+ * void*), allocates nothing and reads nothing back.  Exported by libaec.so.0.  Only whole pixels are coded: a chunk's
+ * trailing fraction of a pixel is not part of the stream and comes back as zero bytes.
+ */
+#ifndef AEC_GPU_SZ_H
+#define AEC_GPU_SZ_H 1
+
+#include "aec_gpu.h"
+#include "szlib.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* What one chunk of chunk_bytes under an SZ_com_t looks like to the coder. */
+typedef struct aec_gpu_sz_layout_s {
+    aec_gpu_params coder;     /* bits per sample 8 with byte planes; rsi = ceil(pixels_per_scanline / pixels_per_block);
+                                 flags from the option mask (MSB, NN -> AEC_DATA_MSB, AEC_DATA_PREPROCESS) plus
+                                 AEC_NOT_ENFORCE, which the encoder needs and the decoder ignores */
+    unsigned int word;        /* 0, or 4 / 8: bytes per pixel when byte planes are used */
+    unsigned int pixel;       /* container bytes of a coded sample: 1 / 2 / 4 */
+    unsigned int fill_repeat; /* 1: padding repeats the last pixel; 0: zero */
+    unsigned int passthrough; /* 1: no planes, no padding, whole lines, whole pixels -- the chunk as it lies is the
+                                 coder's input and the coder's output is the chunk */
+    uint64_t line;            /* bytes of a scan line (with planes: of the concatenated planes) */
+    uint64_t padded_line;     /* bytes of the RSI it becomes */
+    uint64_t lines;           /* scan lines = RSIs per chunk (the last line may be partial) */
+    uint64_t coder_bytes;     /* lines * padded_line: the coder's input / output per chunk */
+    uint64_t coded_bytes;     /* the chunk's whole pixels */
+} aec_gpu_sz_layout_t;
+
+/* Host arithmetic only.  AEC_CONF_ERROR for what SZ_BufftoBuffCompress or aec_gpu_check_params reject (pixels per
+ * block 0, odd or above 64; pixels per scan line 0 or more than 4096 blocks; bits per pixel 0, 33..63, above 64) and
+ * for a chunk that holds no whole pixel. */
+AEC_GPU_API int aec_gpu_sz_layout(const SZ_com_t *sz, size_t chunk_bytes, aec_gpu_sz_layout_t *layout);
+
+/*
+ * n_chunks equal chunks lying back to back at d_src (any alignment) -> their coder inputs back to back at d_coder_in
+ * (16-byte aligned, n_chunks * coder_bytes bytes), and the inverse: exactly chunk_bytes per chunk are written at
+ * d_dst + i * chunk_bytes (any alignment) and nothing outside them.  Source and destination must not overlap.
+ * Chunks and lines that are 16-byte aligned move 16 bytes per lane; byte planes are split and merged in registers
+ * when every plane and line is a multiple of 4 bytes and the chunks are 16-byte aligned; everything else (unaligned
+ * chunk bases, line tails, padding, a partial last line, planes of odd length) goes byte by byte.
+ */
+AEC_GPU_API int aec_gpu_sz_marshal_async(const SZ_com_t *sz, const void *d_src, size_t chunk_bytes, uint64_t n_chunks,
+                                         void *d_coder_in, void *stream);
+AEC_GPU_API int aec_gpu_sz_unmarshal_async(const SZ_com_t *sz, const void *d_coder_out, size_t chunk_bytes,
+                                           uint64_t n_chunks, void *d_dst, void *stream);
+
+/*
+ * 1 when the one-call forms below take such a batch: the layout is valid and aec_gpu_uniform_batch_ok holds for
+ * (coder, coder_bytes, n_chunks).  A stride coder_bytes that is not a multiple of 16 is SERVED: the encoder's fast
+ * loads need 16-byte aligned RSIs and it takes its byte-wise loader otherwise, the decoder stores whole blocks from a
+ * 16-byte aligned base whatever the RSI size.  When 0 (a chunk of more than 2048 segments of 64 blocks, ...):
+ *     aec_gpu_sz_layout(sz, chunk_bytes, &L);
+ *     aec_gpu_sz_marshal_async(sz, d_src, chunk_bytes, n, d_work, stream);         (skip when L.passthrough)
+ *     offsets[i] = i * L.coder_bytes  (host array; chunk by chunk where coder_bytes is not a multiple of 16)
+ *     aec_gpu_encode_batch_async(ctx, &L.coder, d_work, offsets, n, d_out, slot_bytes, d_results, stream);
+ */
+AEC_GPU_API int aec_gpu_sz_batch_ok(const SZ_com_t *sz, size_t chunk_bytes, uint64_t n_chunks);
+
+/*
+ * SZ_BufftoBuffCompress of n_chunks equal chunks at d_src in one enqueue: marshal into d_work, then
+ * aec_gpu_encode_uniform_batch_async.  d_work: n_chunks * coder_bytes bytes, 16-byte aligned, caller-provided; unused
+ * (may be NULL) when the layout says passthrough.  d_out, out_cap, d_chunks, d_result: exactly as that call defines
+ * them; stream i is byte for byte what SZ_BufftoBuffCompress returns for chunk i.  AEC_CONF_ERROR when
+ * aec_gpu_sz_batch_ok says 0.
+ */
+AEC_GPU_API int aec_gpu_sz_compress_batch_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, const void *d_src,
+                                                size_t chunk_bytes, uint64_t n_chunks, void *d_work, void *d_out,
+                                                size_t out_cap, aec_gpu_batch_chunk *d_chunks,
+                                                aec_gpu_enc_result *d_result, void *stream);
+
+/*
+ * SZ_BufftoBuffDecompress of n_chunks streams in one enqueue: aec_gpu_decode_batch_async (d_in, in_bytes,
+ * d_chunk_offsets, d_rsi_bit_offsets -- n_chunks * lines entries --, d_results, d_result as there, rsi_per_chunk =
+ * lines), then un-marshal to d_dst + i * chunk_bytes.  The decode goes to d_work (n_chunks * coder_bytes bytes,
+ * 16-byte aligned), or straight to d_dst when the layout says passthrough and d_dst is 16-byte aligned (d_work may
+ * then be NULL).  Per-chunk status is in d_results; the bytes of a chunk whose record is not clean (status != 0 or
+ * fewer than `lines` RSIs) are unspecified, every other chunk is exact.
+ */
+AEC_GPU_API int aec_gpu_sz_decompress_batch_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, const void *d_in,
+                                                  size_t in_bytes, const uint64_t *d_chunk_offsets, uint64_t n_chunks,
+                                                  size_t chunk_bytes, uint64_t *d_rsi_bit_offsets, void *d_work,
+                                                  void *d_dst, aec_gpu_dec_result *d_results,
+                                                  aec_gpu_dec_result *d_result, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AEC_GPU_SZ_H */

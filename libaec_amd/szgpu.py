@@ -1,0 +1,194 @@
+"""SZIP chunks that stay on the device (include/aec_gpu_sz.h) for torch tensors living in HBM.
+
+torch is used for device memory and streams only; byte planes, scan-line padding and the coder are kernels launched by
+libaec.so.0 through the C entry points declared in aec_gpu_sz.h.  Same parameters as szip.py (the host-buffer SZIP calls).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import gpu
+from .szip import SZ_com_t
+
+AEC_CONF_ERROR = -1
+
+
+class Layout(C.Structure):
+    """aec_gpu_sz_layout_t"""
+    _fields_ = [("coder", gpu.Params), ("word", C.c_uint), ("pixel", C.c_uint), ("fill_repeat", C.c_uint),
+                ("passthrough", C.c_uint), ("line", C.c_uint64), ("padded_line", C.c_uint64), ("lines", C.c_uint64),
+                ("coder_bytes", C.c_uint64), ("coded_bytes", C.c_uint64)]
+
+
+BATCH_CHUNK_DTYPE = np.dtype([("base_bits", "<u8"), ("bits", "<u8")])
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    lib = gpu._lib()
+    if not _bound:
+        vp, sz, u64 = C.c_void_p, C.c_size_t, C.c_uint64
+        ps = C.POINTER(SZ_com_t)
+        lib.aec_gpu_sz_layout.restype = C.c_int
+        lib.aec_gpu_sz_layout.argtypes = [ps, sz, C.POINTER(Layout)]
+        lib.aec_gpu_sz_batch_ok.restype = C.c_int
+        lib.aec_gpu_sz_batch_ok.argtypes = [ps, sz, u64]
+        lib.aec_gpu_sz_marshal_async.restype = C.c_int
+        lib.aec_gpu_sz_marshal_async.argtypes = [ps, vp, sz, u64, vp, vp]
+        lib.aec_gpu_sz_unmarshal_async.restype = C.c_int
+        lib.aec_gpu_sz_unmarshal_async.argtypes = [ps, vp, sz, u64, vp, vp]
+        lib.aec_gpu_sz_compress_batch_async.restype = C.c_int
+        lib.aec_gpu_sz_compress_batch_async.argtypes = [vp, ps, vp, sz, u64, vp, vp, sz, vp, vp, vp]
+        lib.aec_gpu_sz_decompress_batch_async.restype = C.c_int
+        lib.aec_gpu_sz_decompress_batch_async.argtypes = [vp, ps, vp, sz, vp, u64, sz, vp, vp, vp, vp, vp, vp]
+        lib.aec_gpu_encode_batch_async.restype = C.c_int
+        lib.aec_gpu_encode_batch_async.argtypes = [vp, C.POINTER(gpu.Params), vp, C.POINTER(u64), u64, vp, sz, vp, vp]
+        _bound = True
+    return lib
+
+
+def layout(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline, chunk_bytes):
+    """aec_gpu_sz_layout (host arithmetic, no device needed): a Layout, or None where the call says AEC_CONF_ERROR"""
+    p = SZ_com_t(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline)
+    out = Layout()
+    rc = _lib().aec_gpu_sz_layout(C.byref(p), chunk_bytes, C.byref(out))
+    if rc == AEC_CONF_ERROR:
+        return None
+    if rc != 0:
+        raise RuntimeError(f"aec_gpu_sz_layout failed ({rc})")
+    return out
+
+
+def batch_ok(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline, chunk_bytes, n_chunks):
+    """aec_gpu_sz_batch_ok: 1 when compress_batch / decompress_batch take such a batch in one call"""
+    p = SZ_com_t(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline)
+    return int(_lib().aec_gpu_sz_batch_ok(C.byref(p), chunk_bytes, n_chunks))
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class SzCodec:
+    """One SZ_com_t and one aec_gpu context (workspace) on the current torch device."""
+
+    def __init__(self, options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("libaec_amd.szgpu needs a HIP device (no CPU implementation)")
+        self.torch = torch
+        self.lib = _lib()
+        self.sz = SZ_com_t(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline)
+        if layout(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline, 64) is None:
+            raise ValueError("invalid SZIP parameters (aec_gpu_sz_layout -> AEC_CONF_ERROR)")
+        self.ctx = C.c_void_p()
+        torch.zeros(1, device="cuda")          # make sure the HIP context of this device is current
+        rc = self.lib.aec_gpu_create(C.byref(self.ctx))
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_create failed ({rc})")
+
+    def close(self):
+        if self.ctx:
+            self.lib.aec_gpu_destroy(self.ctx)
+            self.ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self, stream):
+        return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
+
+    def layout(self, chunk_bytes):
+        s = self.sz
+        return layout(s.options_mask, s.bits_per_pixel, s.pixels_per_block, s.pixels_per_scanline, chunk_bytes)
+
+    def batch_ok(self, chunk_bytes, n_chunks):
+        return int(self.lib.aec_gpu_sz_batch_ok(C.byref(self.sz), chunk_bytes, n_chunks))
+
+    def encode_bound(self, chunk_bytes):
+        """bytes (a multiple of 16) that hold the stream of any chunk of this size"""
+        L = self.layout(chunk_bytes)
+        return int(self.lib.aec_gpu_encode_bound(C.byref(L.coder), L.coder_bytes))
+
+    # ---- enqueue -------------------------------------------------------------------------------
+    def marshal_async(self, d_src, chunk_bytes, n_chunks, d_coder_in, stream=None):
+        """d_src: uint8 CUDA tensor of n equal chunks back to back; d_coder_in: 16-byte aligned, n * coder_bytes"""
+        return self.lib.aec_gpu_sz_marshal_async(C.byref(self.sz), _ptr(d_src), chunk_bytes, n_chunks, _ptr(d_coder_in),
+                                                 self._stream(stream))
+
+    def unmarshal_async(self, d_coder_out, chunk_bytes, n_chunks, d_dst, stream=None):
+        return self.lib.aec_gpu_sz_unmarshal_async(C.byref(self.sz), _ptr(d_coder_out), chunk_bytes, n_chunks, _ptr(d_dst),
+                                                   self._stream(stream))
+
+    def compress_batch_async(self, d_src, chunk_bytes, n_chunks, d_work, d_out, d_chunks, d_result, stream=None):
+        """d_work: n * coder_bytes bytes, 16-byte aligned (None when the layout says passthrough); d_chunks: n * 16 bytes
+        (BATCH_CHUNK_DTYPE); d_result: 24 bytes (gpu.ENC_RESULT_DTYPE).  Returns the call's return code."""
+        return self.lib.aec_gpu_sz_compress_batch_async(self.ctx, C.byref(self.sz), _ptr(d_src), chunk_bytes, n_chunks,
+                                                        _ptr(d_work), _ptr(d_out), d_out.numel(), _ptr(d_chunks),
+                                                        _ptr(d_result), self._stream(stream))
+
+    def decompress_batch_async(self, d_in, in_bytes, d_chunk_offsets, n_chunks, chunk_bytes, d_rsi_offsets, d_work, d_dst,
+                               d_results, d_result, stream=None):
+        """d_chunk_offsets: int64 tensor, n + 1 byte offsets (multiples of 16); d_rsi_offsets: int64, n * lines;
+        d_results: n * 40 bytes, d_result: 40 bytes (gpu.DEC_RESULT_DTYPE).  Returns the call's return code."""
+        return self.lib.aec_gpu_sz_decompress_batch_async(self.ctx, C.byref(self.sz), _ptr(d_in), in_bytes,
+                                                          _ptr(d_chunk_offsets), n_chunks, chunk_bytes, _ptr(d_rsi_offsets),
+                                                          _ptr(d_work), _ptr(d_dst), _ptr(d_results), _ptr(d_result),
+                                                          self._stream(stream))
+
+    def encode_chunks_async(self, d_coder_in, coder_bytes, n_chunks, d_out, slot_bytes, d_results, stream=None):
+        """the path for batches batch_ok refuses: aec_gpu_encode_batch_async, chunk by chunk, over marshalled chunks
+        (d_results: n * 24 bytes)"""
+        L = self.layout(64)
+        for i in range(n_chunks):
+            offs = (C.c_uint64 * 2)(0, coder_bytes)
+            rc = self.lib.aec_gpu_encode_batch_async(
+                self.ctx, C.byref(L.coder), C.c_void_p(d_coder_in.data_ptr() + i * coder_bytes), offs, 1,
+                C.c_void_p(d_out.data_ptr() + i * slot_bytes), slot_bytes, C.c_void_p(d_results.data_ptr() + i * 24),
+                self._stream(stream))
+            if rc != 0:
+                return rc
+        return 0
+
+    # ---- convenience (synchronising) -------------------------------------------------------------
+    def compress_batch(self, d_src, chunk_bytes, n_chunks):
+        """n equal chunks back to back in d_src -> list of the n streams (bytes), each what SZ_BufftoBuffCompress gives"""
+        torch = self.torch
+        L = self.layout(chunk_bytes)
+        if L is None or not self.batch_ok(chunk_bytes, n_chunks):
+            raise ValueError("not a batch for one call (aec_gpu_sz_batch_ok)")
+        cap = self.encode_bound(chunk_bytes) * n_chunks
+        d_out = torch.empty(cap, dtype=torch.uint8, device=d_src.device)
+        d_work = None if L.passthrough else torch.empty(n_chunks * L.coder_bytes + 16, dtype=torch.uint8, device=d_src.device)
+        d_rec = torch.zeros(n_chunks * 2, dtype=torch.int64, device=d_src.device)
+        d_res = torch.zeros(gpu.ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_src.device)
+        rc = self.compress_batch_async(d_src, chunk_bytes, n_chunks, d_work, d_out, d_rec, d_res)
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_sz_compress_batch_async failed ({rc})")
+        rec = d_rec.cpu().numpy().reshape(n_chunks, 2)
+        if d_res.cpu().numpy().view(gpu.ENC_RESULT_DTYPE)[0]["overflow"]:
+            raise RuntimeError("encode overflow")
+        out = d_out.cpu().numpy()
+        return [out[int(b) // 8:int(b) // 8 + (int(n) + 7) // 8].tobytes() for b, n in rec]
+
+    def decompress_batch(self, d_in, d_chunk_offsets, n_chunks, chunk_bytes):
+        """streams at d_in[d_chunk_offsets[i] : d_chunk_offsets[i + 1]] -> (d_dst of n * chunk_bytes, per-chunk records,
+        overall record)"""
+        torch = self.torch
+        L = self.layout(chunk_bytes)
+        d_work = torch.empty(n_chunks * L.coder_bytes + 16, dtype=torch.uint8, device=d_in.device)
+        d_dst = torch.empty(n_chunks * chunk_bytes, dtype=torch.uint8, device=d_in.device)
+        d_off = torch.zeros(n_chunks * L.lines, dtype=torch.int64, device=d_in.device)
+        d_results = torch.zeros(n_chunks * gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
+        d_result = torch.zeros(gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
+        rc = self.decompress_batch_async(d_in, d_in.numel(), d_chunk_offsets, n_chunks, chunk_bytes, d_off, d_work, d_dst,
+                                         d_results, d_result)
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_sz_decompress_batch_async failed ({rc})")
+        return (d_dst, d_results.cpu().numpy().view(gpu.DEC_RESULT_DTYPE),
+                d_result.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[0])
