@@ -18,6 +18,11 @@
 //           is bounded by the room the caller offers (at least kMinBatchOut), so memory is
 //           O(offered output + undecoded input), never O(decoded size of everything staged).
 //
+// The mechanisms every entry point shares are each stated once: a stream's device belongings (Kit: obtain_kit /
+// give_kit), the hand-out of what a batch produced (hand_out), the copy to the caller beside the next batch (SideCopy),
+// many chunks through pinned staging (stage_up / stage_down).  The arithmetic of a decode batch -- its bounds, the
+// verdict over its result records, the advance of the stream's position -- is pure and lives in aec_stream_plan.h.
+//
 // There is no CPU codec in here: without a working HIP device every call fails with AEC_MEM_ERROR.
 #include <hip/hip_runtime.h>
 
@@ -36,6 +41,7 @@
 #include "../../include/libaec.h"
 #include "aec_cfg.h"
 #include "aec_pool.h"
+#include "aec_stream_plan.h"
 #include "aec_tune.h"
 
 using namespace aec;
@@ -56,17 +62,6 @@ int fail_at(int code, int line)
     return code;
 }
 #define AEC_FAIL(code) fail_at((code), __LINE__)
-
-// What the index pass is told about the coded RSIs: a look-ahead of 1.5 means (the window tables are sized from it) --
-// except for RSIs of uncompressed blocks, where the pass is told the mean itself so that it leaves out the schemes that
-// look for reference samples (aec_kernels.h: index_incompressible), and a look-ahead that happens to fall into that
-// band is moved beyond it.
-uint64_t index_hint_of(const Cfg &c, uint64_t mean)
-{
-    if (index_incompressible(c, mean)) return mean;
-    const uint64_t h = mean + mean / 2;
-    return index_incompressible(c, h) ? (uint64_t)c.rsi * (c.id_len + (uint64_t)c.bs * c.bps) + 65 : h;
-}
 
 struct DevBuf {
     void *p = nullptr;
@@ -99,73 +94,52 @@ struct DevBuf {
     }
 };
 
-// batching thresholds
+// batching thresholds (kMinBatchOut and kPipeOut, which bound a decode batch: aec_stream_plan.h)
 constexpr size_t kEncBatchBytes = (size_t)1 << 20;   // staged input that is worth a launch without AEC_FLUSH
 constexpr size_t kEncDirectMin = (size_t)64 << 10;   // whole RSIs offered in one call: coded from the caller's buffer
 constexpr size_t kDecTinyCall = 8;                   // a call that brings at most this many bytes is a trickle ...
 constexpr size_t kDecTrickle = 4096;                 // ... collected on the host up to this many before a launch
 constexpr size_t kDecDirectMin = 4096;               // input of at least this size goes straight to the device
-constexpr size_t kMinBatchOut = (size_t)4 << 20;     // output a decode batch may produce beyond the room offered
 constexpr size_t kBacklogMax = (size_t)64 << 20;     // undecoded input held on the device before more is accepted
 constexpr size_t kBounce = (size_t)256 << 10;        // pinned bounce buffer: first output bytes ride with the records
-constexpr size_t kPipeOut = (size_t)64 << 20;        // decode: output per batch where batches are pipelined (below)
-constexpr size_t kAsyncMin = (size_t)1 << 20;        // ... and the smallest copy-out that is worth the side stream
+constexpr size_t kAsyncMin = (size_t)1 << 20;        // pipelined decode batches: the smallest copy-out that is worth the side stream
 constexpr size_t kRangeRsis = 2048;                  // aec_decode_range: RSIs per batch at least (below)
 
-}  // namespace
+// The copy of a decode batch's output to the caller's buffer on a side stream, beside the kernels of the next batch,
+// which write the other of the kit's two output buffers.  The stream and the events are created on demand and stay
+// with the kit; which buffer is next and which copies are in flight is the business of one call.
+struct SideCopy {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};     // ev[i]: the last copy out of output buffer i has finished
+    unsigned sel = 0;                          // which output buffer the next batch writes
+    bool pending[2] = {false, false};          // a copy out of buffer i is in flight: waited for before the call returns
 
-struct internal_state {
-    bool encoder;
-    aec_gpu_params prm;
-    Cfg cfg;                       // derived values (sizes are per batch, not used from here)
-    int device;
-    aec_gpu_ctx *ctx;
-    hipStream_t stream;
-    DevBuf d_in, d_out, d_off, d_res, d_seg;   // (d_seg: segment starts beside the RSI starts, long RSIs only)
-    DevBuf d_out2;                 // decoder: second output buffer (batches alternate while copies are in flight)
-    hipStream_t copy_stream;       // decoder: the copy-out of a batch runs here, beside the kernels of the next one
-    hipEvent_t ev_copied[2];       // ... and this says when the copy out of buffer i has finished
-    bool copy_pending;             // a copy to the caller's buffer is in flight: waited for before the call returns
-    unsigned out_sel;              // which output buffer the next batch writes
-    uint8_t *h_res;                // pinned: 256 bytes of records, then kBounce bytes of bounce buffer
-
-    std::vector<uint8_t> stage;    // encoder: input not yet coded; decoder: input not yet on the device
-    size_t stage_pos;              // encoder: first staged byte still to be coded
-    std::vector<uint8_t> outq;     // produced bytes not yet delivered
-    size_t outq_pos;
-
-    // encoder carry (reference state->k, state->bits / *state->cds)
-    uint32_t k;
-    uint32_t part_bits;            // bits used in the open byte, 0..7
-    uint8_t part_byte;
-    bool any_bits;                 // at least one stream bit produced
-    bool finished;                 // final byte queued
-    int flush;                     // last flush argument
-    bool flushed;                  // reference state->flushed
-
-    // decoder: d_in holds stream bytes [base, base + d_len); all *_bit values are absolute stream bits
-    uint64_t base;                 // multiple of 16
-    size_t d_len;
-    uint64_t rsi_start_bit;        // start of the RSI being decoded
-    uint64_t rsi_bits_seen;        // average coded RSI of the previous batch (0 = none yet)
-    uint64_t walk_bit;             // coded-data-set boundary where the index walker resumes
-    uint32_t walk_blocks;          // blocks of that RSI in front of walk_bit
-    uint64_t delivered;            // samples of that RSI already handed out
-    size_t walked_len;             // d_len at the last index pass (anything beyond it is new)
-    uint64_t span_mul;             // widening of the batch's input span (coded data sets beyond the encoder's bound)
-    bool span_wide;                // pipelined batches: the tight span did not hold once, the worst case from now on
-    bool more;                     // the last batch stopped at its RSI bound: decodable input remains
-    bool launched;                 // at least one batch has run
-    int sticky_error;
-
-    // RSI offset tables (include/libaec.h: aec_*_enable_offsets): absolute stream bits, kept only when enabled
-    bool offsets_on;
-    std::vector<uint64_t> offs;
-    uint64_t enc_bits;             // encoder: stream bits produced by the batches so far
-    bool took_input;               // encoder: an aec_encode call has taken input; decoder: aec_decode has run
+    bool event(unsigned i) { return ev[i] || hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess; }
+    // work on `main` is about to write buffer `sel`: the copy that read it two batches ago must have finished first
+    bool claim(hipStream_t main) { return !pending[sel] || hipStreamWaitEvent(main, ev[sel], 0) == hipSuccess; }
+    // n bytes of buffer `sel` to the host.  beside: on the side stream, the next batch's kernels (the other buffer) run
+    // beside it; where the stream or the event is not to be had, and for every other copy, the call blocks
+    bool copy_out(void *dst, const void *d_src, size_t n, bool beside)
+    {
+        if (beside && (stream || hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess) && event(sel)) {
+            if (hipMemcpyAsync(dst, d_src, n, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipEventRecord(ev[sel], stream) != hipSuccess)
+                return false;
+            pending[sel] = true;
+            sel ^= 1u;
+            return true;
+        }
+        if (beside) (void)hipGetLastError();
+        return hipMemcpy(dst, d_src, n, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    // all copies have arrived: the buffers they write are the caller's again (on every way out of a call)
+    bool done()
+    {
+        if (!pending[0] && !pending[1]) return true;
+        pending[0] = pending[1] = false;
+        return hipStreamSynchronize(stream) == hipSuccess;
+    }
 };
-
-namespace {
 
 // Device-side belongings of a stream.  Callers like the HDF5 SZIP filter run one
 // aec_buffer_encode / aec_buffer_decode per chunk, i.e. an init / end cycle per megabyte: creating
@@ -178,13 +152,50 @@ struct Kit {
     int device = -1;
     aec_gpu_ctx *ctx = nullptr;
     hipStream_t stream = nullptr;
-    DevBuf d_in, d_out, d_off, d_res, d_seg, d_out2;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copied[2] = {nullptr, nullptr};
-    uint8_t *h_res = nullptr;
+    DevBuf d_in, d_out, d_off, d_res, d_seg;   // (d_seg: segment starts beside the RSI starts, long RSIs only)
+    DevBuf d_out2;                 // decoder: second output buffer (batches alternate while copies are in flight)
+    SideCopy side;                 // decoder: the copy-out of a batch, beside the kernels of the next one
+    uint8_t *h_res = nullptr;      // pinned: 256 bytes of records, then kBounce bytes of bounce buffer
     uint8_t *h_stage = nullptr;    // pinned staging of the batch entry points (many chunks, one transfer)
     size_t h_stage_cap = 0;
+
+    DevBuf &out_buf() { return side.sel ? d_out2 : d_out; }   // the output buffer the next batch writes
 };
+
+}  // namespace
+
+// A stream: its kit, where its decoder stands (aec_stream_plan.h), and what the host holds for it
+struct internal_state : Kit, StreamPos {
+    bool encoder = false;
+    aec_gpu_params prm{};
+    Cfg cfg{};                     // derived values (sizes are per batch, not used from here)
+
+    std::vector<uint8_t> stage;    // encoder: input not yet coded; decoder: input not yet on the device
+    size_t stage_pos = 0;          // encoder: first staged byte still to be coded
+    std::vector<uint8_t> outq;     // produced bytes not yet delivered
+    size_t outq_pos = 0;
+
+    // encoder carry (reference state->k, state->bits / *state->cds)
+    uint32_t k = 0;
+    uint32_t part_bits = 0;        // bits used in the open byte, 0..7
+    uint8_t part_byte = 0;
+    bool any_bits = false;         // at least one stream bit produced
+    bool finished = false;         // final byte queued
+    int flush = AEC_NO_FLUSH;      // last flush argument
+    bool flushed = false;          // reference state->flushed
+
+    bool launched = false;         // decoder: at least one batch has run
+    int sticky_error = AEC_OK;
+
+    // RSI offset tables (include/libaec.h: aec_*_enable_offsets): absolute stream bits, kept only when enabled
+    bool offsets_on = false;
+    std::vector<uint64_t> offs;
+    uint64_t enc_bits = 0;         // encoder: stream bits produced by the batches so far
+    bool took_input = false;       // encoder: an aec_encode call has taken input; decoder: aec_decode has run
+};
+
+namespace {
+
 // at most kPoolMax parked kits, none holding a buffer above kKeepBytes, all of them together at most kPoolBytes
 constexpr size_t kPoolMax = 8, kKeepBytes = (size_t)256 << 20, kPoolBytes = (size_t)1 << 30;
 constexpr size_t kStageKeep = (size_t)96 << 20, kStagePiece = (size_t)64 << 20, kPoolPinned = (size_t)192 << 20;
@@ -199,8 +210,8 @@ void destroy_kit(Kit &k)
     k.d_res.release();
     k.d_seg.release();
     k.d_out2.release();
-    if (k.copy_stream) (void)hipStreamDestroy(k.copy_stream);
-    for (hipEvent_t &e : k.ev_copied)
+    if (k.side.stream) (void)hipStreamDestroy(k.side.stream);
+    for (hipEvent_t &e : k.side.ev)
         if (e) (void)hipEventDestroy(e);
     if (k.h_res) (void)hipHostFree(k.h_res);
     if (k.h_stage) (void)hipHostFree(k.h_stage);
@@ -222,6 +233,17 @@ bool take_kit(int device, Kit *out)
     return false;
 }
 
+// A kit for the current device: from the pool, else freshly created.  false: no usable HIP device or no memory (the
+// product has no CPU path); what there is of the kit goes back through give_kit all the same.
+bool obtain_kit(Kit &k)
+{
+    if (hipGetDevice(&k.device) != hipSuccess) return false;
+    if (take_kit(k.device, &k)) return true;          // (parked with the index hint and the output buffers' turn reset)
+    return aec_gpu_create(&k.ctx) == RC_OK && hipStreamCreate(&k.stream) == hipSuccess &&
+           hipHostMalloc(reinterpret_cast<void **>(&k.h_res), 256 + kBounce, hipHostMallocDefault) == hipSuccess &&
+           k.d_res.ensure(256);
+}
+
 size_t kit_bytes(const Kit &k)
 {
     return k.d_in.cap + k.d_out.cap + k.d_off.cap + k.d_res.cap + k.d_seg.cap + k.d_out2.cap + aec_gpu_held_bytes(k.ctx);
@@ -231,7 +253,7 @@ void park_kit(Kit &k)
 {
     // an error return may have left copies or kernels of this stream object enqueued: nothing of it may still
     // run when the next owner writes the buffers
-    if (hipStreamSynchronize(k.stream) != hipSuccess || (k.copy_stream && hipStreamSynchronize(k.copy_stream) != hipSuccess)) {
+    if (hipStreamSynchronize(k.stream) != hipSuccess || (k.side.stream && hipStreamSynchronize(k.side.stream) != hipSuccess)) {
         (void)hipGetLastError();
         destroy_kit(k);
         return;
@@ -245,6 +267,8 @@ void park_kit(Kit &k)
     }
     aec_gpu_trim(k.ctx, kKeepBytes);
     aec_gpu_set_index_hint(k.ctx, 0);
+    k.side.sel = 0;
+    k.side.pending[0] = k.side.pending[1] = false;
     {
         std::lock_guard<std::mutex> lock(g_pool_mu);
         if (!g_pool) g_pool = new (std::nothrow) std::vector<Kit>();
@@ -268,25 +292,17 @@ void park_kit(Kit &k)
     destroy_kit(k);
 }
 
+// A kit goes back: parked if it is complete, else destroyed
+void give_kit(Kit &k)
+{
+    if (k.ctx && k.stream && k.h_res && k.d_res.p) park_kit(k);
+    else destroy_kit(k);
+}
+
 void free_state(internal_state *s)
 {
     if (!s) return;
-    Kit k;
-    k.device = s->device;
-    k.ctx = s->ctx;
-    k.stream = s->stream;
-    k.d_in = s->d_in;
-    k.d_out = s->d_out;
-    k.d_off = s->d_off;
-    k.d_res = s->d_res;
-    k.d_seg = s->d_seg;
-    k.d_out2 = s->d_out2;
-    k.copy_stream = s->copy_stream;
-    k.ev_copied[0] = s->ev_copied[0];
-    k.ev_copied[1] = s->ev_copied[1];
-    k.h_res = s->h_res;
-    if (k.ctx && k.stream && k.h_res && k.d_res.p) park_kit(k);
-    else destroy_kit(k);
+    give_kit(*s);
     delete s;
 }
 
@@ -301,57 +317,7 @@ int init_common(struct aec_stream *strm, bool enc)
     s->encoder = enc;
     s->prm = prm;
     s->cfg = c;
-    s->stage_pos = 0;
-    s->outq_pos = 0;
-    s->k = 0;
-    s->part_bits = 0;
-    s->part_byte = 0;
-    s->any_bits = false;
-    s->finished = false;
-    s->flush = AEC_NO_FLUSH;
-    s->flushed = false;
-    s->base = 0;
-    s->d_len = 0;
-    s->rsi_start_bit = 0;
-    s->rsi_bits_seen = 0;
-    s->walk_bit = 0;
-    s->walk_blocks = 0;
-    s->delivered = 0;
-    s->walked_len = 0;
-    s->span_mul = 1;
-    s->span_wide = false;
-    s->more = false;
-    s->launched = false;
-    s->sticky_error = AEC_OK;
-    s->offsets_on = false;
-    s->enc_bits = 0;
-    s->took_input = false;
-    s->ctx = nullptr;
-    s->stream = nullptr;
-    s->copy_stream = nullptr;
-    s->ev_copied[0] = s->ev_copied[1] = nullptr;
-    s->copy_pending = false;
-    s->out_sel = 0;
-    s->h_res = nullptr;
-    s->device = -1;
-    Kit k;
-    if (hipGetDevice(&s->device) == hipSuccess && take_kit(s->device, &k)) {
-        s->ctx = k.ctx;
-        s->stream = k.stream;
-        s->d_in = k.d_in;
-        s->d_out = k.d_out;
-        s->d_off = k.d_off;
-        s->d_res = k.d_res;
-        s->d_seg = k.d_seg;
-        s->d_out2 = k.d_out2;
-        s->copy_stream = k.copy_stream;
-        s->ev_copied[0] = k.ev_copied[0];
-        s->ev_copied[1] = k.ev_copied[1];
-        s->h_res = k.h_res;
-        aec_gpu_set_index_hint(s->ctx, 0);
-    } else if (s->device < 0 || aec_gpu_create(&s->ctx) != RC_OK || hipStreamCreate(&s->stream) != hipSuccess ||
-               hipHostMalloc(reinterpret_cast<void **>(&s->h_res), 256 + kBounce, hipHostMallocDefault) != hipSuccess ||
-               !s->d_res.ensure(256)) {
+    if (!obtain_kit(*s)) {
         free_state(s);
         return AEC_FAIL(AEC_MEM_ERROR);   // no usable HIP device: the product has no CPU path
     }
@@ -380,6 +346,39 @@ inline size_t drain(struct aec_stream *strm, internal_state *s, size_t granule)
     return n;
 }
 
+// Hand out what a batch produced: `count` fresh bytes at d_bytes on the device (in the output buffer whose turn it is),
+// the first `spec` of which are already in the bounce buffer -- they rode with the result record.  As much as fits goes
+// straight into the caller's buffer, in whole granules (next_out / avail_out advance), the remainder is queued; the last
+// `hold` bytes are queued whatever the room.  beside: a large rest of the direct part may go on the side stream.
+int hand_out(internal_state *s, struct aec_stream *strm, const uint8_t *d_bytes, size_t count, size_t hold, size_t spec,
+             size_t granule, bool beside)
+{
+    const uint8_t *bounce = s->h_res + 256;
+    size_t direct = count - hold < strm->avail_out ? count - hold : strm->avail_out;
+    direct -= direct % granule;
+    if (direct) {
+        const size_t from_bounce = direct < spec ? direct : spec, rest = direct - from_bounce;
+        memcpy(strm->next_out, bounce, from_bounce);
+        if (rest && !s->side.copy_out(strm->next_out + from_bounce, d_bytes + from_bounce, rest, beside && rest >= kAsyncMin))
+            return AEC_FAIL(AEC_MEM_ERROR);
+        strm->next_out += direct;
+        strm->avail_out -= direct;
+    }
+    if (count > direct) {
+        const size_t rest = count - direct, at = s->outq.size();
+        s->outq.resize(at + rest);
+        size_t done = 0;
+        if (direct < spec) {
+            done = spec - direct < rest ? spec - direct : rest;
+            memcpy(s->outq.data() + at, bounce + direct, done);
+        }
+        if (rest > done &&
+            hipMemcpy(s->outq.data() + at + done, d_bytes + direct + done, rest - done, hipMemcpyDeviceToHost) != hipSuccess)
+            return AEC_FAIL(AEC_MEM_ERROR);
+    }
+    return AEC_OK;
+}
+
 // Code `nbytes` of input (whole samples) as one GPU batch; append produced whole bytes to the queue
 // and keep the open byte / k as carry.  Nothing is queued when this runs, so finished bytes go
 // straight into the caller's buffer as far as it has room: the first kBounce of them ride with the
@@ -403,11 +402,10 @@ int encode_batch(internal_state *s, const uint8_t *data, size_t nbytes, struct a
                                         s->stream);
     if (rc != RC_OK) return AEC_FAIL(rc);
     const uint8_t *d_bytes = static_cast<const uint8_t *>(s->d_out.p);
-    uint8_t *bounce = s->h_res + 256;
     const size_t spec = cap < kBounce ? cap : kBounce;          // speculative: the size is not known yet
     if (hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(aec_gpu_enc_result), hipMemcpyDeviceToHost, s->stream) !=
             hipSuccess ||
-        hipMemcpyAsync(bounce, d_bytes, spec, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(s->h_res + 256, d_bytes, spec, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
         hipStreamSynchronize(s->stream) != hipSuccess)
         return AEC_FAIL(AEC_MEM_ERROR);
     const aec_gpu_enc_result res = *reinterpret_cast<aec_gpu_enc_result *>(s->h_res);
@@ -423,53 +421,24 @@ int encode_batch(internal_state *s, const uint8_t *data, size_t nbytes, struct a
     s->enc_bits += res.total_bits;
     const uint64_t bits = (uint64_t)s->part_bits + res.total_bits;
     const size_t whole = (size_t)(bits / 8), nb = (size_t)((bits + 7) / 8);
-    // bytes [0, whole) are finished, byte `whole` (if nb > whole) is the new open byte
-    size_t direct = whole < strm->avail_out ? whole : strm->avail_out;
+    // bytes [0, whole) are finished, byte `whole` (if nb > whole) is the new open byte: queued in any case
     uint8_t *out0 = strm->next_out;
-    if (direct) {
-        const size_t from_bounce = direct < spec ? direct : spec;
-        memcpy(strm->next_out, bounce, from_bounce);
-        if (direct > from_bounce &&
-            hipMemcpy(strm->next_out + from_bounce, d_bytes + from_bounce, direct - from_bounce,
-                      hipMemcpyDeviceToHost) != hipSuccess)
-            return AEC_FAIL(AEC_MEM_ERROR);
-    }
-    const size_t rest = nb - direct;                     // queued: unfinished bytes + the open byte
     const size_t at = s->outq.size();
-    s->outq.resize(at + rest);
-    if (rest) {
-        size_t done = 0;
-        if (direct < spec) {
-            done = spec - direct < rest ? spec - direct : rest;
-            memcpy(s->outq.data() + at, bounce + direct, done);
-        }
-        if (rest > done &&
-            hipMemcpy(s->outq.data() + at + done, d_bytes + direct + done, rest - done, hipMemcpyDeviceToHost) !=
-                hipSuccess)
-            return AEC_FAIL(AEC_MEM_ERROR);
-    }
+    const int hrc = hand_out(s, strm, d_bytes, nb, nb - whole, spec, 1, false);
+    if (hrc != AEC_OK) return hrc;
+    const size_t direct = (size_t)(strm->next_out - out0);
     // the byte the batch started in carries the bits of the previous batch
     if (direct) out0[0] |= s->part_byte;
     else if (nb) s->outq[at] |= s->part_byte;
     s->part_bits = (uint32_t)(bits % 8);
     s->part_byte = s->part_bits ? s->outq[at + whole - direct] : 0;
     s->outq.resize(at + whole - direct);
-    if (direct) {
-        strm->next_out += direct;
-        strm->avail_out -= direct;
-    }
     s->k = res.k_out;
     if (res.total_bits) s->any_bits = true;
     return AEC_OK;
 }
 
 // ---- decoder ------------------------------------------------------------------------------------
-
-// bytes one RSI can occupy at most in the stream (every block uncompressed)
-inline uint64_t worst_rsi_bytes(const Cfg &c)
-{
-    return ((uint64_t)c.rsi * (c.id_len + (uint64_t)c.bs * c.bps) + c.bps + 7) / 8 + 1;
-}
 
 // Append `n` bytes at `src` (host) to the device-resident stream.
 int upload(internal_state *s, const uint8_t *src, size_t n)
@@ -483,7 +452,9 @@ int upload(internal_state *s, const uint8_t *src, size_t n)
     return AEC_OK;
 }
 
-// One batch: index from where the walker stopped, decode what it found, hand out / queue the samples.
+// One batch: index from where the walker stopped, decode what it found, hand out / queue the samples.  What the batch
+// takes and brings (plan_batch), what its records mean (judge_batch) and where the stream stands after it
+// (advance_stream) is aec_stream_plan.h's; here are the buffers, the launches, the one synchronisation and the copies.
 int decode_run(internal_state *s, struct aec_stream *strm)
 {
     const Cfg &c = s->cfg;
@@ -497,88 +468,44 @@ int decode_run(internal_state *s, struct aec_stream *strm)
     s->launched = true;
     s->more = false;
     if (s->d_len == 0) return AEC_OK;
-    const size_t blk_bytes = (size_t)c.bs * c.bytes;
-    const size_t rsi_bytes = (size_t)c.rsi * blk_bytes;
+    const size_t rsi_bytes = (size_t)c.rsi * c.bs * c.bytes;
     const uint64_t base_bits = s->base * 8;
-    const uint64_t walk_rel = s->walk_bit - base_bits, rsi_rel = s->rsi_start_bit - base_bits;
-    const size_t skip = (size_t)s->delivered * c.bytes;   // bytes of the current RSI already handed out
     const size_t want_out = strm->avail_out;              // (what the caller asks of THIS call)
-
-    // Look-ahead of the speculative index = a small multiple of the average coded RSI: measured on
-    // the previous batch of this stream, else estimated from the room the caller offers for output
-    // (whole-buffer callers offer the decoded size).
-    uint64_t hint = s->rsi_bits_seen;
-    if (!hint && strm->avail_out >= rsi_bytes) {
-        const uint64_t expect = (strm->avail_out + skip + rsi_bytes - 1) / rsi_bytes;
-        hint = ((uint64_t)s->d_len * 8 - rsi_rel) / expect;
-    }
-    // Large outputs of streams whose index pass is cheap per call (the window tables): batches of kPipeOut, the copy
-    // of one batch to the caller's buffer on a side stream beside the index pass and the decode of the next one (one
-    // batch for everything was upload, index, decode, copy one behind the other: 21 GB/s for 256 MiB of config 2
-    // against 42 for the encoder).  The trunk index pays too much per call for that (spans, burn-in): one batch.
-    const bool pipe = strm->avail_out >= kPipeOut + kPipeOut / 2 &&
-                      aec_gpu_index_is_windowed(&s->prm, s->d_len - (size_t)(rsi_rel / 8), hint + hint / 2) != 0;
-    // bound of the batch: the room offered (at least kMinBatchOut), and no more than the input can hold
-    const size_t room = (pipe ? kPipeOut : (strm->avail_out > kMinBatchOut ? strm->avail_out : kMinBatchOut)) + skip;
-    uint64_t max_rsi = room / rsi_bytes + 2;
-    const uint64_t min_rsi_bits = (uint64_t)c.segs_per_rsi * (c.id_len + 2) + ((c.flags & F_PREPROCESS) ? c.bps : 0);
-    const uint64_t avail_bits = (uint64_t)s->d_len * 8 - rsi_rel;
-    if (max_rsi > avail_bits / min_rsi_bits + 2) max_rsi = avail_bits / min_rsi_bits + 2;
-    // the part of the resident stream this batch can need
-    // (worst_rsi_bytes is what an ENCODER makes of an RSI at most; the format allows longer ones: should the
-    // walker run out of input inside the span while more is resident, the next batch looks further)
-    uint64_t span = walk_rel / 8 + max_rsi * worst_rsi_bytes(c) * s->span_mul + 64;
-    // (pipelined batches: the tables are built over the whole span, so the worst case -- five times the input a
-    // batch of compressible data needs -- would have every batch index most of what is left.  The span is what the
-    // batch's RSIs need on average plus the index pass's look-ahead; the pass is told that it sees a piece
-    // (aec_gpu_set_index_piece) and stops in front of the RSIs its tables cannot resolve at the end of it -- the next
-    // batch's -- instead of walking them serially.)
-    bool piece = false;
-    if (pipe && hint && s->span_mul == 1 && !s->span_wide) {
-        const uint64_t tight = walk_rel / 8 + (max_rsi * hint + 8 * hint) / 8 + 65536;
-        if (tight < span && tight < s->d_len) {
-            span = tight;
-            piece = true;
-        }
-    }
-    const size_t in_bytes = span < s->d_len ? (size_t)span : s->d_len;
-    DevBuf &obuf = s->out_sel ? s->d_out2 : s->d_out;
-    if (!s->d_off.ensure((max_rsi + 2) * 8) || !obuf.ensure(max_rsi * rsi_bytes + blk_bytes + 64))
-        return AEC_FAIL(AEC_MEM_ERROR);
-    // (the copy that read this buffer two batches ago must have finished before the decoder writes it again)
-    if (s->ev_copied[s->out_sel] && s->copy_pending &&
-        hipStreamWaitEvent(s->stream, s->ev_copied[s->out_sel], 0) != hipSuccess)
-        return AEC_FAIL(AEC_MEM_ERROR);
-    // RSIs of eight segments and more: the index pass also leaves the segment starts, and the decoder takes a lane per
-    // segment instead of one per RSI (include/aec_gpu.h: aec_gpu_index_segments_async; without the table -- no memory
-    // for it -- a lane per RSI as before)
+    const uint64_t ahead = plan_hint(c, *s, want_out);
+    const bool windowed = want_out >= kPipeMin &&
+                          aec_gpu_index_is_windowed(&s->prm, s->d_len - (size_t)((s->rsi_start_bit - base_bits) / 8),
+                                                    ahead + ahead / 2) != 0;
+    const BatchPlan b = plan_batch(c, *s, want_out, windowed);
+    if (!s->d_off.ensure(b.off_bytes) || !s->out_buf().ensure(b.out_bytes)) return AEC_FAIL(AEC_MEM_ERROR);
+    DevBuf &obuf = s->out_buf();
+    if (!s->side.claim(s->stream)) return AEC_FAIL(AEC_MEM_ERROR);
+    // (without the table of segment starts -- no memory for it -- a lane per RSI)
     uint64_t *d_seg = nullptr;
-    if (c.segs_per_rsi >= 8 && s->d_seg.ensure((max_rsi + 2) * c.segs_per_rsi * 8)) d_seg = static_cast<uint64_t *>(s->d_seg.p);
+    if (b.seg_bytes && s->d_seg.ensure(b.seg_bytes)) d_seg = static_cast<uint64_t *>(s->d_seg.p);
 
     aec_gpu_dec_result *d_idx = static_cast<aec_gpu_dec_result *>(s->d_res.p), *d_dec = d_idx + 1;
     uint64_t *d_off = static_cast<uint64_t *>(s->d_off.p);
-    aec_gpu_set_index_hint(s->ctx, index_hint_of(c, hint));
-    if (piece) aec_gpu_set_index_piece(s->ctx, 6 * hint + 8192);
-    int rc = d_seg ? aec_gpu_index_segments_async(s->ctx, &s->prm, s->d_in.p, in_bytes, walk_rel, s->walk_blocks, rsi_rel,
-                                                  d_off, d_seg, max_rsi, d_idx, s->stream)
-                   : aec_gpu_index_resume_async(s->ctx, &s->prm, s->d_in.p, in_bytes, walk_rel, s->walk_blocks, rsi_rel,
-                                                d_off, max_rsi, d_idx, s->stream);
+    aec_gpu_set_index_hint(s->ctx, index_hint_of(c, b.hint));
+    if (b.piece) aec_gpu_set_index_piece(s->ctx, 6 * b.hint + 8192);
+    int rc = d_seg ? aec_gpu_index_segments_async(s->ctx, &s->prm, s->d_in.p, b.in_bytes, b.walk_rel, s->walk_blocks, b.rsi_rel,
+                                                  d_off, d_seg, b.max_rsi, d_idx, s->stream)
+                   : aec_gpu_index_resume_async(s->ctx, &s->prm, s->d_in.p, b.in_bytes, b.walk_rel, s->walk_blocks, b.rsi_rel,
+                                                d_off, b.max_rsi, d_idx, s->stream);
     if (rc != RC_OK) return AEC_FAIL(rc);
-    rc = d_seg ? aec_gpu_decode_bare_async(s->ctx, &s->prm, s->d_in.p, in_bytes, d_off, d_seg, max_rsi, 0, d_idx,
+    rc = d_seg ? aec_gpu_decode_bare_async(s->ctx, &s->prm, s->d_in.p, b.in_bytes, d_off, d_seg, b.max_rsi, 0, d_idx,
                                            obuf.p, d_dec, s->stream)
-               : aec_gpu_decode_indexed_async(s->ctx, &s->prm, s->d_in.p, in_bytes, d_off, max_rsi, d_idx, obuf.p,
+               : aec_gpu_decode_indexed_async(s->ctx, &s->prm, s->d_in.p, b.in_bytes, d_off, b.max_rsi, d_idx, obuf.p,
                                               d_dec, s->stream);
     if (rc != RC_OK) return AEC_FAIL(rc);
     // records, the start of the trailing partial RSI, and the first output bytes: one synchronisation
-    uint8_t *bounce = s->h_res + 256;
-    const uint8_t *d_bytes = static_cast<const uint8_t *>(obuf.p) + skip;
-    size_t spec = max_rsi * rsi_bytes - skip;
+    const uint8_t *d_bytes = static_cast<const uint8_t *>(obuf.p) + b.skip;
+    size_t spec = b.max_rsi * rsi_bytes - b.skip;
     if (spec > kBounce) spec = kBounce;
     const auto t_enq = std::chrono::steady_clock::now();                // (AEC_ABI_TRACE: where a batch's time goes)
     if (hipMemcpyAsync(s->h_res, d_idx, 2 * sizeof(aec_gpu_dec_result), hipMemcpyDeviceToHost, s->stream) !=
             hipSuccess ||
-        hipMemcpyAsync(s->h_res + 128, d_off + max_rsi, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipMemcpyAsync(bounce, d_bytes, spec, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(s->h_res + 128, d_off + b.max_rsi, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        hipMemcpyAsync(s->h_res + 256, d_bytes, spec, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
         hipStreamSynchronize(s->stream) != hipSuccess)
         return AEC_FAIL(AEC_MEM_ERROR);
     if (trace_on()) {
@@ -594,98 +521,22 @@ int decode_run(internal_state *s, struct aec_stream *strm)
     const aec_gpu_dec_result dec = reinterpret_cast<aec_gpu_dec_result *>(s->h_res)[1];
     if (trace_on())
         fprintf(stderr, "libaec (MI355X): decode batch: pipelined %d, room for %llu RSIs, span %zu of %zu resident bytes (from byte %llu), "
-                "hint %llu bits per RSI -> %llu RSIs + %llu blocks, walker status %u pad %u\n", (int)pipe, (unsigned long long)max_rsi,
-                in_bytes, s->d_len, (unsigned long long)(walk_rel / 8), (unsigned long long)hint, (unsigned long long)idx.n_rsi,
+                "hint %llu bits per RSI -> %llu RSIs + %llu blocks, walker status %u pad %u\n", (int)b.pipe, (unsigned long long)b.max_rsi,
+                b.in_bytes, s->d_len, (unsigned long long)(b.walk_rel / 8), (unsigned long long)b.hint, (unsigned long long)idx.n_rsi,
                 (unsigned long long)idx.tail_blocks, idx.status, idx.pad);
     uint64_t tail_start = 0;
     memcpy(&tail_start, s->h_res + 128, 8);
 
-    // What is good: all of it, or -- when the decoder met a corrupt coded data set the walker could
-    // not see (a second-extension code beyond the table, reference decode.c:589-616) -- the RSIs in
-    // front of the first bad one; the reference delivers every sample preceding the error as well.
-    uint64_t good_rsi = idx.n_rsi, tail_blocks = idx.tail_blocks;
-    bool corrupt = idx.status == DEC_DATA_ERROR;
-    if (dec.status != DEC_OK) {
-        corrupt = true;
-        if (dec.bad_rsi <= good_rsi) {
-            // (the decode record's tail_blocks: the lowest failing block of the batch -- the blocks of its RSI in
-            // front of it are decoded and good)
-            const uint64_t bad_block = dec.tail_blocks;
-            good_rsi = dec.bad_rsi;
-            tail_blocks = (bad_block != ~0ull && bad_block / c.rsi == good_rsi) ? bad_block % c.rsi : 0;
-        }
+    // the samples in front of an error are delivered before it is reported
+    BatchVerdict v = judge_batch(c, idx, dec, b.skip, want_out);
+    if (v.total > b.skip) {
+        const int hrc = hand_out(s, strm, d_bytes, v.total - b.skip, 0, spec, c.bytes, b.pipe);
+        if (hrc != AEC_OK) return hrc;
     }
-    // samples released from the coded data set the input ends in (reference decode.c:423-460)
-    const uint32_t part = (!corrupt && idx.pad == 1) ? (dec.pad & 0x7FFFFFFFu) : 0u;   // (bit 31: slow path ran)
-    const uint64_t blocks = good_rsi * c.rsi + tail_blocks;
-    const size_t total = (size_t)blocks * blk_bytes + (size_t)part * c.bytes;
-    if (total > skip) {
-        const size_t fresh = total - skip;
-        size_t direct = fresh < strm->avail_out ? fresh : strm->avail_out;
-        direct -= direct % c.bytes;
-        if (direct) {
-            const size_t from_bounce = direct < spec ? direct : spec;
-            memcpy(strm->next_out, bounce, from_bounce);
-            if (direct > from_bounce) {
-                const size_t rest = direct - from_bounce;
-                // a large rest goes on the side stream: the next batch's kernels (the other output buffer) run beside
-                // it, and the call waits for it before it returns (copies_done)
-                bool async = pipe && rest >= kAsyncMin;
-                if (async && !s->copy_stream) async = hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking) == hipSuccess;
-                if (async && !s->ev_copied[s->out_sel])
-                    async = hipEventCreateWithFlags(&s->ev_copied[s->out_sel], hipEventDisableTiming) == hipSuccess;
-                if (async) {
-                    if (hipMemcpyAsync(strm->next_out + from_bounce, d_bytes + from_bounce, rest, hipMemcpyDeviceToHost,
-                                       s->copy_stream) != hipSuccess ||
-                        hipEventRecord(s->ev_copied[s->out_sel], s->copy_stream) != hipSuccess)
-                        return AEC_FAIL(AEC_MEM_ERROR);
-                    s->copy_pending = true;
-                    s->out_sel ^= 1u;
-                } else {
-                    (void)hipGetLastError();
-                    if (hipMemcpy(strm->next_out + from_bounce, d_bytes + from_bounce, rest, hipMemcpyDeviceToHost) != hipSuccess)
-                        return AEC_FAIL(AEC_MEM_ERROR);
-                }
-            }
-            strm->next_out += direct;
-            strm->avail_out -= direct;
-        }
-        if (fresh > direct) {
-            const size_t rest = fresh - direct, at = s->outq.size();
-            s->outq.resize(at + rest);
-            size_t done = 0;
-            if (direct < spec) {
-                done = spec - direct < rest ? spec - direct : rest;
-                memcpy(s->outq.data() + at, bounce + direct, done);
-            }
-            if (rest > done &&
-                hipMemcpy(s->outq.data() + at + done, d_bytes + direct + done, rest - done, hipMemcpyDeviceToHost) !=
-                    hipSuccess)
-                return AEC_FAIL(AEC_MEM_ERROR);
-        }
-    }
-    // A coded data set that cannot be accepted -- a zero run overrunning its RSI (found by the walker), a
-    // second-extension code beyond the table (found by the decoder) -- BEHIND everything this call was asked for is
-    // not this call's error: the reference stops when the output is full (decode.c:797-831) and only meets it
-    // when it is asked for more, as the next call here will.  The walk then resumes at the coded data set the walker
-    // stopped at, or at the start of the RSI the decoder gave up.
-    uint64_t res_rsi = idx.n_rsi, res_tail = idx.tail_blocks, res_end = idx.end_bit;
-    bool more_behind = false;
-    // (a call that offers NO room defers what the walker found -- the reference's m_zero_block only refuses a run when
-    // avail_out holds it, decode.c:542-544 -- but not a second-extension code beyond the table, which the reference
-    // reports whatever the room, decode.c:589-616)
-    if (corrupt && total >= skip + want_out && (want_out || dec.status == DEC_OK)) {
-        corrupt = false;
-        more_behind = true;                                 // (the next call that offers room meets the error)
-        if (dec.status != DEC_OK) {
-            uint64_t off = 0;
-            if (hipMemcpy(&off, d_off + good_rsi, 8, hipMemcpyDeviceToHost) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-            res_rsi = good_rsi;
-            res_tail = 0;                                   // (the walker starts the RSI again; its good blocks are `delivered`)
-            res_end = off;
-        }
-    }
-    if (corrupt) {
+    // (a decoder's error deferred to the next call: the walk resumes at the start of the RSI the decoder gave up)
+    if (v.fetch_off && hipMemcpy(&v.res_end, d_off + v.good_rsi, 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return AEC_FAIL(AEC_MEM_ERROR);
+    if (v.corrupt) {
         if (trace_on())
             fprintf(stderr, "libaec (MI355X): AEC_DATA_ERROR: walker status %u after %llu RSIs + %llu blocks (bit %llu), "
                     "decoder status %u at RSI %llu\n", idx.status, (unsigned long long)idx.n_rsi,
@@ -693,52 +544,24 @@ int decode_run(internal_state *s, struct aec_stream *strm)
                     (unsigned long long)dec.bad_rsi);
         return AEC_DATA_ERROR;
     }
-    if (res_rsi) s->rsi_bits_seen = (res_end - rsi_rel) / (res_rsi + (res_tail ? 1 : 0));
     // offsets enabled: the RSIs of the batch whose first coded data set is decoded -- the whole ones, and the one it
     // ends in -- in absolute bits; the first of them may be the one the batch in front ended in (counted once)
-    if (s->offsets_on && (res_rsi || res_tail)) {
-        std::vector<uint64_t> got(res_rsi + (res_tail ? 1 : 0));
-        if (res_rsi && hipMemcpy(got.data(), d_off, res_rsi * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    if (s->offsets_on && (v.res_rsi || v.res_tail)) {
+        std::vector<uint64_t> got(v.res_rsi + (v.res_tail ? 1 : 0));
+        if (v.res_rsi && hipMemcpy(got.data(), d_off, v.res_rsi * 8, hipMemcpyDeviceToHost) != hipSuccess)
             return AEC_FAIL(AEC_MEM_ERROR);
-        if (res_tail) got[res_rsi] = tail_start;
-        for (const uint64_t v : got)
-            if (s->offs.empty() || base_bits + v > s->offs.back()) s->offs.push_back(base_bits + v);
+        if (v.res_tail) got[v.res_rsi] = tail_start;
+        for (const uint64_t o : got)
+            if (s->offs.empty() || base_bits + o > s->offs.back()) s->offs.push_back(base_bits + o);
     }
-
-    // advance: the walker resumes behind the last complete coded data set
-    s->walk_bit = base_bits + res_end;
-    s->walk_blocks = (uint32_t)res_tail;
-    if (res_tail) {
-        s->rsi_start_bit = base_bits + tail_start;
-        s->delivered = res_tail * c.bs + part;
-    } else {
-        s->rsi_start_bit = s->walk_bit;
-        s->delivered = (more_behind && dec.status != DEC_OK) ? tail_blocks * c.bs : part;
-    }
-    s->walked_len = in_bytes;
-    // (the walker ran out of input inside the span although more is resident: first the worst case instead of the
-    // tight span of the pipelined batches, then wider and wider)
-    if (idx.pad == 1 && in_bytes < s->d_len) {
-        if (piece && !s->span_wide) s->span_wide = true;
-        else s->span_mul = s->span_mul < (1u << 20) ? s->span_mul * 4 : s->span_mul;
-    } else {
-        s->span_mul = 1;
-    }
-    // stopped at the bound with input left: the caller's next call (or this one, if it still has
-    // room) goes on from here
-    s->more = idx.n_rsi >= max_rsi || in_bytes < s->d_len || more_behind;
-
-    // drop the consumed front of the resident stream once it is the larger part (the copy must not overlap)
-    const uint64_t keep_from = (s->rsi_start_bit / 8 - s->base) & ~(uint64_t)15;
-    const size_t rem = s->d_len - (size_t)keep_from;
-    if (keep_from >= rem && keep_from >= 4096) {
-        if (rem && hipMemcpyAsync(s->d_in.p, static_cast<uint8_t *>(s->d_in.p) + keep_from, rem,
-                                  hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
-            return AEC_FAIL(AEC_MEM_ERROR);
-        s->base += keep_from;
-        s->d_len = rem;
-        s->walked_len = s->walked_len > keep_from ? s->walked_len - (size_t)keep_from : 0;
-    }
+    // the stream's new position; the consumed front of the resident stream goes (the copy must not overlap:
+    // advance_stream drops the front only once it is the larger part)
+    StreamPos next = *s;
+    const size_t drop = advance_stream(c, next, b, v, idx, tail_start);
+    if (drop && next.d_len && hipMemcpyAsync(s->d_in.p, static_cast<uint8_t *>(s->d_in.p) + drop, next.d_len,
+                                             hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
+        return AEC_FAIL(AEC_MEM_ERROR);
+    static_cast<StreamPos &>(*s) = next;
     return AEC_OK;
 }
 
@@ -887,10 +710,7 @@ int decode_call(struct aec_stream *strm, int flush)
         if (!progressed) break;           // what is here needs more input before anything else comes out
     }
     // (copies to the caller's buffer that run on the side stream: the buffer is the caller's again on return)
-    if (s->copy_pending) {
-        s->copy_pending = false;
-        if (hipStreamSynchronize(s->copy_stream) != hipSuccess && rc == AEC_OK) rc = AEC_FAIL(AEC_MEM_ERROR);
-    }
+    if (!s->side.done() && rc == AEC_OK) rc = AEC_FAIL(AEC_MEM_ERROR);
     if (rc == AEC_DATA_ERROR) drain(strm, s, bytes);   // the samples in front of the error are delivered
     if (rc != AEC_OK) return rc;          // reference decode.c:818-819 (totals left as they are)
     if (strm->avail_out > 0 && strm->avail_out < bytes) return AEC_FAIL(AEC_MEM_ERROR);   // decode.c:821-823
@@ -902,20 +722,9 @@ int decode_call(struct aec_stream *strm, int flush)
 // ---- many independent streams per call (include/libaec.h: aec_buffer_*_batch) -------------------------
 struct BatchKit {
     Kit k;
-    bool ok = false;
-    explicit BatchKit(int device)
-    {
-        if (take_kit(device, &k)) { ok = true; return; }
-        k.device = device;
-        ok = aec_gpu_create(&k.ctx) == RC_OK && hipStreamCreate(&k.stream) == hipSuccess &&
-             hipHostMalloc(reinterpret_cast<void **>(&k.h_res), 256 + kBounce, hipHostMallocDefault) == hipSuccess &&
-             k.d_res.ensure(256);
-    }
-    ~BatchKit()
-    {
-        if (ok && k.ctx && k.stream && k.h_res && k.d_res.p) park_kit(k);
-        else destroy_kit(k);
-    }
+    const bool ok;
+    BatchKit() : ok(obtain_kit(k)) {}
+    ~BatchKit() { give_kit(k); }
 };
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -943,20 +752,28 @@ struct CopyJob {
 };
 thread_local bool t_in_part = false;          // this thread is one of run_parts' workers: no threads of its own
 
-// Waiting for a kit's stream inside the batch paths.  With several host threads each waiting on a stream of its own,
-// hipStreamSynchronize was measured to return up to 9 ms late now and then (2.4 ms batches taking 10); polling the
-// stream does not.  The poll yields for the first few dozen microseconds -- a small batch is through by then -- and then
-// sleeps between two looks (round 6: a part thread burnt a core for the whole of its batch; the timer's slack, ~60 us,
-// is a few per cent of the milliseconds such a batch takes).
-hipError_t batch_sync(hipStream_t st)
+// Waiting for a kit's stream, or for an event on it, inside the batch paths.  With several host threads each waiting on
+// a stream of its own, hipStreamSynchronize was measured to return up to 9 ms late now and then (2.4 ms batches taking
+// 10); polling the stream does not.  The poll yields for the first few dozen microseconds -- a small batch is through by
+// then -- and then sleeps between two looks (round 6: a part thread burnt a core for the whole of its batch; the timer's
+// slack, ~60 us, is a few per cent of the milliseconds such a batch takes).
+template <class Query>
+hipError_t poll(Query query)
 {
-    if (!t_in_part) return hipStreamSynchronize(st);
     for (unsigned spins = 0;; spins++) {
-        const hipError_t e = hipStreamQuery(st);
+        const hipError_t e = query();
         if (e != hipErrorNotReady) return e;
         if (spins < 256u) std::this_thread::yield();
         else std::this_thread::sleep_for(std::chrono::microseconds(25));
     }
+}
+hipError_t batch_sync(hipStream_t st)
+{
+    return t_in_part ? poll([st] { return hipStreamQuery(st); }) : hipStreamSynchronize(st);
+}
+hipError_t batch_sync(hipEvent_t ev)
+{
+    return t_in_part ? poll([ev] { return hipEventQuery(ev); }) : hipEventSynchronize(ev);
 }
 
 void copy_all(const std::vector<CopyJob> &jobs)
@@ -976,6 +793,107 @@ void copy_all(const std::vector<CopyJob> &jobs)
     }
     // (the pool's threads, kept between calls -- round 5; until then a thread per share was created and joined per call)
     WorkerPool::run(nt, [&](size_t t) { work((unsigned)t); });
+}
+
+// Many chunks from the callers' buffers into k.d_in.  Chunk i is len(i) bytes at src[i] and goes to byte at(i) of
+// d_in; at(i + 1) - at(i) is the room it has there (at(n): the end of the last one).  cap != 0: through the pinned
+// staging buffer in pieces of as many whole chunks as cap bytes hold -- the host's copies on a few threads, ONE
+// transfer per piece, each waiting until the piece in front has left the buffer; cap == 0: chunk by chunk, straight
+// from the callers' buffers.  zero: the room behind every chunk is zeroed.  each(i) runs once chunk i is on its way
+// (launches on k.stream that read it); anything but AEC_OK from it ends the transfer and is returned.
+template <class At, class Len, class Each>
+int stage_up(Kit &k, size_t n, const void *const *src, At at, Len len, size_t cap, bool zero, Each each)
+{
+    uint8_t *d_in = static_cast<uint8_t *>(k.d_in.p);
+    if (!cap) {
+        if (zero && hipMemsetAsync(d_in + at(0), 0, at(n) - at(0), k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
+        for (size_t i = 0; i < n; i++) {
+            if (len(i) && hipMemcpyAsync(d_in + at(i), src[i], len(i), hipMemcpyHostToDevice, k.stream) != hipSuccess)
+                return AEC_FAIL(AEC_MEM_ERROR);
+            const int rc = each(i);
+            if (rc != AEC_OK) return rc;
+        }
+        return AEC_OK;
+    }
+    std::vector<CopyJob> jobs;
+    for (size_t i = 0, j; i < n; i = j) {
+        for (j = i; j < n && at(j + 1) - at(i) <= cap;) j++;
+        if (j == i) return AEC_FAIL(AEC_MEM_ERROR);                               // (cannot happen: a chunk fits)
+        if (i && batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);   // staging is free again
+        jobs.clear();
+        for (size_t q = i; q < j; q++) {
+            uint8_t *h = k.h_stage + (at(q) - at(i));
+            jobs.push_back(CopyJob{h, src[q], len(q)});
+            if (zero) memset(h + len(q), 0, at(q + 1) - at(q) - len(q));
+        }
+        copy_all(jobs);
+        if (hipMemcpyAsync(d_in + at(i), k.h_stage, at(j) - at(i), hipMemcpyHostToDevice, k.stream) != hipSuccess)
+            return AEC_FAIL(AEC_MEM_ERROR);
+        for (size_t q = i; q < j; q++) {
+            const int rc = each(q);
+            if (rc != AEC_OK) return rc;
+        }
+    }
+    return AEC_OK;
+}
+inline int no_launch(size_t) { return AEC_OK; }
+
+// What a batch left in k.d_out to the callers' buffers, then the end of the batch is waited for.  Chunk i occupies
+// ext(i) bytes at byte pos(i) of d_out; done(i, &st) says how many of them the caller gets (dst_len[i]) and with what
+// status (status[i]; the last one that is not AEC_OK is returned).  cap != 0: through the pinned staging buffer in
+// pieces of as many whole chunks as cap bytes hold (one that alone is larger goes directly) -- ONE transfer per piece,
+// then copies to the callers' buffers on a few threads.  twice: the buffer has two halves of cap bytes and k.side.ev
+// its two events; the transfer of piece p + 1 runs beside the host's copies of piece p (every chunk fits then).
+// cap == 0: chunk by chunk, straight into the callers' buffers.
+template <class Pos, class Ext, class Done>
+int stage_down(Kit &k, size_t n, void *const *dst, size_t *dst_len, int *status, Pos pos, Ext ext, size_t cap, bool twice,
+               Done done)
+{
+    const uint8_t *d_out = static_cast<const uint8_t *>(k.d_out.p);
+    auto cut = [&](size_t i) {                       // the end of the piece that begins with chunk i (i: it does not fit)
+        size_t j = i;
+        while (cap && j < n && pos(j) + ext(j) - pos(i) <= cap) j++;
+        return j;
+    };
+    auto fetch = [&](size_t i, size_t j, unsigned half) {        // the transfer of chunks [i, j) into a half of the buffer
+        return hipMemcpyAsync(k.h_stage + half * cap, d_out + pos(i), pos(j - 1) + ext(j - 1) - pos(i), hipMemcpyDeviceToHost,
+                              k.stream) == hipSuccess &&
+               (!twice || hipEventRecord(k.side.ev[half], k.stream) == hipSuccess);
+    };
+    int worst = AEC_OK;
+    std::vector<CopyJob> jobs;
+    size_t j = cut(0);
+    if (twice && !fetch(0, j, 0)) return AEC_FAIL(AEC_MEM_ERROR);
+    for (size_t i = 0, piece = 0; i < n; piece++) {
+        const unsigned half = twice ? piece & 1u : 0u;
+        const bool staged = j > i;
+        size_t next = 0;
+        if (staged && twice) {                       // the next piece sets out, this one has to be here
+            next = cut(j);
+            if ((next > j && !fetch(j, next, half ^ 1u)) || batch_sync(k.side.ev[half]) != hipSuccess)
+                return AEC_FAIL(AEC_MEM_ERROR);
+        } else if (staged) {
+            if (!fetch(i, j, 0) || batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
+        } else {
+            j = i + 1;
+        }
+        jobs.clear();
+        for (size_t q = i; q < j; q++) {
+            int st = AEC_OK;
+            const size_t bytes = done(q, &st);
+            if (staged) jobs.push_back(CopyJob{dst[q], k.h_stage + half * cap + (pos(q) - pos(i)), bytes});
+            else if (bytes && hipMemcpyAsync(dst[q], d_out + pos(q), bytes, hipMemcpyDeviceToHost, k.stream) != hipSuccess)
+                return AEC_FAIL(AEC_MEM_ERROR);
+            dst_len[q] = bytes;
+            if (status) status[q] = st;
+            if (st != AEC_OK) worst = st;
+        }
+        copy_all(jobs);
+        i = j;
+        j = twice ? next : cut(i);
+    }
+    if (batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
+    return worst;
 }
 
 // A large batch as several parts side by side: every part is a batch of its own on its own kit (HIP stream,
@@ -1024,12 +942,9 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
     int rc = make_cfg(gp.bits_per_sample, gp.block_size, gp.rsi, gp.flags, 0, false, &c);
     if (rc != RC_OK) return AEC_FAIL(rc);
     if (n == 0) return AEC_OK;
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-    BatchKit bk(device);
+    BatchKit bk;
     if (!bk.ok) return AEC_FAIL(AEC_MEM_ERROR);
-    Kit &k = bk.k;
-    aec_gpu_set_index_hint(k.ctx, 0);      // (a kit from the pool: whatever its last stream measured is not this batch's)
+    Kit &k = bk.k;                         // (from the pool: parked with its index hint reset)
     const size_t blk_bytes = (size_t)c.bs * c.bytes, rsi_bytes = (size_t)c.rsi * blk_bytes;
     // geometry: every stream gets room for the RSIs of the largest one
     uint64_t rpc = 1;
@@ -1053,23 +968,11 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
         !k.d_off.ensure(o_one + 64))
         return AEC_FAIL(AEC_MEM_ERROR);
     uint8_t *meta = static_cast<uint8_t *>(k.d_off.p);
-    if (n >= 4 && total_in <= kStagePiece && stage_ensure(k, total_in)) {
-        // the streams and the zero padding behind each of them, assembled in pinned memory: ONE transfer
-        std::vector<CopyJob> jobs(n);
-        for (size_t i = 0; i < n; i++) {
-            jobs[i] = CopyJob{k.h_stage + off[i], src[i], src_len[i]};
-            memset(k.h_stage + off[i] + src_len[i], 0, (size_t)(off[i + 1] - off[i]) - src_len[i]);
-        }
-        copy_all(jobs);
-        if (hipMemcpyAsync(k.d_in.p, k.h_stage, total_in, hipMemcpyHostToDevice, k.stream) != hipSuccess)
-            return AEC_FAIL(AEC_MEM_ERROR);
-    } else {
-        if (hipMemsetAsync(k.d_in.p, 0, total_in, k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-        for (size_t i = 0; i < n; i++)
-            if (src_len[i] && hipMemcpyAsync(static_cast<uint8_t *>(k.d_in.p) + off[i], src[i], src_len[i],
-                                             hipMemcpyHostToDevice, k.stream) != hipSuccess)
-                return AEC_FAIL(AEC_MEM_ERROR);
-    }
+    // (assembled in pinned memory and ONE transfer where there are a few of them and staging is to be had)
+    const auto at_in = [&](size_t i) { return (size_t)off[i]; };
+    const bool stage_in = n >= 4 && total_in <= kStagePiece && stage_ensure(k, total_in);
+    rc = stage_up(k, n, src, at_in, [&](size_t i) { return src_len[i]; }, stage_in ? total_in : 0, true, no_launch);
+    if (rc != AEC_OK) return rc;
     if (hipMemcpyAsync(meta + o_choff, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, k.stream) != hipSuccess)
         return AEC_FAIL(AEC_MEM_ERROR);
     // Small chunks: one wavefront walks each stream, all streams at once (aec_gpu_decode_batch_async).
@@ -1159,7 +1062,6 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
         hipMemcpyAsync(&res[n], meta + o_one, sizeof(aec_gpu_dec_result), hipMemcpyDeviceToHost, k.stream) != hipSuccess ||
         batch_sync(k.stream) != hipSuccess)
         return AEC_FAIL(AEC_MEM_ERROR);
-    int worst = AEC_OK;
     // the outputs: through pinned staging in pieces of whole slots (one transfer per piece, then copies to the
     // callers' buffers on a few threads), or chunk by chunk where there is no staging to be had
     // (pieces of about 4 MiB through the two halves of the staging buffer: the transfer of piece p + 1 runs beside the
@@ -1169,51 +1071,17 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
     constexpr size_t kOutPiece = (size_t)4 << 20;
     const size_t per_piece = !slot_out ? 0 : (slot_out <= kOutPiece ? kOutPiece / slot_out : (slot_out <= kStagePiece / 2 ? 1 : 0));
     const size_t npieces = per_piece ? (n + per_piece - 1) / per_piece : 0;
-    const size_t half_bytes = per_piece * slot_out;
-    bool staged = n >= 4 && per_piece && stage_ensure(k, (npieces > 1 ? 2 : 1) * (n < per_piece ? n : per_piece) * slot_out);
-    for (int e = 0; e < 2 && staged; e++)
-        if (!k.ev_copied[e]) staged = hipEventCreateWithFlags(&k.ev_copied[e], hipEventDisableTiming) == hipSuccess;
-    auto fetch = [&](size_t piece) -> bool {         // the transfer of a piece into half (piece & 1)
-        const size_t first = piece * per_piece, cnt = n - first < per_piece ? n - first : per_piece;
-        return hipMemcpyAsync(k.h_stage + (piece & 1) * half_bytes, static_cast<uint8_t *>(k.d_out.p) + first * slot_out,
-                              cnt * slot_out, hipMemcpyDeviceToHost, k.stream) == hipSuccess &&
-               hipEventRecord(k.ev_copied[piece & 1], k.stream) == hipSuccess;
-    };
-    auto landed = [&](size_t piece) -> bool {
-        if (!t_in_part) return hipEventSynchronize(k.ev_copied[piece & 1]) == hipSuccess;
-        for (unsigned spins = 0;; spins++) {         // (polling, as batch_sync does)
-            const hipError_t e = hipEventQuery(k.ev_copied[piece & 1]);
-            if (e != hipErrorNotReady) return e == hipSuccess;
-            if (spins < 256u) std::this_thread::yield();
-            else std::this_thread::sleep_for(std::chrono::microseconds(25));
-        }
-    };
-    if (staged && !fetch(0)) return AEC_FAIL(AEC_MEM_ERROR);
-    std::vector<CopyJob> jobs;
-    for (size_t i = 0; i < n; i++) {
+    const bool staged = n >= 4 && per_piece && stage_ensure(k, (npieces > 1 ? 2 : 1) * (n < per_piece ? n : per_piece) * slot_out) &&
+                        k.side.event(0) && k.side.event(1);
+    return stage_down(k, n, dst, dst_len, status, [&](size_t i) { return i * slot_out; }, [&](size_t) { return slot_out; },
+                      staged ? per_piece * slot_out : 0, staged, [&](size_t i, int *st) {
         const uint64_t blocks = res[i].n_rsi * c.rsi + res[i].tail_blocks;
         size_t produced = (size_t)blocks * blk_bytes;
         if (produced > dst_len[i]) produced = dst_len[i] - dst_len[i] % c.bytes;
-        int st = res[i].status == DEC_DATA_ERROR ? AEC_DATA_ERROR : AEC_OK;
-        if (!grouped && res[n].status != DEC_OK && res[n].bad_rsi / rpc == i) st = AEC_DATA_ERROR;
-        if (staged) {
-            const size_t piece = i / per_piece, first = piece * per_piece;
-            if (i == first) {                            // a new piece: the next one sets out, this one has to be here
-                if ((piece + 1 < npieces && !fetch(piece + 1)) || !landed(piece)) return AEC_FAIL(AEC_MEM_ERROR);
-                jobs.clear();
-            }
-            jobs.push_back(CopyJob{dst[i], k.h_stage + (piece & 1) * half_bytes + (i - first) * slot_out, produced});
-            if (i + 1 == n || (i + 1) % per_piece == 0) copy_all(jobs);
-        } else if (produced && hipMemcpyAsync(dst[i], static_cast<uint8_t *>(k.d_out.p) + i * slot_out, produced,
-                                              hipMemcpyDeviceToHost, k.stream) != hipSuccess) {
-            return AEC_FAIL(AEC_MEM_ERROR);
-        }
-        dst_len[i] = produced;
-        if (status) status[i] = st;
-        if (st != AEC_OK) worst = st;
-    }
-    if (batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-    return worst;
+        if (res[i].status == DEC_DATA_ERROR) *st = AEC_DATA_ERROR;
+        if (!grouped && res[n].status != DEC_OK && res[n].bad_rsi / rpc == i) *st = AEC_DATA_ERROR;
+        return produced;
+    });
 }
 
 int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const *src, const size_t *src_len,
@@ -1224,9 +1092,7 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
     int rc = make_cfg(gp.bits_per_sample, gp.block_size, gp.rsi, gp.flags, 0, true, &c);
     if (rc != RC_OK) return AEC_FAIL(rc);
     if (n == 0) return AEC_OK;
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-    BatchKit bk(device);
+    BatchKit bk;
     if (!bk.ok) return AEC_FAIL(AEC_MEM_ERROR);
     Kit &k = bk.k;
     std::vector<uint64_t> off(n + 1);
@@ -1255,25 +1121,10 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
             const size_t per_up = len <= kStagePiece ? kStagePiece / len : 0;
             // (also large chunks: copies from and to pageable memory issued by several threads at once were measured
             // erratic -- 2.4 or 9 ms for the same 64 MiB -- while pinned transfers plus plain memcpy are steady)
-            const bool stage_up = per_up && stage_ensure(k, (n < per_up ? n : per_up) * len);
-            for (size_t i = 0; i < n;) {
-                if (stage_up) {
-                    const size_t cnt = n - i < per_up ? n - i : per_up;
-                    if (i && batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-                    std::vector<CopyJob> jobs;
-                    for (size_t q = 0; q < cnt; q++) jobs.push_back(CopyJob{k.h_stage + q * len, src[i + q], len});
-                    copy_all(jobs);
-                    if (hipMemcpyAsync(static_cast<uint8_t *>(k.d_in.p) + i * len, k.h_stage, cnt * len, hipMemcpyHostToDevice,
-                                       k.stream) != hipSuccess)
-                        return AEC_FAIL(AEC_MEM_ERROR);
-                    i += cnt;
-                } else {
-                    if (hipMemcpyAsync(static_cast<uint8_t *>(k.d_in.p) + i * len, src[i], len, hipMemcpyHostToDevice,
-                                       k.stream) != hipSuccess)
-                        return AEC_FAIL(AEC_MEM_ERROR);
-                    i++;
-                }
-            }
+            const size_t up_bytes = (n < per_up ? n : per_up) * len;
+            const size_t cap_up = per_up && stage_ensure(k, up_bytes) ? up_bytes : 0;
+            rc = stage_up(k, n, src, [&](size_t i) { return i * len; }, [&](size_t) { return len; }, cap_up, false, no_launch);
+            if (rc != AEC_OK) return rc;
             rc = aec_gpu_encode_uniform_batch_async(k.ctx, &gp, k.d_in.p, len, n, k.d_out.p, cap, d_chunks, d_one, k.stream);
             if (rc != RC_OK) return AEC_FAIL(rc);
 
@@ -1286,44 +1137,15 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
             if (one.overflow) return AEC_FAIL(AEC_MEM_ERROR);                     // (cannot happen: cap is the sum of the bounds)
 
             // down: the packed streams in pieces of whole streams through the staging buffer
-            int worst = AEC_OK;
             const size_t total = (size_t)(one.total_bits / 8);
-            const bool stage_down = stage_ensure(k, total < kStagePiece ? (total ? total : 16) : kStagePiece);
-            for (size_t i = 0; i < n;) {
-                const size_t lo = (size_t)(rec[i].base_bits / 8);
-                size_t j = i, hi = lo;
-                while (j < n && (size_t)(rec[j].base_bits / 8) + (size_t)((rec[j].bits + 7) / 8) - lo <= k.h_stage_cap) {
-                    hi = (size_t)(rec[j].base_bits / 8) + (size_t)((rec[j].bits + 7) / 8);
-                    j++;
-                }
-                const bool piece = stage_down && j > i;
-                if (piece) {
-                    if (hipMemcpyAsync(k.h_stage, static_cast<uint8_t *>(k.d_out.p) + lo, hi - lo, hipMemcpyDeviceToHost,
-                                       k.stream) != hipSuccess ||
-                        batch_sync(k.stream) != hipSuccess)
-                        return AEC_FAIL(AEC_MEM_ERROR);
-                } else {
-                    j = i + 1;
-                }
-                std::vector<CopyJob> jobs;
-                for (size_t q = i; q < j; q++) {
-                    size_t bytes = (size_t)((rec[q].bits + 7) / 8);
-                    int st = AEC_OK;
-                    if (bytes > dst_len[q]) { st = AEC_STREAM_ERROR; bytes = dst_len[q]; }     // as aec_buffer_encode: a prefix
-                    const size_t at = (size_t)(rec[q].base_bits / 8);
-                    if (piece) jobs.push_back(CopyJob{dst[q], k.h_stage + (at - lo), bytes});
-                    else if (bytes && hipMemcpyAsync(dst[q], static_cast<uint8_t *>(k.d_out.p) + at, bytes, hipMemcpyDeviceToHost,
-                                                     k.stream) != hipSuccess)
-                        return AEC_FAIL(AEC_MEM_ERROR);
-                    dst_len[q] = bytes;
-                    if (status) status[q] = st;
-                    if (st != AEC_OK) worst = st;
-                }
-                copy_all(jobs);
-                i = j;
-            }
-            if (batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-            return worst;
+            const bool staged = stage_ensure(k, total < kStagePiece ? (total ? total : 16) : kStagePiece);
+            const auto ext = [&](size_t i) { return (size_t)((rec[i].bits + 7) / 8); };
+            return stage_down(k, n, dst, dst_len, status, [&](size_t i) { return (size_t)(rec[i].base_bits / 8); }, ext,
+                              staged ? k.h_stage_cap : 0, false, [&](size_t i, int *st) {
+                if (ext(i) <= dst_len[i]) return ext(i);
+                *st = AEC_STREAM_ERROR;                                                     // as aec_buffer_encode: a prefix
+                return dst_len[i];
+            });
         }
     }
     const size_t slot = aec_gpu_encode_bound(&gp, largest);
@@ -1335,71 +1157,31 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
     aec_gpu_enc_result *d_res = static_cast<aec_gpu_enc_result *>(k.d_off.p);
     if (aec_gpu_reserve(k.ctx, &gp, largest) != RC_OK) return AEC_FAIL(AEC_MEM_ERROR);
     const bool stage_in = n >= 16 && largest <= ((size_t)256 << 10) && stage_ensure(k, total_in < kStagePiece ? total_in : kStagePiece);
-    size_t staged_to = 0;                                // chunks [.., staged_to) are on the device
-    for (size_t i = 0; i < n; i++) {
-        const size_t whole = src_len[i] - src_len[i] % c.bytes;
-        if (stage_in) {
-            if (i == staged_to) {
-                size_t j = i;
-                while (j < n && off[j + 1] - off[i] <= k.h_stage_cap) j++;
-                if (j == i) return AEC_FAIL(AEC_MEM_ERROR);                       // (cannot happen: a chunk fits)
-                if (i && batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);   // staging is free again
-                std::vector<CopyJob> jobs;
-                for (size_t q = i; q < j; q++)
-                    jobs.push_back(CopyJob{k.h_stage + (off[q] - off[i]), src[q], src_len[q] - src_len[q] % c.bytes});
-                copy_all(jobs);
-                if (hipMemcpyAsync(static_cast<uint8_t *>(k.d_in.p) + off[i], k.h_stage, (size_t)(off[j] - off[i]),
-                                   hipMemcpyHostToDevice, k.stream) != hipSuccess)
-                    return AEC_FAIL(AEC_MEM_ERROR);
-                staged_to = j;
-            }
-        } else if (whole && hipMemcpyAsync(static_cast<uint8_t *>(k.d_in.p) + off[i], src[i], whole, hipMemcpyHostToDevice,
-                                           k.stream) != hipSuccess) {
-            return AEC_FAIL(AEC_MEM_ERROR);
-        }
-        const uint64_t pair[2] = {off[i], off[i] + whole};
-        rc = aec_gpu_encode_batch_async(k.ctx, &gp, k.d_in.p, pair, 1, static_cast<uint8_t *>(k.d_out.p) + i * slot, slot,
-                                        d_res + i, k.stream);
-        if (rc != RC_OK) return AEC_FAIL(rc);
-    }
+    const auto whole = [&](size_t i) { return src_len[i] - src_len[i] % c.bytes; };
+    rc = stage_up(k, n, src, [&](size_t i) { return (size_t)off[i]; }, whole, stage_in ? k.h_stage_cap : 0, false, [&](size_t i) {
+        const uint64_t pair[2] = {off[i], off[i] + whole(i)};
+        const int erc = aec_gpu_encode_batch_async(k.ctx, &gp, k.d_in.p, pair, 1, static_cast<uint8_t *>(k.d_out.p) + i * slot, slot,
+                                                   d_res + i, k.stream);
+        return erc == RC_OK ? AEC_OK : AEC_FAIL(erc);
+    });
+    if (rc != AEC_OK) return rc;
     std::vector<aec_gpu_enc_result> res(n);
     if (hipMemcpyAsync(res.data(), d_res, n * sizeof(aec_gpu_enc_result), hipMemcpyDeviceToHost, k.stream) != hipSuccess ||
         batch_sync(k.stream) != hipSuccess)
         return AEC_FAIL(AEC_MEM_ERROR);
-    int worst = AEC_OK;
     // many small streams: whole slots through pinned staging, piece by piece (a transfer per piece beats a copy
     // call per stream even though a slot is the worst case of its stream)
     const size_t per_piece = slot <= kStagePiece ? kStagePiece / slot : 0;
     const bool stage_out = n >= 16 && slot <= ((size_t)512 << 10) && per_piece &&
                            stage_ensure(k, (n < per_piece ? n : per_piece) * slot);
-    std::vector<CopyJob> out_jobs;
-    for (size_t i = 0; i < n; i++) {
+    return stage_down(k, n, dst, dst_len, status, [&](size_t i) { return i * slot; }, [&](size_t) { return slot; },
+                      stage_out ? per_piece * slot : 0, false, [&](size_t i, int *st) {
         size_t bytes = (size_t)((res[i].total_bits + 7) / 8);
         if (bytes == 0) bytes = 1;                                           // an empty stream is one zero byte
-        int st = AEC_OK;
-        if (res[i].overflow) st = AEC_MEM_ERROR;
-        else if (bytes > dst_len[i]) { st = AEC_STREAM_ERROR; bytes = dst_len[i]; }   // as aec_buffer_encode: a prefix
-        if (stage_out) {
-            const size_t first = i - i % per_piece;
-            if (i == first) {
-                const size_t cnt = n - first < per_piece ? n - first : per_piece;
-                if (hipMemcpyAsync(k.h_stage, static_cast<uint8_t *>(k.d_out.p) + first * slot, cnt * slot,
-                                   hipMemcpyDeviceToHost, k.stream) != hipSuccess ||
-                    batch_sync(k.stream) != hipSuccess)
-                    return AEC_FAIL(AEC_MEM_ERROR);
-                out_jobs.clear();
-            }
-            out_jobs.push_back(CopyJob{dst[i], k.h_stage + (i - first) * slot, bytes});
-            if (i + 1 == n || (i + 1) % per_piece == 0) copy_all(out_jobs);
-        } else if (bytes && hipMemcpyAsync(dst[i], static_cast<uint8_t *>(k.d_out.p) + i * slot, bytes, hipMemcpyDeviceToHost,
-                                           k.stream) != hipSuccess)
-            return AEC_FAIL(AEC_MEM_ERROR);
-        dst_len[i] = bytes;
-        if (status) status[i] = st;
-        if (st != AEC_OK) worst = st;
-    }
-    if (batch_sync(k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
-    return worst;
+        if (res[i].overflow) *st = AEC_MEM_ERROR;
+        else if (bytes > dst_len[i]) { *st = AEC_STREAM_ERROR; bytes = dst_len[i]; }   // as aec_buffer_encode: a prefix
+        return bytes;
+    });
 }
 
 // ---- random access (include/libaec.h: aec_decode_range) -----------------------------------------------
@@ -1436,7 +1218,6 @@ int decode_range_call(struct aec_stream *strm, const size_t *offs, size_t n, siz
     const size_t per = kPipeOut / rsi_bytes > least ? kPipeOut / rsi_bytes : least;
     aec_gpu_dec_result *d_dec = static_cast<aec_gpu_dec_result *>(s->d_res.p);
     uint8_t *bounce = s->h_res + 256;
-    bool pending[2] = {false, false};
     int rc = AEC_OK;
     std::vector<uint64_t> tbl;
     for (size_t ra = r0; ra <= r1 && rc == AEC_OK; ra += per) {
@@ -1453,13 +1234,9 @@ int decode_range_call(struct aec_stream *strm, const size_t *offs, size_t n, siz
         const size_t in_bytes = to - from;
         tbl.resize(rb - ra + 1 + (next ? 1 : 0));
         for (size_t i = 0; i < tbl.size(); i++) tbl[i] = offs[ra + i] - (uint64_t)from * 8;
-        DevBuf &obuf = s->out_sel ? s->d_out2 : s->d_out;
-        if (!s->d_in.ensure(in_bytes + 32) || !s->d_off.ensure(tbl.size() * 8) || !obuf.ensure(dev_size + 64)) {
-            rc = AEC_FAIL(AEC_MEM_ERROR);
-            break;
-        }
-        // (the copy that read this output buffer two batches ago must be through before the decoder writes it again)
-        if (pending[s->out_sel] && hipStreamWaitEvent(s->stream, s->ev_copied[s->out_sel], 0) != hipSuccess) {
+        DevBuf &obuf = s->out_buf();
+        if (!s->d_in.ensure(in_bytes + 32) || !s->d_off.ensure(tbl.size() * 8) || !obuf.ensure(dev_size + 64) ||
+            !s->side.claim(s->stream)) {
             rc = AEC_FAIL(AEC_MEM_ERROR);
             break;
         }
@@ -1496,29 +1273,10 @@ int decode_range_call(struct aec_stream *strm, const size_t *offs, size_t n, siz
             memcpy(dst, bounce, len);
             continue;
         }
-        bool async = true;
-        if (!s->copy_stream) async = hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking) == hipSuccess;
-        if (async && !s->ev_copied[s->out_sel])
-            async = hipEventCreateWithFlags(&s->ev_copied[s->out_sel], hipEventDisableTiming) == hipSuccess;
-        if (async) {
-            if (hipMemcpyAsync(dst, d_bytes, len, hipMemcpyDeviceToHost, s->copy_stream) != hipSuccess ||
-                hipEventRecord(s->ev_copied[s->out_sel], s->copy_stream) != hipSuccess) {
-                rc = AEC_FAIL(AEC_MEM_ERROR);
-                break;
-            }
-            pending[s->out_sel] = true;
-            s->out_sel ^= 1u;
-        } else {
-            (void)hipGetLastError();
-            if (hipMemcpy(dst, d_bytes, len, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = AEC_FAIL(AEC_MEM_ERROR);
-                break;
-            }
-        }
+        if (!s->side.copy_out(dst, d_bytes, len, true)) rc = AEC_FAIL(AEC_MEM_ERROR);
     }
     // (nothing of ours may still write the caller's buffer on return)
-    if ((pending[0] || pending[1]) && hipStreamSynchronize(s->copy_stream) != hipSuccess && rc == AEC_OK)
-        rc = AEC_FAIL(AEC_MEM_ERROR);
+    if (!s->side.done() && rc == AEC_OK) rc = AEC_FAIL(AEC_MEM_ERROR);
     if (rc != AEC_OK) return rc;
     strm->next_out += size;
     strm->avail_out -= size;
@@ -1603,10 +1361,7 @@ int aec_decode(struct aec_stream *strm, int flush)
         return decode_call(strm, flush);   // (flush is ignored by the reference, decode.c:797; here it only
                                            // says that the caller is not trickling input in)
     } catch (const std::bad_alloc &) {
-        if (strm->state->copy_pending) {       // (nothing of ours may still write the caller's buffer)
-            strm->state->copy_pending = false;
-            (void)hipStreamSynchronize(strm->state->copy_stream);
-        }
+        (void)strm->state->side.done();        // (nothing of ours may still write the caller's buffer)
         strm->total_in -= strm->avail_in;      // (added on entry, as on every other way out)
         strm->total_out -= strm->avail_out;
         return AEC_MEM_ERROR;
@@ -1690,7 +1445,10 @@ int aec_decode_range(struct aec_stream *strm, const size_t *rsi_offsets, size_t 
 {
     try {
         return decode_range_call(strm, rsi_offsets, rsi_offsets_count, pos, size);
-    } catch (const std::bad_alloc &) { return AEC_MEM_ERROR; }
+    } catch (const std::bad_alloc &) {
+        (void)strm->state->side.done();        // (nothing of ours may still write the caller's buffer)
+        return AEC_MEM_ERROR;
+    }
 }
 
 int aec_buffer_decode(struct aec_stream *strm)
