@@ -337,7 +337,7 @@ AEC_GPU_API int aec_gpu_encode_batch_async(aec_gpu_ctx *ctx, const aec_gpu_param
  * in bits, d_result->total_bits = the end of the last one, d_result->overflow = 1 if that lies beyond out_cap
  * (the sum of aec_gpu_encode_bound(chunk_bytes) always suffices).  aec_gpu_uniform_batch_ok says whether a
  * geometry can be taken this way (whole RSIs, at most 2048 segments of 64 blocks per chunk); if not, or for
- * unequal chunks, use aec_gpu_encode_batch_async.
+ * unequal chunks, use aec_gpu_encode_chunks_async below (one launch set for any batch) or aec_gpu_encode_batch_async.
  */
 typedef struct aec_gpu_batch_chunk {
     uint64_t base_bits;
@@ -348,6 +348,44 @@ AEC_GPU_API int aec_gpu_encode_uniform_batch_async(aec_gpu_ctx *ctx, const aec_g
                                                    size_t chunk_bytes, uint64_t n_chunks, void *d_out, size_t out_cap,
                                                    aec_gpu_batch_chunk *d_chunks, aec_gpu_enc_result *d_result,
                                                    void *stream);
+
+/*
+ * n_chunks UNEQUAL chunks anywhere in d_in as ONE launch set: no limit on the segments of a chunk, no whole-RSI
+ * condition.  chunk_offsets and chunk_bytes are HOST arrays of n_chunks entries (free again when the call returns):
+ * chunk i is chunk_bytes[i] bytes at d_in + chunk_offsets[i]; the offsets are multiples of 16, in any order, the chunks
+ * do not overlap, and nothing between them is read.  A trailing fraction of a sample is ignored, as aec_encode ignores
+ * it.  Every chunk is a stream of its own -- k = 0, bit 0 of its first byte, zero-padded to a byte: byte for byte what
+ * aec_buffer_encode gives for that chunk alone -- and the streams lie back to back in d_out in chunk order:
+ * d_chunks[i] = {base_bits (a multiple of 8), bits}; a chunk without a whole sample has bits = 0 and occupies one zero
+ * byte (the reference's empty stream).  d_result->total_bits = the end of the last stream, d_result->overflow = 1 if
+ * that lies beyond out_cap (a multiple of 16; d_out 16-byte aligned); nothing is written at or beyond out_cap either
+ * way, plan.out_bound always suffices, and d_out need not be cleared.
+ * d_rsi_bit_offsets (optional, plan.rsi_entries entries): for chunk i its rsi_count_i + 1 entries at index
+ * sum over j < i of (rsi_count_j + 1) -- bit positions relative to d_out, the last one the end of the chunk's stream
+ * before padding -- so aec_gpu_decode_async(d_in = d_out, table + that index, rsi_count_i, blocks_i, ...) is a round
+ * trip of chunk i without an index pass.  A segment table set with aec_gpu_set_segment_table is NOT filled by this call.
+ * The call does not synchronise the device unless one of the context's buffers has to grow.
+ * n_chunks == 0: AEC_OK, nothing is enqueued; parameters aec_gpu_check_params(p, 1) refuses: AEC_CONF_ERROR.
+ *
+ * aec_gpu_encode_chunks_plan is host arithmetic only (1 = the batch is taken, 0 = it would be refused):
+ *   out_bound        16 + the sum over the chunks of max(1, ceil(blocks_i * (id_len + block_size * bits_per_sample + 2)
+ *                    / 8)), rounded up to a multiple of 16
+ *   rsi_entries      the sum of rsi_count_i + 1
+ *   workspace_bytes  device memory the context holds for such a batch
+ *   waves            wavefronts of the analysis and of the pack kernel: the sum of ceil(segments_i / segments per wave)
+ */
+typedef struct aec_gpu_chunks_plan {
+    size_t out_bound;
+    uint64_t rsi_entries;
+    size_t workspace_bytes;
+    uint64_t waves;
+} aec_gpu_chunks_plan;
+AEC_GPU_API int aec_gpu_encode_chunks_plan(const aec_gpu_params *p, const uint64_t *chunk_bytes, uint64_t n_chunks,
+                                           aec_gpu_chunks_plan *plan);
+AEC_GPU_API int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in,
+                                            const uint64_t *chunk_offsets, const uint64_t *chunk_bytes, uint64_t n_chunks,
+                                            void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
+                                            uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result, void *stream);
 
 /*
  * Measurement hooks (bench.py): with profiling enabled the context records HIP events on the

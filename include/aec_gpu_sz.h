@@ -67,6 +67,8 @@ AEC_GPU_API int aec_gpu_sz_unmarshal_async(const SZ_com_t *sz, const void *d_cod
  *     aec_gpu_sz_marshal_async(sz, d_src, chunk_bytes, n, d_work, stream);         (skip when L.passthrough)
  *     offsets[i] = i * L.coder_bytes  (host array; chunk by chunk where coder_bytes is not a multiple of 16)
  *     aec_gpu_encode_batch_async(ctx, &L.coder, d_work, offsets, n, d_out, slot_bytes, d_results, stream);
+ * or, where coder_bytes is a multiple of 16, as one launch set for all chunks (aec_gpu.h):
+ *     aec_gpu_encode_chunks_async(ctx, &L.coder, d_work, offsets, sizes, n, d_out, cap, d_chunks, NULL, d_result, stream);
  */
 AEC_GPU_API int aec_gpu_sz_batch_ok(const SZ_com_t *sz, size_t chunk_bytes, uint64_t n_chunks);
 

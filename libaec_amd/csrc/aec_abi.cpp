@@ -1084,6 +1084,13 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
     });
 }
 
+// (AEC_ABI_TRACE) the way an encode batch takes: "uniform" (equal chunks of whole RSIs, one launch set), "chunks" (any
+// other batch of two and more, one launch set) or "loop" (chunk after chunk)
+void trace_encode_batch(const char *path, size_t n, size_t bytes)
+{
+    if (trace_on()) fprintf(stderr, "libaec (MI355X): encode batch: %zu chunks, %zu bytes on the device, path %s\n", n, bytes, path);
+}
+
 int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const *src, const size_t *src_len,
                       void *const *dst, size_t *dst_len, int *status)
 {
@@ -1111,6 +1118,7 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
         for (size_t i = 1; i < n && equal; i++) equal = src_len[i] == src_len[0];
         const size_t len = src_len[0];
         if (equal && aec_gpu_uniform_batch_ok(&gp, len, n)) {
+            trace_encode_batch("uniform", n, n * len);
             const size_t bound = up16(aec_gpu_encode_bound(&gp, len)), cap = n * bound;
             const size_t o_rec = up16(n * sizeof(aec_gpu_batch_chunk));
             if (!k.d_in.ensure(n * len + 32) || !k.d_out.ensure(cap) || !k.d_off.ensure(o_rec + 64))
@@ -1148,6 +1156,43 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
             });
         }
     }
+    const auto whole = [&](size_t i) { return src_len[i] - src_len[i] % c.bytes; };
+    const bool stage_in = n >= 16 && largest <= ((size_t)256 << 10) && stage_ensure(k, total_in < kStagePiece ? total_in : kStagePiece);
+    // Any other batch of two chunks and more: still ONE launch set (aec_gpu_encode_chunks_async) -- the chunks at their
+    // 16-byte aligned off[i] on the device, the streams back to back, one transfer each way
+    aec_gpu_chunks_plan plan;
+    std::vector<uint64_t> lens(n);
+    for (size_t i = 0; i < n; i++) lens[i] = whole(i);
+    if (n >= 2 && aec_gpu_encode_chunks_plan(&gp, lens.data(), n, &plan)) {
+        trace_encode_batch("chunks", n, total_in);
+        const size_t o_rec = up16(n * sizeof(aec_gpu_batch_chunk));
+        if (!k.d_in.ensure(total_in + 32) || !k.d_out.ensure(plan.out_bound) || !k.d_off.ensure(o_rec + 64))
+            return AEC_FAIL(AEC_MEM_ERROR);
+        aec_gpu_batch_chunk *d_chunks = static_cast<aec_gpu_batch_chunk *>(k.d_off.p);
+        aec_gpu_enc_result *d_one = reinterpret_cast<aec_gpu_enc_result *>(static_cast<uint8_t *>(k.d_off.p) + o_rec);
+        rc = stage_up(k, n, src, [&](size_t i) { return (size_t)off[i]; }, whole, stage_in ? k.h_stage_cap : 0, false, no_launch);
+        if (rc != AEC_OK) return rc;
+        rc = aec_gpu_encode_chunks_async(k.ctx, &gp, k.d_in.p, off.data(), lens.data(), n, k.d_out.p, plan.out_bound, d_chunks,
+                                         nullptr, d_one, k.stream);
+        if (rc != RC_OK) return AEC_FAIL(rc);
+        std::vector<aec_gpu_batch_chunk> rec(n);
+        aec_gpu_enc_result one{};
+        if (hipMemcpyAsync(rec.data(), d_chunks, n * sizeof(aec_gpu_batch_chunk), hipMemcpyDeviceToHost, k.stream) != hipSuccess ||
+            hipMemcpyAsync(&one, d_one, sizeof(one), hipMemcpyDeviceToHost, k.stream) != hipSuccess ||
+            batch_sync(k.stream) != hipSuccess)
+            return AEC_FAIL(AEC_MEM_ERROR);
+        if (one.overflow) return AEC_FAIL(AEC_MEM_ERROR);                         // (cannot happen: cap is the plan's bound)
+        const size_t total = (size_t)(one.total_bits / 8);
+        const bool staged = stage_ensure(k, total < kStagePiece ? (total ? total : 16) : kStagePiece);
+        const auto ext = [&](size_t i) { return rec[i].bits ? (size_t)((rec[i].bits + 7) / 8) : (size_t)1; };   // an empty stream is one zero byte
+        return stage_down(k, n, dst, dst_len, status, [&](size_t i) { return (size_t)(rec[i].base_bits / 8); }, ext,
+                          staged ? k.h_stage_cap : 0, false, [&](size_t i, int *st) {
+            if (ext(i) <= dst_len[i]) return ext(i);
+            *st = AEC_STREAM_ERROR;                                                         // as aec_buffer_encode: a prefix
+            return dst_len[i];
+        });
+    }
+    trace_encode_batch("loop", n, total_in);
     const size_t slot = aec_gpu_encode_bound(&gp, largest);
     if (!k.d_in.ensure(total_in + 32) || !k.d_out.ensure(n * slot) || !k.d_off.ensure(n * sizeof(aec_gpu_enc_result) + 64))
         return AEC_FAIL(AEC_MEM_ERROR);
@@ -1156,8 +1201,6 @@ int encode_batch_host(const struct aec_stream *prm, size_t n, const void *const 
     // and coding alternating so that the kernels of one chunk run while the host stages the next one's copy.
     aec_gpu_enc_result *d_res = static_cast<aec_gpu_enc_result *>(k.d_off.p);
     if (aec_gpu_reserve(k.ctx, &gp, largest) != RC_OK) return AEC_FAIL(AEC_MEM_ERROR);
-    const bool stage_in = n >= 16 && largest <= ((size_t)256 << 10) && stage_ensure(k, total_in < kStagePiece ? total_in : kStagePiece);
-    const auto whole = [&](size_t i) { return src_len[i] - src_len[i] % c.bytes; };
     rc = stage_up(k, n, src, [&](size_t i) { return (size_t)off[i]; }, whole, stage_in ? k.h_stage_cap : 0, false, [&](size_t i) {
         const uint64_t pair[2] = {off[i], off[i] + whole(i)};
         const int erc = aec_gpu_encode_batch_async(k.ctx, &gp, k.d_in.p, pair, 1, static_cast<uint8_t *>(k.d_out.p) + i * slot, slot,

@@ -18,6 +18,10 @@
 //               coalesced byte-swapped copy to HBM; only the first/last word of a segment can be
 //               shared with a neighbour and uses a global atomic OR.
 //
+//   k_analyze_chunks / k_pack_chunks   the same bodies (aec_enc_analyze.inc / aec_enc_pack.inc) behind a prologue that
+//               gives a wave ONE chunk of a batch of unequal chunks; k_chunks_* is the scan that restarts at every
+//               chunk (aec_chunks.h).
+//
 // HBM traffic per input byte: 2 reads of the input + 4/(bs*bytes) summary write+read
 // + 1 write of the compressed stream.  Algorithmic bytes are N + C.
 //
@@ -25,6 +29,7 @@
 // block size: objects aec_enc_bs<N>.o) and once without (scans, batch kernels, dispatch), as aec_dec.hip is.
 #include <hip/hip_runtime.h>
 
+#include "aec_chunks.h"
 #include "aec_kernels.h"
 #include "aec_lane.h"
 #include "aec_tune.h"
@@ -45,6 +50,9 @@ template <int BS> void enc_part(bool pack, const Cfg &c, const uint8_t *in, cons
 template <int BS> void enc_part_fused(const Cfg &c, const uint8_t *in, uint32_t *out_words, uint64_t cap_words,
                                       const FusedGeom &g, void *ctl, uint32_t start_bit, uint32_t k_in, uint64_t *rsi_off,
                                       SegEntry *seg_table, EncResult *res, uint32_t fast_ok, hipStream_t st);
+
+template <int BS> void enc_part_chunks(bool pack, const Cfg &c, const uint8_t *in, const ChunksLaunch &k, const EncWorkspace &ws,
+                                       uint32_t *out_words, uint64_t cap_words, uint32_t fast_ok, hipStream_t st);
 
 namespace {
 
@@ -704,48 +712,55 @@ k_analyze(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict__ me
           uint32_t *__restrict__ seg_bits, uint16_t *__restrict__ seg_clamp, uint32_t segs_per_wave,
           uint32_t fast_ok)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: segment geometry and addresses then run on the SALU)
-    const uint32_t bs = BS ? (uint32_t)BS : c.bs;
-    const uint32_t stride = Rows<BS, BYTES>::stride_words(bs);
-    uint32_t *rows = smem + (size_t)wave * 64u * stride;
+#define AEC_WAVE_INDEX ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wave)
+#include "aec_enc_analyze.inc"
+#undef AEC_WAVE_INDEX
+}
 
-    const uint64_t gwave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    uint64_t sg = gwave * segs_per_wave;
-    uint64_t sg_end = sg + segs_per_wave;
-    if (sg_end > c.total_segs) sg_end = c.total_segs;
+// A wavefront of a batch of unequal chunks (aec_chunks.h): its chunk from the per-wave table that k_chunks_setup wrote,
+// then the chunk's counts, input and array bases in scalar registers -- the body then runs on the chunk as on an input of
+// its own.  A chunk has ceil(segs / segs_per_wave) waves, so no wave works across a chunk border.
+struct ChunkWave {
+    Cfg c;
+    const uint8_t *in;
+    uint64_t blk0, seg0, wave;      // bases in the workspace arrays, wave number inside the chunk
+};
+__device__ __forceinline__ ChunkWave chunk_wave(const Cfg &call, const uint8_t *d_in, const ChunkDesc *__restrict__ desc,
+                                                const uint32_t *__restrict__ wave_chunk, uint64_t gwave)
+{
+    const uint32_t ci = __builtin_amdgcn_readfirstlane(wave_chunk[gwave]);
+    const ChunkDesc d = desc[ci], next = desc[ci + 1];     // (the prefix sums of the next one give this one's counts)
+    ChunkWave w;
+    w.c = call;
+    w.c.total_samples = d.samples;
+    w.c.total_blocks = next.blk0 - d.blk0;
+    w.c.total_segs = next.seg0 - d.seg0;
+    w.c.rsi_count = next.rsi0 - d.rsi0 - 1;
+    w.in = d_in + d.in_off;
+    w.blk0 = d.blk0;
+    w.seg0 = d.seg0;
+    w.wave = gwave - d.wave0;
+    return w;
+}
 
-    Feeder<BS, BYTES> feeder;
-    feeder.init(c, fast_ok);
-    Seg g = seg_geom(c, sg < sg_end ? sg : 0);
-    if (Feeder<BS, BYTES>::DIRECT) {
-        // small blocks: lane = block from the load on, nothing goes through the rows (Feeder::DIRECT)
-        if (sg < sg_end) feeder.prefetch_direct(c, in, g, lane);
-        for (; sg < sg_end; sg++) {
-            const auto cur = feeder.pre_direct;
-            const Seg gcur = g;
-            if (sg + 1 < sg_end) g = seg_next(c, g);
-            feeder.prefetch_direct(c, in, g, lane);       // the next segment's loads fly during this one
-            if (feeder.direct_ok(c, gcur)) {
-                uint32_t w[BS ? BS / 2 : 1];
-                direct_finish<(Feeder<BS, BYTES>::DIRECT ? BS : 8), (Feeder<BS, BYTES>::DIRECT ? BYTES : 1)>(c, gcur, cur, lane, w);
-                analyze_body<BS, BYTES>(c, gcur, rows, stride, lane, sg, meta, seg_bits, seg_clamp, w);
-            } else {
-                feeder.feed_now(c, in, gcur, rows, stride, lane);
-                analyze_body<BS, BYTES>(c, gcur, rows, stride, lane, sg, meta, seg_bits, seg_clamp);
-            }
-        }
-        return;
-    }
-    if (sg < sg_end) feeder.prefetch(c, in, g, lane);
-    for (; sg < sg_end; sg++) {
-        const auto cur = feeder.pre;
-        const Seg gcur = g;
-        if (sg + 1 < sg_end) g = seg_next(c, g);
-        feeder.prefetch(c, in, g, lane);          // next segment's loads fly during this one
-        feeder.feed(c, in, gcur, cur, rows, stride, lane);
-        analyze_body<BS, BYTES>(c, gcur, rows, stride, lane, sg, meta, seg_bits, seg_clamp);
-    }
+template <int BS, int BYTES>
+__global__ void __launch_bounds__(256)
+k_analyze_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDesc *__restrict__ desc,
+                 const uint32_t *__restrict__ wave_chunk, uint64_t nwaves, uint32_t *__restrict__ meta_all,
+                 uint32_t *__restrict__ seg_bits_all, uint16_t *__restrict__ seg_clamp_all, uint32_t segs_per_wave,
+                 uint32_t fast_ok)
+{
+    const uint64_t gw = (uint64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (gw >= nwaves) return;
+    const ChunkWave cw = chunk_wave(call, d_in, desc, wave_chunk, gw);
+    const Cfg &c = cw.c;
+    const uint8_t *__restrict__ in = cw.in;
+    uint32_t *__restrict__ meta = meta_all + cw.blk0;
+    uint32_t *__restrict__ seg_bits = seg_bits_all + cw.seg0;
+    uint16_t *__restrict__ seg_clamp = seg_clamp_all + cw.seg0;
+#define AEC_WAVE_INDEX cw.wave
+#include "aec_enc_analyze.inc"
+#undef AEC_WAVE_INDEX
 }
 
 // Phase B of one segment (rows already in LDS): this lane's block summary (meta_pack), the segment's
@@ -1068,6 +1083,154 @@ k_batch_apply(const uint32_t *__restrict__ seg_bits, const uint16_t *__restrict_
     }
 }
 
+// ---- a batch of UNEQUAL chunks as one launch set (aec_chunks.h) ---------------------------------------------------------
+// The segmented scan over tiles of kScanChunk segments of the concatenated numbering: three launches like the scans
+// above, a chunk may span any number of tiles and a tile any number of chunks.
+__device__ __forceinline__ CkVal ck_shfl_up(CkVal v, uint32_t o)
+{
+    CkVal t;
+    t.bits = __shfl_up((unsigned long long)v.bits, o);
+    t.cl = __shfl_up(v.cl, o);
+    t.head = __shfl_up(v.head, o);
+    return t;
+}
+// block_excl_scan for the restarting operator
+__device__ __forceinline__ CkVal block_excl_scan_ck(CkVal v, CkVal &total, CkVal *sh /*[4]*/)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    CkVal inc = v;
+#pragma unroll
+    for (uint32_t o = 1; o < kWave; o <<= 1) {
+        const CkVal t = ck_shfl_up(inc, o);
+        if (lane >= o) inc = ck_then(t, inc);
+    }
+    if (lane == 63) sh[wave] = inc;
+    __syncthreads();
+    CkVal wprefix = ck_identity();
+    for (uint32_t w = 0; w < wave; w++) wprefix = ck_then(wprefix, sh[w]);
+    total = ck_identity();
+    for (uint32_t w = 0; w < (blockDim.x >> 6); w++) total = ck_then(total, sh[w]);
+    CkVal exc = ck_shfl_up(inc, 1);
+    if (lane == 0) exc = ck_identity();
+    __syncthreads();
+    return ck_then(wprefix, exc);
+}
+
+// the per-wave table of the chunk kernels (4 bytes per wave), and the chunk totals cleared for k_chunks_reduce
+__global__ void __launch_bounds__(256)
+k_chunks_setup(const ChunkDesc *__restrict__ desc, uint64_t n, uint64_t nwaves, uint32_t *__restrict__ wave_chunk,
+               BatchChunk *__restrict__ chunks)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwaves || i < n; i += stride) {
+        if (i < nwaves) wave_chunk[i] = (uint32_t)chunk_of_wave(desc, n, i);
+        if (i < n) chunks[i] = BatchChunk{0, 0};
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_chunks_reduce(const ChunkDesc *__restrict__ desc, uint64_t n, const uint32_t *__restrict__ seg_bits,
+                const uint16_t *__restrict__ seg_clamp, uint64_t nseg, CkVal *__restrict__ tiles,
+                BatchChunk *__restrict__ chunks)
+{
+    __shared__ CkVal sh[4];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kScanChunk;
+    const uint64_t tile_end = tile0 + kScanChunk < nseg ? tile0 + kScanChunk : nseg;
+    uint64_t s0 = tile0 + (uint64_t)threadIdx.x * kScanItems, s1 = s0 + kScanItems;
+    if (s0 > tile_end) s0 = tile_end;
+    if (s1 > tile_end) s1 = tile_end;
+    const CkVal acc = ck_reduce_items(desc, n, seg_bits, seg_clamp, s0, s1);
+    CkVal total;
+    const CkVal run = block_excl_scan_ck(acc, total, sh);
+    ck_flush_totals(desc, n, seg_bits, seg_clamp, s0, s1, tile_end, run, [&](uint64_t chunk, uint64_t bits) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(&chunks[chunk].bits), (unsigned long long)bits);
+    });
+    if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+}
+
+// one workgroup: the chunks' bases from their totals, the empty chunks' byte and table entry, the tile carries
+__global__ void __launch_bounds__(256)
+k_chunks_bases(const ChunkDesc *__restrict__ desc, BatchChunk *chunks, uint64_t n, CkVal *tiles, uint64_t ntiles,
+               uint8_t *__restrict__ out, uint64_t cap_bytes, uint64_t *__restrict__ rsi_off, EncResult *res)
+{
+    __shared__ ScanVal sh[4];
+    __shared__ CkVal shc[4];
+    const uint64_t per = (n + 255) / 256;
+    const uint64_t lo = (uint64_t)threadIdx.x * per < n ? (uint64_t)threadIdx.x * per : n;
+    const uint64_t hi = lo + per < n ? lo + per : n;
+    ScanVal acc = scan_identity();
+    for (uint64_t i = lo; i < hi; i++) acc.bits += chunk_stream_bytes(chunks[i].bits);
+    ScanVal total;
+    ScanVal run = block_excl_scan(acc, total, sh);
+    for (uint64_t i = lo; i < hi; i++) {
+        uint64_t base_bits;
+        const uint64_t before = run.bits;
+        run.bits = ck_base(run.bits, chunks[i].bits, &base_bits);
+        chunks[i].base_bits = base_bits;
+        if (desc[i + 1].seg0 == desc[i].seg0) {       // an empty chunk: no segment, so nobody else writes for it
+            if (before < cap_bytes) out[before] = 0;
+            if (rsi_off) rsi_off[desc[i].rsi0] = base_bits;
+        }
+    }
+    if (threadIdx.x == 0) {
+        res->total_bits = total.bits * 8;
+        res->k_out = 0;
+        res->overflow = total.bits > cap_bytes ? 1u : 0u;
+        res->k_lo = 0;
+        res->k_hi = 0;
+    }
+    // exclusive scan of the tile aggregates in place: what the chunk open at a tile's start has in front of the tile
+    const uint64_t tper = (ntiles + 255) / 256;
+    const uint64_t tlo = (uint64_t)threadIdx.x * tper < ntiles ? (uint64_t)threadIdx.x * tper : ntiles;
+    const uint64_t thi = tlo + tper < ntiles ? tlo + tper : ntiles;
+    CkVal tacc = ck_identity();
+    for (uint64_t t = tlo; t < thi; t++) tacc = ck_then(tacc, tiles[t]);
+    CkVal ttotal;
+    CkVal trun = block_excl_scan_ck(tacc, ttotal, shc);
+    for (uint64_t t = tlo; t < thi; t++) {
+        const CkVal cur = tiles[t];
+        tiles[t] = trun;
+        trun = ck_then(trun, cur);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_chunks_apply(const ChunkDesc *__restrict__ desc, uint64_t n, const uint32_t *__restrict__ seg_bits,
+               const uint16_t *__restrict__ seg_clamp, uint64_t nseg, const CkVal *__restrict__ tiles,
+               const BatchChunk *__restrict__ chunks, uint32_t segs_per_rsi, uint32_t segs_per_wave,
+               uint64_t *__restrict__ seg_start, uint8_t *__restrict__ seg_kin, uint64_t *__restrict__ rsi_off,
+               uint32_t *__restrict__ out_words, uint64_t cap_words)
+{
+    __shared__ CkVal sh[4];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kScanChunk;
+    const uint64_t tile_end = tile0 + kScanChunk < nseg ? tile0 + kScanChunk : nseg;
+    uint64_t s0 = tile0 + (uint64_t)threadIdx.x * kScanItems, s1 = s0 + kScanItems;
+    if (s0 > tile_end) s0 = tile_end;
+    if (s1 > tile_end) s1 = tile_end;
+    const CkVal acc = ck_reduce_items(desc, n, seg_bits, seg_clamp, s0, s1);
+    CkVal total;
+    CkVal run = block_excl_scan_ck(acc, total, sh);
+    run = ck_then(tiles[blockIdx.x], run);
+    if (s0 >= s1) return;
+    CkCursor cur = ck_cursor(desc, n, s0);
+    for (uint64_t s = s0; s < s1; s++) {
+        ck_advance(desc, n, s, cur);
+        const CkVal item = ck_item(desc, cur, s, seg_bits[s], seg_clamp[s]);
+        const CkSeg g = ck_segment(desc, cur, s, run, item, chunks[cur.chunk].base_bits, segs_per_rsi, segs_per_wave);
+        seg_start[s] = g.start;
+        seg_kin[s] = (uint8_t)g.kin;
+        if (rsi_off && g.first_rsi) rsi_off[g.rsi_entry] = g.start;
+        // (as k_scan_apply: the word a wave's first segment starts in is shared with its neighbour ...
+        if (g.wave_first && (g.start >> 5) < cap_words) out_words[g.start >> 5] = 0u;
+        if (g.last) {                                  // ... and the chunk's open last word, + one: its byte padding)
+            if (rsi_off) rsi_off[g.rsi_entry_end] = g.end;
+            for (uint64_t w = g.end >> 5; w <= (g.end >> 5) + 1; w++)
+                if (w < cap_words) out_words[w] = 0u;
+        }
+        run = ck_then(run, item);
+    }
+}
+
 // segment table for segment-parallel decoding: start bit + preceding raw sample per segment
 __global__ void __launch_bounds__(256)
 k_seg_table(const Cfg c, const uint8_t *__restrict__ in, const uint64_t *__restrict__ seg_start,
@@ -1164,115 +1327,30 @@ k_pack(const Cfg c, const uint8_t *__restrict__ in, const uint32_t *__restrict__
        uint32_t *__restrict__ out_words, uint64_t cap_words, uint32_t segs_per_wave, uint32_t obuf_words,
        uint32_t fast_ok)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: segment geometry and addresses then run on the SALU)
-    const uint32_t bs = BS ? (uint32_t)BS : c.bs;
-    const uint32_t stride = Rows<BS, BYTES>::stride_words(bs);
-    const uint32_t per_wave = 64u * stride + obuf_words;
-    uint32_t *rows = smem + (size_t)wave * per_wave;
-    uint32_t *obuf = rows + 64u * stride;
-    const bool pp = c.flags & F_PREPROCESS, msb = c.flags & F_MSB;
+#define AEC_WAVE_INDEX ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wave)
+#include "aec_enc_pack.inc"
+#undef AEC_WAVE_INDEX
+}
 
-    const uint64_t gwave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    uint64_t sg = gwave * segs_per_wave;
-    uint64_t sg_end = sg + segs_per_wave;
-    if (sg_end > c.total_segs) sg_end = c.total_segs;
-
-    Feeder<BS, BYTES> feeder;
-    feeder.init(c, fast_ok);
-    Seg gnext = seg_geom(c, sg < sg_end ? sg : 0);
-    if (sg < sg_end) {
-        if (Feeder<BS, BYTES>::DIRECT) feeder.prefetch_direct(c, in, gnext, lane);
-        else feeder.prefetch(c, in, gnext, lane);
-    }
-    uint32_t pending = 0;        // open tail word of the previous segment (stream bit order)
-    bool first_seg = true, carried_shared = false;
-    // the image buffer starts out zero and every word is zeroed again when it is copied out
-    for (uint32_t w = lane; w < obuf_words; w += kWave) obuf[w] = 0u;
-
-    // what a segment needs from HBM besides its samples
-    struct SegIn {
-        uint32_t m, kin, ref_sample;
-        uint64_t start;
-    };
-    auto seg_in = [&](const Seg &g, uint64_t sgi) {
-        SegIn r;
-        r.m = lane < g.nv ? meta[g.blk0 + lane] : meta_pack(0, OPT_ZCONT, 0, 0);
-        r.kin = seg_kin[sgi];
-        r.start = seg_start[sgi];
-        r.ref_sample = 0;
-        if (pp && g.b0 == 0 && lane == 0)
-            r.ref_sample = load_sample_bytes(in + g.samp0 * c.bytes, c.bytes, msb) & low_mask32(c.bps);
-        return r;
-    };
-    // emission of one segment from its rows and copy-out of the image
-    auto do_segment = [&](const Seg &g, const uint32_t *seg_rows, const SegIn &si, uint64_t sgi, const uint32_t *direct) {
-        const uint32_t lead = (uint32_t)(si.start & 31u);
-        uint32_t total;
-        emit_segment<BS, BYTES>(c, g, seg_rows, stride, obuf, lane, si.m, si.kin, lead, si.ref_sample, pending, total, direct);
-        const uint32_t nwords = (lead + total + 31u) >> 5;
-
-        // Copy the image out.  Only a word this wave does not own alone needs an atomic: the first
-        // word of the wave's first segment (shared with the previous wave) and the open tail word of
-        // its last segment.  An open tail in between is carried to the next segment in `pending`.
-        const uint64_t gw = si.start >> 5;
-        const uint32_t tail = (lead + total) & 31u;
-        const bool last_seg = sgi + 1 == sg_end;
-        const bool carry_tail = tail != 0 && !last_seg && nwords > 0;
-        // word 0 also holds bits of another wave only in the wave's first segment, or when a one-word
-        // segment carried that word along
-        const bool left_shared = first_seg ? lead != 0 : carried_shared;
-        const uint32_t tail_word = carry_tail ? obuf[nwords - 1] : 0u;   // uniform: every lane reads the same word
-        for (uint32_t w = lane; w < nwords; w += kWave) {
-            const uint32_t v = obuf[w];
-            obuf[w] = 0u;
-            const uint64_t idx = gw + w;
-            const bool is_tail = w == nwords - 1 && tail != 0;
-            if (idx < cap_words && !(is_tail && carry_tail)) {
-                const bool shared = (w == 0 && left_shared) || is_tail;
-                const uint32_t sv = bswap32(v);
-                if (!shared)
-                    out_words[idx] = sv;                 // (zero words too: nothing clears the buffer)
-                else if (v != 0)
-                    __hip_atomic_fetch_or(&out_words[idx], sv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        pending = tail_word;
-        carried_shared = carry_tail && nwords == 1 && left_shared;
-        first_seg = false;
-        wave_lds_fence();
-    };
-
-    if (Feeder<BS, BYTES>::DIRECT) {
-        // small blocks: lane = block from the load on, nothing goes through the rows (Feeder::DIRECT)
-        for (; sg < sg_end; sg++) {
-            const auto cur = feeder.pre_direct;
-            const Seg g = gnext;
-            const SegIn si = seg_in(g, sg);
-            if (sg + 1 < sg_end) gnext = seg_next(c, gnext);
-            feeder.prefetch_direct(c, in, gnext, lane);   // the next segment's loads fly during this one
-            if (feeder.direct_ok(c, g)) {
-                uint32_t w[BS ? BS / 2 : 1];
-                direct_finish<(Feeder<BS, BYTES>::DIRECT ? BS : 8), (Feeder<BS, BYTES>::DIRECT ? BYTES : 1)>(c, g, cur, lane, w);
-                do_segment(g, rows, si, sg, w);
-            } else {
-                feeder.feed_now(c, in, g, rows, stride, lane);
-                do_segment(g, rows, si, sg, nullptr);
-            }
-        }
-        return;
-    }
-    for (; sg < sg_end; sg++) {
-        const auto cur = feeder.pre;
-        const Seg g = gnext;
-        // everything this segment needs from HBM is requested before the first wait (requesting the
-        // summaries a segment ahead as well was tried: no gain, two registers too many)
-        const SegIn si = seg_in(g, sg);
-        if (sg + 1 < sg_end) gnext = seg_next(c, gnext);
-        feeder.prefetch(c, in, gnext, lane);      // next segment's loads fly during this one
-        feeder.feed(c, in, g, cur, rows, stride, lane);
-        do_segment(g, rows, si, sg, nullptr);
-    }
+template <int BS, int BYTES>
+__global__ void __launch_bounds__(256)
+k_pack_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDesc *__restrict__ desc,
+              const uint32_t *__restrict__ wave_chunk, uint64_t nwaves, const uint32_t *__restrict__ meta_all,
+              const uint64_t *__restrict__ seg_start_all, const uint8_t *__restrict__ seg_kin_all,
+              uint32_t *__restrict__ out_words, uint64_t cap_words, uint32_t segs_per_wave, uint32_t obuf_words,
+              uint32_t fast_ok)
+{
+    const uint64_t gw = (uint64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (gw >= nwaves) return;
+    const ChunkWave cw = chunk_wave(call, d_in, desc, wave_chunk, gw);
+    const Cfg &c = cw.c;
+    const uint8_t *__restrict__ in = cw.in;
+    const uint32_t *__restrict__ meta = meta_all + cw.blk0;
+    const uint64_t *__restrict__ seg_start = seg_start_all + cw.seg0;
+    const uint8_t *__restrict__ seg_kin = seg_kin_all + cw.seg0;
+#define AEC_WAVE_INDEX cw.wave
+#include "aec_enc_pack.inc"
+#undef AEC_WAVE_INDEX
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1669,6 +1747,21 @@ void launch_pack_t(const Cfg &c, const uint8_t *in, const EncWorkspace &ws, uint
                        g.obuf_words, fast_ok);
 }
 
+template <int BS, int BYTES>
+void launch_chunks_t(bool pack, const Cfg &c, const uint8_t *in, const ChunksLaunch &k, const EncWorkspace &ws,
+                     uint32_t *out_words, uint64_t cap_words, uint32_t fast_ok, hipStream_t st)
+{
+    const LaunchGeom g = make_geom(c, pack);
+    const uint32_t grid = (uint32_t)((k.nwaves + g.waves_per_block - 1) / g.waves_per_block);
+    if (pack)
+        hipLaunchKernelGGL((k_pack_chunks<BS, BYTES>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, c, in,
+                           k.desc, k.wave_chunk, k.nwaves, ws.meta, ws.seg_start, ws.seg_kin, out_words, cap_words,
+                           k.segs_per_wave, g.obuf_words, fast_ok);
+    else
+        hipLaunchKernelGGL((k_analyze_chunks<BS, BYTES>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, c, in,
+                           k.desc, k.wave_chunk, k.nwaves, ws.meta, ws.seg_bits, ws.seg_clamp, k.segs_per_wave, fast_ok);
+}
+
 template <int BS>
 void dispatch_bytes(bool pack, const Cfg &c, const uint8_t *in, const EncWorkspace &ws,
                     uint32_t *out_words, uint64_t cap_words, uint32_t fast_ok, hipStream_t st)
@@ -1790,6 +1883,23 @@ void enc_part_fused(const Cfg &c, const uint8_t *in, uint32_t *out_words, uint64
 }
 template void enc_part<AEC_ENC_PART>(bool, const Cfg &, const uint8_t *, const EncWorkspace &, uint32_t *, uint64_t, uint32_t,
                                      hipStream_t);
+template <int BS>
+void enc_part_chunks(bool pack, const Cfg &c, const uint8_t *in, const ChunksLaunch &k, const EncWorkspace &ws, uint32_t *out_words,
+                     uint64_t cap_words, uint32_t fast_ok, hipStream_t st)
+{
+    if constexpr (BS == 0) {
+        launch_chunks_t<0, 0>(pack, c, in, k, ws, out_words, cap_words, 0, st);
+    } else {
+        switch (c.bytes) {
+        case 1: launch_chunks_t<BS, 1>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+        case 2: launch_chunks_t<BS, 2>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+        case 3: launch_chunks_t<BS, 3>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+        default: launch_chunks_t<BS, 4>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+        }
+    }
+}
+template void enc_part_chunks<AEC_ENC_PART>(bool, const Cfg &, const uint8_t *, const ChunksLaunch &, const EncWorkspace &,
+                                            uint32_t *, uint64_t, uint32_t, hipStream_t);
 #if AEC_ENC_PART != 0
 template void enc_part_fused<AEC_ENC_PART>(const Cfg &, const uint8_t *, uint32_t *, uint64_t, const FusedGeom &, void *,
                                            uint32_t, uint32_t, uint64_t *, SegEntry *, EncResult *, uint32_t, hipStream_t);
@@ -1806,6 +1916,24 @@ AEC_ENC_EXTERN(0) AEC_ENC_EXTERN(8) AEC_ENC_EXTERN(16) AEC_ENC_EXTERN(32) AEC_EN
                                             uint32_t, uint32_t, uint64_t *, SegEntry *, EncResult *, uint32_t, hipStream_t);
 AEC_ENC_EXTERN(8) AEC_ENC_EXTERN(16) AEC_ENC_EXTERN(32) AEC_ENC_EXTERN(64)
 #undef AEC_ENC_EXTERN
+
+#define AEC_ENC_EXTERN(BS)                                                                                                  \
+    extern template void enc_part_chunks<BS>(bool, const Cfg &, const uint8_t *, const ChunksLaunch &, const EncWorkspace &, \
+                                             uint32_t *, uint64_t, uint32_t, hipStream_t);
+AEC_ENC_EXTERN(0) AEC_ENC_EXTERN(8) AEC_ENC_EXTERN(16) AEC_ENC_EXTERN(32) AEC_ENC_EXTERN(64)
+#undef AEC_ENC_EXTERN
+
+static void dispatch_chunks(bool pack, const Cfg &c, const uint8_t *in, const ChunksLaunch &k, const EncWorkspace &ws,
+                            uint32_t *out_words, uint64_t cap_words, uint32_t fast_ok, hipStream_t st)
+{
+    switch (c.bs) {
+    case 8: enc_part_chunks<8>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+    case 16: enc_part_chunks<16>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+    case 32: enc_part_chunks<32>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+    case 64: enc_part_chunks<64>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+    default: enc_part_chunks<0>(pack, c, in, k, ws, out_words, cap_words, fast_ok, st); break;
+    }
+}
 
 static void dispatch(bool pack, const Cfg &c, const uint8_t *in, const EncWorkspace &ws, uint32_t *out_words,
                      uint64_t cap_words, uint32_t fast_ok, hipStream_t st)
@@ -1938,6 +2066,45 @@ void launch_encode_uniform_batch(const Cfg &c, const uint8_t *d_in, uint64_t seg
     hipLaunchKernelGGL(k_batch_apply, dim3(n), dim3(256), 0, st, ws.seg_bits, ws.seg_clamp, (uint32_t)segs_per_chunk,
                        d_chunks, ws.seg_start, ws.seg_kin, out_words, cap_words, make_geom(c, true).segs_per_wave);
     dispatch(true, c, d_in, ws, out_words, cap_words, fast_ok, st);
+}
+
+// c describes the sum of the chunks (total_blocks, total_segs, rsi_count summed over them)
+uint32_t chunks_segs_per_wave(const Cfg &c)
+{
+    const uint32_t force = tune("AEC_CHUNKS_SPW", 0);          // (tuning build: every value at a small total)
+    if (force == 1 || force == 2 || force == 4 || force == 8) return force;
+    return make_geom(c, true).segs_per_wave;
+}
+
+void launch_encode_chunks(const Cfg &c, const uint8_t *d_in, const ChunksLaunch &k, uint8_t *d_out, size_t out_cap,
+                          const EncWorkspace &ws, BatchChunk *d_chunks, uint64_t *d_rsi_off, EncResult *d_res, hipStream_t st)
+{
+    static_assert(sizeof(CkVal) == sizeof(ScanPartial), "the tile aggregates live where the scan partials do");
+    uint32_t *out_words = reinterpret_cast<uint32_t *>(d_out);
+    const uint64_t cap_words = out_cap / 4;
+    const uint64_t nseg = c.total_segs, ntiles = (nseg + kScanChunk - 1) / kScanChunk;
+    CkVal *tiles = reinterpret_cast<CkVal *>(ws.partials);
+    // (chunk offsets are multiples of 16, so a chunk's segments start on 16-byte boundaries as a single input's do)
+    const uint32_t fast_ok = ((reinterpret_cast<uintptr_t>(d_in) & 15u) == 0 &&
+                              ((uint64_t)c.rsi * c.bs * c.bytes) % 16 == 0) ? 1u : 0u;
+    const uint64_t most = k.nwaves > k.n ? k.nwaves : k.n;
+    uint64_t setup_grid = (most + 255) / 256;
+    if (setup_grid > 4096) setup_grid = 4096;
+    hipLaunchKernelGGL(k_chunks_setup, dim3((uint32_t)setup_grid), dim3(256), 0, st, k.desc, k.n, k.nwaves, k.wave_chunk,
+                       d_chunks);
+    if (nseg) {
+        dispatch_chunks(false, c, d_in, k, ws, nullptr, 0, fast_ok, st);
+        hipLaunchKernelGGL(k_chunks_reduce, dim3((uint32_t)ntiles), dim3(256), 0, st, k.desc, k.n, ws.seg_bits, ws.seg_clamp,
+                           nseg, tiles, d_chunks);
+    }
+    hipLaunchKernelGGL(k_chunks_bases, dim3(1), dim3(256), 0, st, k.desc, d_chunks, k.n, tiles, ntiles, d_out,
+                       (uint64_t)out_cap, d_rsi_off, d_res);
+    if (nseg) {
+        hipLaunchKernelGGL(k_chunks_apply, dim3((uint32_t)ntiles), dim3(256), 0, st, k.desc, k.n, ws.seg_bits, ws.seg_clamp,
+                           nseg, tiles, d_chunks, c.segs_per_rsi, k.segs_per_wave, ws.seg_start, ws.seg_kin, d_rsi_off,
+                           out_words, cap_words);
+        dispatch_chunks(true, c, d_in, k, ws, out_words, cap_words, fast_ok, st);
+    }
 }
 
 #endif      // AEC_ENC_PART

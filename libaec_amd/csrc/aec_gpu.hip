@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "aec_chunks.h"
 #include "aec_kernels.h"
 
 using namespace aec;
@@ -48,6 +49,15 @@ struct aec_gpu_ctx {
     size_t fused_bytes;
     void *range_ws;        // whole blocks of a range decode whose window does not start on an RSI / end on a block
     size_t range_ws_bytes;
+    // aec_gpu_encode_chunks_async: the chunk descriptors and the per-wave table on the device, and the pinned buffers
+    // the descriptors are written to on the host -- two, taken in turn, each guarded by the event of its last transfer
+    void *chunks_d;
+    size_t chunks_d_bytes;
+    static constexpr unsigned kChunkStages = 2;
+    void *chunks_h[kChunkStages];
+    size_t chunks_h_bytes[kChunkStages];
+    hipEvent_t chunks_ev[kChunkStages];
+    unsigned chunks_calls;
 };
 static_assert(sizeof(aec_gpu_seg_entry) == sizeof(SegEntry), "segment table layout");
 
@@ -88,6 +98,14 @@ int aec_gpu_create(aec_gpu_ctx **out)
     ctx->enc_calls = ctx->dec_calls = 0;
     for (auto &set : ctx->ev)
         for (auto &e : set.ev) e = nullptr;
+    ctx->chunks_d = nullptr;
+    ctx->chunks_d_bytes = 0;
+    ctx->chunks_calls = 0;
+    for (unsigned i = 0; i < aec_gpu_ctx::kChunkStages; i++) {
+        ctx->chunks_h[i] = nullptr;
+        ctx->chunks_h_bytes[i] = 0;
+        ctx->chunks_ev[i] = nullptr;
+    }
     *out = ctx;
     return RC_OK;
 }
@@ -101,6 +119,11 @@ void aec_gpu_destroy(aec_gpu_ctx *ctx)
     if (ctx->carry) (void)hipFree(ctx->carry);
     if (ctx->fused) (void)hipFree(ctx->fused);
     if (ctx->range_ws) (void)hipFree(ctx->range_ws);
+    if (ctx->chunks_d) (void)hipFree(ctx->chunks_d);
+    for (unsigned i = 0; i < aec_gpu_ctx::kChunkStages; i++) {
+        if (ctx->chunks_h[i]) (void)hipHostFree(ctx->chunks_h[i]);
+        if (ctx->chunks_ev[i]) (void)hipEventDestroy(ctx->chunks_ev[i]);
+    }
     for (auto &set : ctx->ev)
         for (auto &e : set.ev)
             if (e) (void)hipEventDestroy(e);
@@ -556,11 +579,18 @@ void aec_gpu_trim(aec_gpu_ctx *ctx, size_t keep_bytes)
         ctx->dec_ws = nullptr;
         ctx->dec_ws_bytes = 0;
     }
+    if (ctx->chunks_d && ctx->chunks_d_bytes > keep_bytes) {
+        (void)hipFree(ctx->chunks_d);
+        ctx->chunks_d = nullptr;
+        ctx->chunks_d_bytes = 0;
+    }
 }
 
 size_t aec_gpu_held_bytes(const aec_gpu_ctx *ctx)
 {
-    return ctx ? ctx->ws_bytes + ctx->fused_bytes + ctx->idx_ws_bytes + ctx->dec_ws_bytes + ctx->range_ws_bytes : 0;
+    return ctx ? ctx->ws_bytes + ctx->fused_bytes + ctx->idx_ws_bytes + ctx->dec_ws_bytes + ctx->range_ws_bytes +
+                     ctx->chunks_d_bytes
+               : 0;
 }
 
 int aec_gpu_index_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -684,6 +714,147 @@ int aec_gpu_uniform_batch_ok(const aec_gpu_params *p, size_t chunk_bytes, uint64
     if (chunk_bytes % ((size_t)one.rsi * one.bs * one.bytes)) return 0;
     if (cfg_from(p, chunk_bytes * n_chunks, true, &c) != RC_OK) return 0;
     return batch_uniform_ok(c, one.total_segs) ? 1 : 0;
+}
+
+// ---- a batch of unequal chunks as one launch set (aec_chunks.h) -------------------------------------------------------
+namespace {
+struct ChunksShape {
+    Cfg c;                  // the parameters with the sums of the chunks' samples, blocks, segments and RSIs
+    uint64_t waves, entries;
+    uint32_t spw;
+    size_t out_bound, ws_bytes, desc_bytes, table_bytes;
+};
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// host arithmetic of a batch; with desc (n + 1 entries) the descriptors are written too.  false = refused.
+bool chunks_shape(const aec_gpu_params *p, const uint64_t *offsets, const uint64_t *bytes, uint64_t n, ChunksShape *sh,
+                  ChunkDesc *desc)
+{
+    Cfg &c = sh->c;
+    if (cfg_from(p, 0, true, &c) != RC_OK || (n && !bytes) || n > 0x7FFFFFFFull) return false;
+    const uint64_t cds_bits = c.id_len + (uint64_t)c.bs * c.bps + 2;            // (max_encoded_bytes)
+    uint64_t samples = 0, blocks = 0, segs = 0, entries = 0, bound = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t smp = bytes[i] / c.bytes;                                  // a fraction of a sample is ignored
+        const ChunkCounts k = chunk_counts(smp, c.bs, c.rsi, c.segs_per_rsi);
+        if (desc) desc[i] = ChunkDesc{offsets[i], smp, blocks, segs, entries, 0};
+        samples += smp;
+        blocks += k.blocks;
+        segs += k.segs;
+        entries += k.rsis + 1;
+        const uint64_t most = (k.blocks * cds_bits + 7) / 8;
+        bound += most ? most : 1;
+        if (bound >> 48 || blocks >> 48) return false;
+    }
+    c.total_samples = samples;
+    c.total_blocks = blocks;
+    c.total_segs = segs;
+    c.rsi_count = entries - n;
+    sh->spw = chunks_segs_per_wave(c);
+    uint64_t waves = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const ChunkCounts k = chunk_counts(bytes[i] / c.bytes, c.bs, c.rsi, c.segs_per_rsi);
+        if (desc) desc[i].wave0 = waves;
+        waves += (k.segs + sh->spw - 1) / sh->spw;
+    }
+    if (waves > 0x7FFFFFFFull) return false;
+    if (desc) desc[n] = ChunkDesc{0, 0, blocks, segs, entries, waves};
+    sh->waves = waves;
+    sh->entries = entries;
+    sh->out_bound = (size_t)((bound + 15) & ~(uint64_t)15) + 16;
+    size_t o[6];
+    sh->desc_bytes = up256((size_t)(n + 1) * sizeof(ChunkDesc));
+    sh->table_bytes = up256((size_t)(waves ? waves : 1) * 4);
+    sh->ws_bytes = enc_workspace_bytes(c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]) + sh->desc_bytes + sh->table_bytes;
+    return true;
+}
+}  // namespace
+
+int aec_gpu_encode_chunks_plan(const aec_gpu_params *p, const uint64_t *chunk_bytes, uint64_t n_chunks,
+                               aec_gpu_chunks_plan *plan)
+{
+    ChunksShape sh;
+    if (!p || !plan || !chunks_shape(p, nullptr, chunk_bytes, n_chunks, &sh, nullptr)) return 0;
+    plan->out_bound = sh.out_bound;
+    plan->rsi_entries = sh.entries;
+    plan->workspace_bytes = sh.ws_bytes;
+    plan->waves = sh.waves;
+    return 1;
+}
+
+int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, const uint64_t *chunk_offsets,
+                                const uint64_t *chunk_bytes, uint64_t n_chunks, void *d_out, size_t out_cap,
+                                aec_gpu_batch_chunk *d_chunks, uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result,
+                                void *stream)
+{
+    const int prc = aec_gpu_check_params(p, 1);
+    if (prc != RC_OK) return RC_CONF_ERROR;
+    if (n_chunks == 0) return RC_OK;
+    if (!chunk_offsets || !chunk_bytes || !d_chunks || !d_result || (reinterpret_cast<uintptr_t>(d_out) & 15u) ||
+        (out_cap & 15u) || out_cap < 16)
+        return RC_CONF_ERROR;
+    for (uint64_t i = 0; i < n_chunks; i++)
+        if (chunk_offsets[i] & 15u) return RC_CONF_ERROR;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // the descriptors: written to a pinned buffer of the context (the one whose last transfer lies furthest back; its
+    // event says when that transfer has left it), then one copy to the device in stream order
+    const unsigned slot = ctx->chunks_calls++ % aec_gpu_ctx::kChunkStages;
+    const size_t h_need = (size_t)(n_chunks + 1) * sizeof(ChunkDesc);
+    if (!ctx->chunks_ev[slot] && hipEventCreateWithFlags(&ctx->chunks_ev[slot], hipEventDisableTiming) != hipSuccess) {
+        ctx->chunks_ev[slot] = nullptr;
+        (void)hipGetLastError();
+        return RC_MEM_ERROR;
+    }
+    if (ctx->chunks_h[slot] && hipEventSynchronize(ctx->chunks_ev[slot]) != hipSuccess) return RC_MEM_ERROR;
+    if (h_need > ctx->chunks_h_bytes[slot]) {
+        if (ctx->chunks_h[slot]) (void)hipHostFree(ctx->chunks_h[slot]);
+        ctx->chunks_h[slot] = nullptr;
+        ctx->chunks_h_bytes[slot] = 0;
+        const size_t want = h_need + h_need / 4 + 4096;
+        if (hipHostMalloc(&ctx->chunks_h[slot], want, hipHostMallocDefault) != hipSuccess) {
+            ctx->chunks_h[slot] = nullptr;
+            (void)hipGetLastError();
+            return RC_MEM_ERROR;
+        }
+        ctx->chunks_h_bytes[slot] = want;
+    }
+    ChunkDesc *h_desc = static_cast<ChunkDesc *>(ctx->chunks_h[slot]);
+    ChunksShape sh;
+    if (!chunks_shape(p, chunk_offsets, chunk_bytes, n_chunks, &sh, h_desc)) return RC_CONF_ERROR;
+    int rc = reserve_two_pass(ctx, sh.c);
+    if (rc != RC_OK) return rc;
+    if (sh.desc_bytes + sh.table_bytes > ctx->chunks_d_bytes) {
+        if (ctx->chunks_d) (void)hipFree(ctx->chunks_d);           // (synchronises: no kernel still reads it)
+        ctx->chunks_d = nullptr;
+        ctx->chunks_d_bytes = 0;
+        const size_t want = up256(sh.desc_bytes + sh.table_bytes + (sh.desc_bytes + sh.table_bytes) / 4);
+        if (hipMalloc(&ctx->chunks_d, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return RC_MEM_ERROR;
+        }
+        ctx->chunks_d_bytes = want;
+    }
+    (void)hipGetLastError();
+    uint8_t *cd = static_cast<uint8_t *>(ctx->chunks_d);
+    if (hipMemcpyAsync(cd, h_desc, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipEventRecord(ctx->chunks_ev[slot], st) != hipSuccess)
+        return RC_MEM_ERROR;
+    size_t o[6];
+    enc_workspace_bytes(sh.c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]);
+    uint8_t *base = static_cast<uint8_t *>(ctx->ws);
+    EncWorkspace ws{};
+    ws.meta = reinterpret_cast<uint32_t *>(base + o[0]);
+    ws.seg_bits = reinterpret_cast<uint32_t *>(base + o[1]);
+    ws.seg_clamp = reinterpret_cast<uint16_t *>(base + o[2]);
+    ws.seg_start = reinterpret_cast<uint64_t *>(base + o[3]);
+    ws.seg_kin = base + o[4];
+    ws.partials = reinterpret_cast<ScanPartial *>(base + o[5]);
+    const ChunksLaunch k{reinterpret_cast<const ChunkDesc *>(cd), reinterpret_cast<uint32_t *>(cd + sh.desc_bytes), n_chunks,
+                         sh.waves, sh.spw};
+    launch_encode_chunks(sh.c, static_cast<const uint8_t *>(d_in), k, static_cast<uint8_t *>(d_out), out_cap, ws,
+                         reinterpret_cast<BatchChunk *>(d_chunks), d_rsi_bit_offsets, reinterpret_cast<EncResult *>(d_result), st);
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
 }
 
 int aec_gpu_profile(aec_gpu_ctx *ctx, int enable)

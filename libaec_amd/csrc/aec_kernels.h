@@ -102,6 +102,22 @@ void launch_encode_uniform_batch(const Cfg &c, const uint8_t *d_in, uint64_t seg
                                  size_t out_cap, const EncWorkspace &ws, BatchChunk *d_chunks, EncResult *d_res,
                                  hipStream_t stream);
 
+// A batch of n UNEQUAL chunks anywhere in d_in as one launch set (aec_chunks.h; aec_gpu_encode_chunks_async): the same
+// layout of streams and records, d_rsi_off (optional) = every chunk's rsi_count + 1 entries one chunk after the other.
+// c: the parameters with the SUMS of the chunks' blocks, segments and RSIs; k.desc: the n + 1 descriptors on the
+// device, k.wave_chunk: room for nwaves entries; ws: sized for c (enc_workspace_bytes).
+struct ChunkDesc;
+struct ChunksLaunch {
+    const ChunkDesc *desc;
+    uint32_t *wave_chunk;
+    uint64_t n, nwaves;
+    uint32_t segs_per_wave;
+};
+uint32_t chunks_segs_per_wave(const Cfg &c);
+void launch_encode_chunks(const Cfg &c, const uint8_t *d_in, const ChunksLaunch &k, uint8_t *d_out, size_t out_cap,
+                          const EncWorkspace &ws, BatchChunk *d_chunks, uint64_t *d_rsi_off, EncResult *d_res,
+                          hipStream_t stream);
+
 // One stream over several devices (aec_shard.hip): carry-in of shard `rank` from the plan records of
 // all shards; reassembly of the gathered slices into one stream.
 void launch_shard_carry(const EncResult *d_plans, uint32_t rank, ShardCarry *d_carry, hipStream_t stream);

@@ -15,6 +15,11 @@ class Params(C.Structure):
                 ("flags", C.c_uint)]
 
 
+class ChunksPlan(C.Structure):
+    _fields_ = [("out_bound", C.c_size_t), ("rsi_entries", C.c_uint64), ("workspace_bytes", C.c_size_t),
+                ("waves", C.c_uint64)]
+
+
 SEG_ENTRY_DTYPE = np.dtype([("bit", "<u8"), ("prev", "<u4"), ("pad", "<u4")])
 ENC_RESULT_DTYPE = np.dtype([("total_bits", "<u8"), ("k_out", "<u4"), ("overflow", "<u4"),
                              ("k_lo", "<u4"), ("k_hi", "<u4")])
@@ -72,6 +77,10 @@ def _lib():
         lib.aec_gpu_uniform_batch_ok.argtypes = [pp, sz, u64]
         lib.aec_gpu_encode_uniform_batch_async.restype = C.c_int
         lib.aec_gpu_encode_uniform_batch_async.argtypes = [vp, pp, vp, sz, u64, vp, sz, vp, vp, vp]
+        lib.aec_gpu_encode_chunks_plan.restype = C.c_int
+        lib.aec_gpu_encode_chunks_plan.argtypes = [pp, vp, u64, C.POINTER(ChunksPlan)]
+        lib.aec_gpu_encode_chunks_async.restype = C.c_int
+        lib.aec_gpu_encode_chunks_async.argtypes = [vp, pp, vp, vp, vp, u64, vp, sz, vp, vp, vp, vp]
         lib.aec_gpu_index_async.restype = C.c_int
         lib.aec_gpu_index_async.argtypes = [vp, pp, vp, sz, u64, vp, u64, vp, vp]
         lib.aec_gpu_segments_per_rsi.restype = C.c_uint
@@ -124,6 +133,18 @@ def index_plan(bits_per_sample, block_size, rsi, flags, in_bytes, rsi_bits=0, st
     if n < 0:
         raise ValueError("invalid stream parameters")
     return list(ids[:n]), asked.value, large.value, used.value
+
+
+def encode_chunks_plan(bits_per_sample, block_size, rsi, flags, sizes):
+    """aec_gpu_encode_chunks_plan: host arithmetic of a batch of chunks of `sizes` bytes.  Returns the dict
+    {out_bound, rsi_entries, workspace_bytes, waves}, or None where the batch would be refused."""
+    p = Params(bits_per_sample, block_size, rsi, flags)
+    a = np.ascontiguousarray(sizes, dtype=np.uint64)
+    plan = ChunksPlan()
+    if not _lib().aec_gpu_encode_chunks_plan(C.byref(p), C.c_void_p(a.ctypes.data), a.size, C.byref(plan)):
+        return None
+    return {"out_bound": int(plan.out_bound), "rsi_entries": int(plan.rsi_entries),
+            "workspace_bytes": int(plan.workspace_bytes), "waves": int(plan.waves)}
 
 
 class Codec:
@@ -325,6 +346,46 @@ class Codec:
         if res["overflow"]:
             raise RuntimeError("encode overflow")
         return d_out, rec
+
+    def encode_chunks_plan(self, sizes):
+        return encode_chunks_plan(self.p.bits_per_sample, self.p.block_size, self.p.rsi, self.p.flags, sizes)
+
+    def encode_chunks_async(self, d_in, offsets, sizes, d_out, out_cap, d_records, d_table, d_result, stream=None):
+        """aec_gpu_encode_chunks_async as it is: offsets / sizes are uint64 numpy arrays on the host, d_records an int64
+        tensor of 2 n entries, d_table an int64 tensor of the plan's rsi_entries (or None), d_result 24 bytes"""
+        rc = self.lib.aec_gpu_encode_chunks_async(
+            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), C.c_void_p(offsets.ctypes.data),
+            C.c_void_p(sizes.ctypes.data), int(sizes.size), C.c_void_p(d_out.data_ptr()), out_cap,
+            C.c_void_p(d_records.data_ptr()), C.c_void_p(d_table.data_ptr()) if d_table is not None else None,
+            C.c_void_p(d_result.data_ptr()), self._stream(stream))
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_encode_chunks_async failed ({rc})")
+
+    def encode_chunks(self, d_in, offsets, sizes, want_offsets=False, out_cap=None, d_out=None):
+        """Chunks of sizes[i] bytes at byte offsets[i] (multiples of 16) of d_in, each a stream of its own, as one launch
+        set (include/aec_gpu.h: aec_gpu_encode_chunks_async).  Returns (d_out, records, d_table, result): records[i] =
+        (base_bits, bits) of stream i inside d_out, d_table the int64 RSI table (plan rsi_entries entries; None unless
+        want_offsets), result the ENC_RESULT_DTYPE record (overflow is reported there, not raised).  out_cap / d_out:
+        a capacity or a buffer of the caller's instead of the plan's bound.  Synchronises."""
+        torch = self.torch
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        siz = np.ascontiguousarray(sizes, dtype=np.uint64)
+        if off.size != siz.size:
+            raise ValueError("offsets and sizes differ in length")
+        plan = self.encode_chunks_plan(siz)
+        if plan is None:
+            raise ValueError("aec_gpu_encode_chunks_plan refuses this batch")
+        n = int(siz.size)
+        cap = plan["out_bound"] if out_cap is None else out_cap
+        if d_out is None:
+            d_out = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+        d_rec = torch.zeros(max(n, 1) * 2, dtype=torch.int64, device=d_in.device)
+        d_tab = torch.zeros(max(plan["rsi_entries"], 1), dtype=torch.int64, device=d_in.device) if want_offsets else None
+        d_res = torch.zeros(ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
+        self.encode_chunks_async(d_in, off, siz, d_out, cap, d_rec, d_tab, d_res)
+        rec = d_rec.cpu().numpy().reshape(-1, 2)[:n]
+        res = d_res.cpu().numpy().view(ENC_RESULT_DTYPE)[0]
+        return d_out, rec, d_tab, res
 
     # ---- convenience (synchronising) -------------------------------------------------------------
     def encode(self, d_in, start_bit=0, k_in=0):
