@@ -362,8 +362,9 @@ AEC_GPU_API int aec_gpu_encode_uniform_batch_async(aec_gpu_ctx *ctx, const aec_g
  * way, plan.out_bound always suffices, and d_out need not be cleared.
  * d_rsi_bit_offsets (optional, plan.rsi_entries entries): for chunk i its rsi_count_i + 1 entries at index
  * sum over j < i of (rsi_count_j + 1) -- bit positions relative to d_out, the last one the end of the chunk's stream
- * before padding -- so aec_gpu_decode_async(d_in = d_out, table + that index, rsi_count_i, blocks_i, ...) is a round
- * trip of chunk i without an index pass.  A segment table set with aec_gpu_set_segment_table is NOT filled by this call.
+ * before padding -- exactly the table aec_gpu_decode_chunks_async below takes with have_table != 0: one call, one decode
+ * launch, is the round trip of the whole batch without an index pass (aec_gpu_decode_async(d_in = d_out, table + that
+ * index, rsi_count_i, blocks_i, ...) still decodes chunk i alone).  A segment table set with aec_gpu_set_segment_table is NOT filled by this call.
  * The call does not synchronise the device unless one of the context's buffers has to grow.
  * n_chunks == 0: AEC_OK, nothing is enqueued; parameters aec_gpu_check_params(p, 1) refuses: AEC_CONF_ERROR.
  *
@@ -386,6 +387,60 @@ AEC_GPU_API int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_para
                                             const uint64_t *chunk_offsets, const uint64_t *chunk_bytes, uint64_t n_chunks,
                                             void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
                                             uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result, void *stream);
+
+/*
+ * The decode side of that shape: n_chunks streams of UNEQUAL decoded sizes anywhere in d_in as ONE decode launch, every
+ * lane of it an RSI that holds blocks -- no room per chunk for the RSIs of the largest one, neither in the table nor in
+ * the output nor in the launch.  All four arrays are HOST arrays of n_chunks entries (free again when the call returns).
+ *   input    chunk i is the stream of in_bytes_each[i] bytes at d_in + in_offsets[i]: any byte offset, any order, no
+ *            overlap; d_in is 4-byte aligned and readable up to the next multiple of 4 behind in_bytes.
+ *   output   chunk i decodes to out_bytes[i] bytes of samples: out_bytes[i] / (bytes per sample) samples, whose blocks
+ *            and RSIs are what aec_gpu_block_count / aec_gpu_rsi_count say (the last RSI may be short; the last block
+ *            is decoded whole, as everywhere here).  The blocks land at d_out + out_offsets[i], a multiple of 16, where
+ *            the caller guarantees blocks_i * block_size * bytes per sample bytes; nothing outside these rooms is
+ *            written, whatever a stream holds.  d_out as for aec_gpu_decode_async.  A chunk of less than one sample
+ *            decodes nothing and writes nothing.
+ *   have_table != 0   d_rsi_bit_offsets holds rsi_count_i + 1 entries for chunk i at index sum over j < i of
+ *            (rsi_count_j + 1), bit positions relative to d_in (the last entry of a chunk is not read): the table
+ *            aec_gpu_encode_chunks_async writes.  No index pass; in_offsets and in_bytes_each may be NULL.  The call is
+ *            the upload of the descriptors, one set-up kernel, ONE decode launch and the (idle) sequential decoder
+ *            behind it.
+ *   have_table == 0   bare streams: the same table (plan.rsi_entries entries) is filled first -- one wavefront per
+ *            stream walks from bit 8 * in_offsets[i] to at most bit 8 * (in_offsets[i] + in_bytes_each[i]), so streams
+ *            may lie back to back without padding, and writes up to rsi_count_i starts at the chunk's place -- then the
+ *            same decode launch runs with every chunk's counts from its record on the device.  Only the serial walk is
+ *            used here: there are no window tables for unequal batches, so large low-entropy chunks (tens of KiB and
+ *            more per stream) are better served chunk by chunk (aec_gpu_index_async + aec_gpu_decode_indexed_async) or
+ *            as an equal batch (aec_gpu_decode_batch_async), as the libaec ABI's batch decode decides.
+ *   d_results[i]   bare streams: the index record of stream i as aec_gpu_index_batch_async writes it (n_rsi / tail_blocks
+ *            below what the chunk announces: the stream was shorter; status 2: corrupt); with a table: n_rsi /
+ *            tail_blocks from the arguments, status 0.  Either way raised to status 2 when one of the chunk's items
+ *            fails to decode.
+ *   d_result   the overall decode record; bad_rsi = the lowest failing ITEM of the launch (items: the RSIs of all chunks
+ *            numbered through, chunk after chunk), tail_blocks = that item * rsi + the failing block within it; bit 31
+ *            of pad as documented above.
+ * The call does not synchronise the device unless one of the context's buffers has to grow (they are the ones
+ * aec_gpu_encode_chunks_async uses: counted by aec_gpu_held_bytes, released by aec_gpu_trim).
+ * n_chunks == 0: AEC_OK, nothing is enqueued; parameters aec_gpu_check_params(p, 0) refuses, or an out_offsets[i] that is
+ * not a multiple of 16: AEC_CONF_ERROR.
+ *
+ * aec_gpu_decode_chunks_plan is host arithmetic only (1 = the batch is taken, 0 = it would be refused: more than
+ * 2^31 - 1 chunks or items -- a launch addresses at most that many workgroups, and a wavefront per item is one of the
+ * ways an item is decoded -- or invalid parameters).
+ */
+typedef struct aec_gpu_dchunks_plan {
+    uint64_t items;          /* sum of rsi_count_i: the decode launch's items */
+    uint64_t rsi_entries;    /* sum of rsi_count_i + 1: the table's entries (= aec_gpu_chunks_plan.rsi_entries) */
+    size_t   out_bytes;      /* packed output: sum of up16(blocks_i * block bytes) */
+    size_t   workspace_bytes;/* device memory the context holds for such a batch */
+} aec_gpu_dchunks_plan;
+AEC_GPU_API int aec_gpu_decode_chunks_plan(const aec_gpu_params *p, const uint64_t *out_bytes, uint64_t n_chunks,
+                                           aec_gpu_dchunks_plan *plan);
+AEC_GPU_API int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                                            const uint64_t *in_offsets, const uint64_t *in_bytes_each,
+                                            const uint64_t *out_offsets, const uint64_t *out_bytes, uint64_t n_chunks,
+                                            uint64_t *d_rsi_bit_offsets, int have_table, void *d_out,
+                                            aec_gpu_dec_result *d_results, aec_gpu_dec_result *d_result, void *stream);
 
 /*
  * Measurement hooks (bench.py): with profiling enabled the context records HIP events on the

@@ -26,6 +26,7 @@
 // There is no CPU codec in here: without a working HIP device every call fails with AEC_MEM_ERROR.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -934,6 +935,14 @@ int run_parts(size_t n, size_t total_bytes, Part part)
     return rc;
 }
 
+// (AEC_ABI_TRACE) the way a decode batch takes: "chunks" (small chunks of unequal RSI counts: one walker launch and ONE
+// decode launch over packed output, aec_gpu_decode_chunks_async), "batch" (small chunks of equal RSI counts), "grouped"
+// (large low-entropy chunks over window tables, group by group) or "loop" (large chunks, one after the other)
+void trace_decode_batch(const char *path, size_t n, size_t bytes)
+{
+    if (trace_on()) fprintf(stderr, "libaec (MI355X): decode batch: %zu chunks, %zu bytes on the device, path %s\n", n, bytes, path);
+}
+
 int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src, const size_t *src_len,
                  void *const *dst, size_t *dst_len, int *status)
 {
@@ -950,21 +959,48 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
     uint64_t rpc = 1;
     std::vector<uint64_t> off(n + 1);
     size_t total_in = 0;
+    bool unequal = false;                  // the chunks' RSI counts differ
     for (size_t i = 0; i < n; i++) {
         off[i] = total_in;
         total_in += up16(src_len[i]) + 16;
         const uint64_t r = (dst_len[i] + rsi_bytes - 1) / rsi_bytes;
+        if (i && r != (dst_len[0] + rsi_bytes - 1) / rsi_bytes) unequal = true;
         if (r > rpc) rpc = r;
     }
     off[n] = total_in;
+    const bool large = total_in / n >= ((size_t)32 << 10) || n < 64;
+    // Small chunks of unequal RSI counts: every chunk gets the room its own blocks need -- packed output, a table of
+    // its own RSIs, a launch of the RSIs there are -- instead of the largest chunk's (aec_gpu_decode_chunks_async)
+    // (streams of 16 KiB and more that the equal-stride batch would index over window tables stay with it: the serial
+    // walk of such a stream is what the tables are there to avoid)
+    const bool packed = !large && unequal && !aec_gpu_batch_uses_tables(k.ctx, &gp, total_in, n, rpc);
+    std::vector<uint64_t> slot_at, out_want, in_len, item0;
+    size_t packed_out = 0;
+    uint64_t packed_entries = 0;
+    if (packed) {
+        slot_at.resize(n);
+        out_want.resize(n);
+        in_len.resize(n);
+        item0.resize(n + 1);
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t blocks = ((uint64_t)dst_len[i] / c.bytes + c.bs - 1) / c.bs;
+            slot_at[i] = packed_out;
+            out_want[i] = dst_len[i];
+            in_len[i] = src_len[i];
+            item0[i] = packed_entries - i;
+            packed_out += up16((size_t)blocks * blk_bytes);
+            packed_entries += (blocks + c.rsi - 1) / c.rsi + 1;
+        }
+        item0[n] = packed_entries - n;
+    }
     // the index walker takes [off[i], off[i+1]) as stream i: the padding behind a stream is zeroed (zero
     // bits never complete a coded data set), the streams go up straight from the caller's buffers
     // (chunk offsets twice: the n + 1 absolute ones, and -- for the table path, which takes the batch in groups --
     // relative to the group a chunk belongs to, every group with a closing entry of its own: n + G entries for G <= n
     // groups, so the region holds 3 n + 4)
-    const size_t o_choff = up16((size_t)n * rpc * 8), o_res = o_choff + up16((3 * n + 4) * 8),
-                 o_one = o_res + up16(n * 40);
-    if (!k.d_in.ensure(total_in + 32) || !k.d_out.ensure((size_t)n * rpc * rsi_bytes + 64) ||
+    const size_t o_choff = up16(packed ? (size_t)packed_entries * 8 : (size_t)n * rpc * 8),
+                 o_res = o_choff + up16((3 * n + 4) * 8), o_one = o_res + up16(n * 40);
+    if (!k.d_in.ensure(total_in + 32) || !k.d_out.ensure((packed ? packed_out : (size_t)n * rpc * rsi_bytes) + 64) ||
         !k.d_off.ensure(o_one + 64))
         return AEC_FAIL(AEC_MEM_ERROR);
     uint8_t *meta = static_cast<uint8_t *>(k.d_off.p);
@@ -981,7 +1017,6 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
     // the host in between.
     aec_gpu_dec_result *d_results = reinterpret_cast<aec_gpu_dec_result *>(meta + o_res);
     aec_gpu_dec_result *d_one = reinterpret_cast<aec_gpu_dec_result *>(meta + o_one);
-    const bool large = total_in / n >= ((size_t)32 << 10) || n < 64;
     // Large low-entropy chunks: groups of about 12 MiB of streams, each group ONE table launch + one wavefront
     // per stream + one decode launch (aec_gpu_decode_batch_async)
     constexpr size_t kGroupBytes = (size_t)12 << 20;
@@ -995,7 +1030,13 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
         }
         grouped = aec_gpu_batch_uses_tables(k.ctx, &gp, probe_bytes, probe_n, rpc) != 0;
     }
-    if (grouped) {
+    if (packed) {
+        trace_decode_batch("chunks", n, total_in);
+        rc = aec_gpu_decode_chunks_async(k.ctx, &gp, k.d_in.p, total_in, off.data(), in_len.data(), slot_at.data(), out_want.data(),
+                                         n, reinterpret_cast<uint64_t *>(meta), 0, k.d_out.p, d_results, d_one, k.stream);
+        if (rc != RC_OK) return AEC_FAIL(rc);
+    } else if (grouped) {
+        trace_decode_batch("grouped", n, total_in);
         std::vector<uint64_t> rel;
         std::vector<size_t> first;                      // first chunk of every group, index of its offsets in rel
         std::vector<size_t> at;
@@ -1023,10 +1064,12 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
         // (decoder-side errors are in the chunks' own records; the overall record belongs to the last group only)
         if (hipMemsetAsync(d_one, 0, sizeof(aec_gpu_dec_result), k.stream) != hipSuccess) return AEC_FAIL(AEC_MEM_ERROR);
     } else if (!large) {
+        trace_decode_batch("batch", n, total_in);
         rc = aec_gpu_decode_batch_async(k.ctx, &gp, k.d_in.p, total_in, reinterpret_cast<uint64_t *>(meta + o_choff), n,
                                         rpc, reinterpret_cast<uint64_t *>(meta), k.d_out.p, d_results, d_one, k.stream);
         if (rc != RC_OK) return AEC_FAIL(rc);
     } else {
+        trace_decode_batch("loop", n, total_in);
         // (per chunk: its own decode record behind the index records; the overall record is folded on the host)
         // (the per-chunk decode records live behind the stream's own record in d_res, which stays with the kit)
         if (!k.d_res.ensure(256 + n * sizeof(aec_gpu_dec_result) + 64)) return AEC_FAIL(AEC_MEM_ERROR);
@@ -1067,6 +1110,24 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
     // (pieces of about 4 MiB through the two halves of the staging buffer: the transfer of piece p + 1 runs beside the
     // host's copies of piece p -- one transfer of a whole part and then its copies were the two largest items of a
     // batch of 64 x 1 MiB behind the index kernels)
+    const auto finish = [&](size_t i, int *st, bool bad_item) {
+        const uint64_t blocks = res[i].n_rsi * c.rsi + res[i].tail_blocks;
+        size_t produced = (size_t)blocks * blk_bytes;
+        if (produced > dst_len[i]) produced = dst_len[i] - dst_len[i] % c.bytes;
+        if (res[i].status == DEC_DATA_ERROR || bad_item) *st = AEC_DATA_ERROR;
+        return produced;
+    };
+    if (packed) {
+        // (the packed slots in pieces of whole slots through the staging buffer; the item the overall record names
+        // belongs to the last chunk whose first item is not behind it)
+        size_t bad = n;
+        if (res[n].status != DEC_OK)
+            bad = (size_t)(std::upper_bound(item0.begin(), item0.end(), res[n].bad_rsi) - item0.begin()) - 1;
+        const bool staged = n >= 4 && stage_ensure(k, packed_out < kStagePiece ? (packed_out ? packed_out : 16) : kStagePiece);
+        return stage_down(k, n, dst, dst_len, status, [&](size_t i) { return (size_t)slot_at[i]; },
+                          [&](size_t i) { return (size_t)((i + 1 < n ? slot_at[i + 1] : packed_out) - slot_at[i]); },
+                          staged ? k.h_stage_cap : 0, false, [&](size_t i, int *st) { return finish(i, st, i == bad); });
+    }
     const size_t slot_out = (size_t)rpc * rsi_bytes;
     constexpr size_t kOutPiece = (size_t)4 << 20;
     const size_t per_piece = !slot_out ? 0 : (slot_out <= kOutPiece ? kOutPiece / slot_out : (slot_out <= kStagePiece / 2 ? 1 : 0));
@@ -1075,12 +1136,7 @@ int decode_batch(const struct aec_stream *prm, size_t n, const void *const *src,
                         k.side.event(0) && k.side.event(1);
     return stage_down(k, n, dst, dst_len, status, [&](size_t i) { return i * slot_out; }, [&](size_t) { return slot_out; },
                       staged ? per_piece * slot_out : 0, staged, [&](size_t i, int *st) {
-        const uint64_t blocks = res[i].n_rsi * c.rsi + res[i].tail_blocks;
-        size_t produced = (size_t)blocks * blk_bytes;
-        if (produced > dst_len[i]) produced = dst_len[i] - dst_len[i] % c.bytes;
-        if (res[i].status == DEC_DATA_ERROR) *st = AEC_DATA_ERROR;
-        if (!grouped && res[n].status != DEC_OK && res[n].bad_rsi / rpc == i) *st = AEC_DATA_ERROR;
-        return produced;
+        return finish(i, st, !grouped && res[n].status != DEC_OK && res[n].bad_rsi / rpc == i);
     });
 }
 

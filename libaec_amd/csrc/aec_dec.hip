@@ -24,6 +24,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "aec_dchunks.h"
 #include "aec_kernels.h"
 #include "aec_lane.h"
 #include "aec_spec.h"
@@ -68,7 +69,22 @@ struct DecLaunch {
     bool next_entry = false;       // ... whose table has an entry behind the last item: passed where a batch passes rpc
     uint32_t rpc_arg() const { return win ? (next_entry ? 1u : 0u) : rpc; }
     BareArgs ba;
+    // the CHUNKS variants of the kernels (aec_dchunks.h: no segments, no sums, no window): the chunk descriptors and the
+    // chunk of every item; `batch` holds the chunks' records
+    const DChunkDesc *chunks = nullptr;
+    const uint32_t *item_chunk = nullptr;
 };
+// what the CHUNKS variants take beyond the arguments of the others (nothing for those: an empty argument)
+template <bool CHUNKS> struct ChunksArg {};
+template <> struct ChunksArg<true> {
+    const DChunkDesc *desc;
+    const uint32_t *item_chunk;
+};
+template <bool CHUNKS> ChunksArg<CHUNKS> chunks_arg(const DecLaunch &a)
+{
+    if constexpr (CHUNKS) return ChunksArg<true>{a.chunks, a.item_chunk};
+    else return ChunksArg<false>{};
+}
 template <int BS> void dec_part_bytes(bool seg, bool sums, const DecLaunch &a);      // k_decode<BS, ...>
 template <int BS> void dec_part_wave(const DecLaunch &a);                             // k_decode_wave<BS, ...>
 
@@ -426,17 +442,23 @@ __host__ __device__ constexpr uint32_t stg_row(int blk) { return blk == 8 ? (AEC
 //
 // WIN: the RSIs of a window, with the end check that win_end_check() describes (this kernel keeps its own text of it and
 // of dec_counts: through the helpers its instruction counts moved, and it has no register to spare).
-template <int BS, int BYTES, bool SEG, int kPend, bool SUMS = false, bool WIN = false>
+//
+// CHUNKS: the RSIs of a batch of unequal chunks (aec_dchunks.h): an item takes its chunk from ck.item_chunk, its start
+// bit, block count and output position from dchunk_item, and reports to its chunk's record in `batch`.  The stores need
+// nothing of their own: rows, groups and vector stores are placed relative to the item's first block, which lies whole
+// RSIs behind the chunk's 16-byte aligned room -- as an RSI of a plain launch lies behind the 16-byte aligned output.
+template <int BS, int BYTES, bool SEG, int kPend, bool SUMS = false, bool WIN = false, bool CHUNKS = false>
 __global__ void __launch_bounds__(256, AEC_DEC_MINW)
 k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
          const uint64_t *__restrict__ rsi_off, const SegEntry *__restrict__ seg_table, uint64_t n_rsi,
          uint64_t total_blocks, uint8_t *__restrict__ out, DecResult *res, uint32_t ring_words, uint32_t maxw,
          uint32_t needw, uint8_t *__restrict__ dump, const DecResult *__restrict__ idx,
          const DecResult *__restrict__ batch, uint32_t rsi_per_chunk, SegSum *__restrict__ sums,
-         const uint32_t *__restrict__ list, const uint32_t *__restrict__ list_cnt)
+         const uint32_t *__restrict__ list, const uint32_t *__restrict__ list_cnt, const ChunksArg<CHUNKS> ck)
 {
     static_assert(!SUMS || (SEG && BS != 0), "the summing pass runs per segment on the templated block sizes");
     static_assert(!WIN || (!SEG && !SUMS), "windows are tables of RSI starts");
+    static_assert(!CHUNKS || (!SEG && !SUMS && !WIN), "chunks are tables of RSI starts with a record per chunk");
     // item counts straight from the record the index pass left on the device (the grid was sized for
     // the most it could find): no host round trip between the two passes
     if (idx) {
@@ -477,8 +499,17 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
 
     uint32_t nb = 0, b0 = 0, x = 0;
     uint64_t start = 0, first_blk = 0;
+    [[maybe_unused]] uint64_t ck_chunk = 0, ck_pos = 0;   // CHUNKS: the item's chunk, byte offset of its first block
     if (active) {
-        if (SEG) {
+        if constexpr (CHUNKS) {
+            ck_chunk = ck.item_chunk[r];
+            const DItem it = dchunk_item(ck.desc, ck_chunk, r, c.rsi, (uint64_t)bs * c.bytes, batch[ck_chunk].n_rsi,
+                                         batch[ck_chunk].tail_blocks);
+            nb = it.nb;
+            start = nb ? rsi_off[it.entry] : 0;
+            first_blk = r * c.rsi;                    // (what the reports count in: items)
+            ck_pos = it.out_pos;
+        } else if (SEG) {
             const uint64_t rsi_idx = (r >> 32) ? r / c.segs_per_rsi : (uint64_t)((uint32_t)r / c.segs_per_rsi);
             b0 = (uint32_t)(r - rsi_idx * c.segs_per_rsi) * 64u;
             uint64_t left = total_blocks > rsi_idx * c.rsi ? total_blocks - rsi_idx * c.rsi : 0u;
@@ -513,7 +544,9 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
         }
     }
     const size_t blk_bytes = (size_t)bs * c.bytes;
-    uint8_t *dst = out + (size_t)first_blk * blk_bytes;
+    uint8_t *dst;
+    if constexpr (CHUNKS) dst = out + (size_t)ck_pos;
+    else dst = out + (size_t)first_blk * blk_bytes;
     // (a row's destination and fill level live in its lane's registers; the lanes that write the row out
     // fetch them with a lane permute -- as pointer and count arrays they cost 768 bytes of LDS per wave, the
     // 16th wave of a CU at C2)
@@ -692,7 +725,10 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
                     report(res, st, SEG ? (first_blk + bb) / c.rsi : r, first_blk + bb);
                     // (a batch of independent streams: the stream's own record says so as well -- one overall
                     // record names only the first bad RSI of the whole batch)
-                    if (batch && st == DEC_DATA_ERROR)
+                    if constexpr (CHUNKS) {
+                        if (st == DEC_DATA_ERROR)
+                            atomicMax(&const_cast<DecResult *>(batch)[ck_chunk].status, (uint32_t)DEC_DATA_ERROR);
+                    } else if (batch && st == DEC_DATA_ERROR)
                         atomicMax(&const_cast<DecResult *>(batch)[r / rsi_per_chunk].status, (uint32_t)DEC_DATA_ERROR);
                     ok = 0u;
                 } else if (nz) {
@@ -756,7 +792,10 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
                     report(res, st, r, first_blk + bo);
                     // (a batch of independent streams: the stream's own record says so as well -- one overall
                     // record names only the first bad RSI of the whole batch)
-                    if (batch && st == DEC_DATA_ERROR)
+                    if constexpr (CHUNKS) {
+                        if (st == DEC_DATA_ERROR)
+                            atomicMax(&const_cast<DecResult *>(batch)[ck_chunk].status, (uint32_t)DEC_DATA_ERROR);
+                    } else if (batch && st == DEC_DATA_ERROR)
                         atomicMax(&const_cast<DecResult *>(batch)[r / rsi_per_chunk].status, (uint32_t)DEC_DATA_ERROR);
                     ok = 0u;
                 } else if (nz) {
@@ -815,14 +854,15 @@ k_decode(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint6
 // (BitReader + parse_cds, the sequential reader the index pass and the emulator use): slow, but the answer for
 // any stream the format allows -- a foreign encoder that picks k = 0 for large residuals is within its rights.
 // Items and results as in k_decode (same tables, same output, same status record; WIN: the same end check).
-template <bool SEG, bool WIN = false>
+template <bool SEG, bool WIN = false, bool CHUNKS = false>
 __global__ void __launch_bounds__(64)
 k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
               const uint64_t *__restrict__ rsi_off, const SegEntry *__restrict__ seg_table, uint64_t n_rsi,
               uint64_t total_blocks, uint8_t *__restrict__ out, DecResult *res, const DecResult *__restrict__ idx,
               const DecResult *__restrict__ batch, uint32_t rsi_per_chunk, const uint32_t *__restrict__ list,
-              const uint32_t *__restrict__ list_cnt)
+              const uint32_t *__restrict__ list_cnt, const ChunksArg<CHUNKS> ck)
 {
+    static_assert(!CHUNKS || (!SEG && !WIN), "chunks are tables of RSI starts with a record per chunk");
     if (!(*reinterpret_cast<volatile uint32_t *>(&res->pad) & kDecRedo)) return;
     dec_counts<SEG>(c, idx, n_rsi, total_blocks);
     if (!SEG && list) n_rsi = *list_cnt;
@@ -832,7 +872,15 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
         const uint64_t r = (!SEG && list) ? list[r_lin] : r_lin;
         uint32_t nb = 0, b0 = 0, x = 0;
         uint64_t start = 0, first_blk = 0;
-        if (SEG) {
+        [[maybe_unused]] uint64_t ck_chunk = 0, ck_pos = 0;
+        if constexpr (CHUNKS) {
+            ck_chunk = ck.item_chunk[r];
+            const DItem it = dchunk_item(ck.desc, ck_chunk, r, c.rsi, blk_bytes, batch[ck_chunk].n_rsi, batch[ck_chunk].tail_blocks);
+            nb = it.nb;
+            start = nb ? rsi_off[it.entry] : 0;
+            first_blk = r * c.rsi;
+            ck_pos = it.out_pos;
+        } else if (SEG) {
             const uint64_t rsi_idx = r / c.segs_per_rsi;
             b0 = (uint32_t)(r - rsi_idx * c.segs_per_rsi) * 64u;
             uint64_t left = total_blocks > rsi_idx * c.rsi ? total_blocks - rsi_idx * c.rsi : 0u;
@@ -856,7 +904,9 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
             start = rsi_off[r];
             first_blk = r * c.rsi;
         }
-        uint8_t *dst = out + (size_t)first_blk * blk_bytes;
+        uint8_t *dst;
+        if constexpr (CHUNKS) dst = out + (size_t)ck_pos;
+        else dst = out + (size_t)first_blk * blk_bytes;
         BitReader br;
         br.init(words, nwords, end_bit, start);
         uint32_t d[kMaxBlockSize];
@@ -869,7 +919,10 @@ k_decode_redo(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
                 const uint32_t st = parse_cds<0>(br, d, c, rf ? 1u : 0u, b0 + bo, nz);
                 if (st != DEC_OK) {
                     report(res, st, r, first_blk + bo);
-                    if (batch && st == DEC_DATA_ERROR)
+                    if constexpr (CHUNKS) {
+                        if (st == DEC_DATA_ERROR)
+                            atomicMax(&const_cast<DecResult *>(batch)[ck_chunk].status, (uint32_t)DEC_DATA_ERROR);
+                    } else if (batch && st == DEC_DATA_ERROR)
                         atomicMax(&const_cast<DecResult *>(batch)[r / rsi_per_chunk].status, (uint32_t)DEC_DATA_ERROR);
                     whole = false;
                     break;
@@ -979,14 +1032,15 @@ __device__ unsigned long long g_dw_prof[8];      // (diagnostics, AEC_DW_PROF=1:
 #define DW_T1(k) do { } while (0)
 #endif
 
-template <int BS, int BYTES, bool WIN = false>
+template <int BS, int BYTES, bool WIN = false, bool CHUNKS = false>
 __global__ void __launch_bounds__(256)
 k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
               const uint64_t *__restrict__ rsi_off, uint64_t n_rsi, uint64_t total_blocks, uint8_t *__restrict__ out,
               DecResult *res, uint8_t *__restrict__ dump, const DecResult *__restrict__ idx,
-              const DecResult *__restrict__ batch, uint32_t rsi_per_chunk)
+              const DecResult *__restrict__ batch, uint32_t rsi_per_chunk, const ChunksArg<CHUNKS> ck)
 {
     static_assert(BS == 8 || BS == 16 || BS == 32 || BS == 64, "templated block sizes");
+    static_assert(!CHUNKS || !WIN, "chunks have no end check");
     dec_counts<false>(c, idx, n_rsi, total_blocks);
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t lane = threadIdx.x & 63u;
@@ -998,11 +1052,25 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
     const uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     if (r >= n_rsi) return;
     const bool pp = c.flags & F_PREPROCESS, sgn = c.flags & F_SIGNED;
-    const DecItem it = dec_item(c, r, total_blocks, rsi_off, batch, rsi_per_chunk);
+    constexpr uint32_t BLK = (uint32_t)BS * (uint32_t)BYTES;
+    DecItem it;
+    uint8_t *dst;
+    [[maybe_unused]] uint64_t ck_chunk = 0;
+    if constexpr (CHUNKS) {
+        // (an RSI of a batch of unequal chunks, aec_dchunks.h: blocks lie one behind the other from the item's first,
+        // whole RSIs behind the chunk's 16-byte aligned room)
+        ck_chunk = ck.item_chunk[r];
+        const DItem ci = dchunk_item(ck.desc, ck_chunk, r, c.rsi, BLK, batch[ck_chunk].n_rsi, batch[ck_chunk].tail_blocks);
+        it.nb = ci.nb;
+        it.start = ci.nb ? rsi_off[ci.entry] : 0;
+        it.first_blk = r * c.rsi;
+        dst = out + (size_t)ci.out_pos;
+    } else {
+        it = dec_item(c, r, total_blocks, rsi_off, batch, rsi_per_chunk);
+        dst = out + (size_t)it.first_blk * BLK;
+    }
     const uint32_t nb = it.nb;
     const uint64_t start = it.start, first_blk = it.first_blk;
-    constexpr uint32_t BLK = (uint32_t)BS * (uint32_t)BYTES;
-    uint8_t *dst = out + (size_t)first_blk * BLK;
     const uint32_t maxbits = c.id_len + 1u + c.bps + c.bs * c.bps, idmax = (1u << c.id_len) - 1u;
     const bool coop = maxbits + 128u <= 2048u;
 
@@ -1320,7 +1388,13 @@ k_decode_wave(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, 
                 if (over) {
                     atomicOr(&res->pad, kDecRedo);
                 } else {
-                    report_item(res, batch, rsi_per_chunk, st, r, first_blk + done_blocks + f);
+                    if constexpr (CHUNKS) {
+                        report(res, st, r, first_blk + done_blocks + f);
+                        if (st == DEC_DATA_ERROR)
+                            atomicMax(&const_cast<DecResult *>(batch)[ck_chunk].status, (uint32_t)DEC_DATA_ERROR);
+                    } else {
+                        report_item(res, batch, rsi_per_chunk, st, r, first_blk + done_blocks + f);
+                    }
                 }
             }
         } else if (fail_lane < 64u) {
@@ -1545,27 +1619,29 @@ DecGeom dec_geom(const Cfg &c, uint64_t n_rsi, uint64_t avg_cds_bits, uint32_t s
 // ---- DecLaunch -> kernel arguments: one place per kernel family ------------------------------------------------
 // (the kernels take their arguments one by one: __restrict__ on a kernel parameter is what tells the compiler that the
 // tables, the stream and the output do not alias, and members of a by-value struct lose it)
-template <int BS, int BYTES, bool SEG, int KP, bool SUMS, bool WIN>
+template <int BS, int BYTES, bool SEG, int KP, bool SUMS, bool WIN, bool CHUNKS = false>
 void go_lanes(const DecLaunch &a, const DecGeom &g)
 {
-    hipLaunchKernelGGL((k_decode<BS, BYTES, SEG, KP, SUMS, WIN>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c,
+    hipLaunchKernelGGL((k_decode<BS, BYTES, SEG, KP, SUMS, WIN, CHUNKS>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c,
                        a.words, a.nwords, a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res,
-                       g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc_arg(), a.ba.sums, a.ba.list, a.ba.list_cnt);
+                       g.ring_words, g.maxw, g.needw, a.dump, a.idx, a.batch, a.rpc_arg(), a.ba.sums, a.ba.list, a.ba.list_cnt,
+                       chunks_arg<CHUNKS>(a));
 }
 
-template <int BS, int BYTES, bool WIN>
+template <int BS, int BYTES, bool WIN, bool CHUNKS = false>
 void go_wave(const DecLaunch &a, const DecGeom &g)
 {
-    hipLaunchKernelGGL((k_decode_wave<BS, BYTES, WIN>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c, a.words,
-                       a.nwords, a.end_bit, a.rsi_off, a.n_items, a.total_blocks, a.out, a.res, a.dump, a.idx, a.batch, a.rpc_arg());
+    hipLaunchKernelGGL((k_decode_wave<BS, BYTES, WIN, CHUNKS>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c, a.words,
+                       a.nwords, a.end_bit, a.rsi_off, a.n_items, a.total_blocks, a.out, a.res, a.dump, a.idx, a.batch, a.rpc_arg(),
+                       chunks_arg<CHUNKS>(a));
 }
 
-template <bool SEG, bool WIN>
+template <bool SEG, bool WIN, bool CHUNKS = false>
 void go_redo(const DecLaunch &a, const DecGeom &g)
 {
-    hipLaunchKernelGGL((k_decode_redo<SEG, WIN>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c, a.words, a.nwords,
+    hipLaunchKernelGGL((k_decode_redo<SEG, WIN, CHUNKS>), dim3(g.grid), dim3(64 * g.waves), g.lds_bytes, a.st, *a.c, a.words, a.nwords,
                        a.end_bit, a.rsi_off, a.seg_table, a.n_items, a.total_blocks, a.out, a.res, a.idx, a.batch, a.rpc_arg(),
-                       a.ba.list, a.ba.list_cnt);
+                       a.ba.list, a.ba.list_cnt, chunks_arg<CHUNKS>(a));
 }
 
 // f(std::integral_constant<int, B>) for the container width B of the configuration
@@ -1581,7 +1657,8 @@ void with_container_bytes(const Cfg &c, F &&f)
 }
 
 // k_decode for the items of a launch.  A window (a.win) takes the geometry of any other launch and 4 loads in flight,
-// which every templated block size takes: one instantiation per container width instead of two or three.
+// which every templated block size takes: one instantiation per container width instead of two or three.  The same for
+// the items of a batch of unequal chunks (a.chunks).
 template <int BS, bool SEG, bool SUMS>
 void launch_lanes(const DecLaunch &a)
 {
@@ -1592,6 +1669,7 @@ void launch_lanes(const DecLaunch &a)
         const DecGeom g = dec_geom(c, a.n_items, 0, 0u);
         if constexpr (kCanWin) {
             if (a.win) return go_lanes<0, 0, false, 2, false, true>(a, g);
+            if (a.chunks) return go_lanes<0, 0, false, 2, false, false, true>(a, g);
         }
         go_lanes<0, 0, SEG, 2, false, false>(a, g);
     } else {
@@ -1611,6 +1689,7 @@ void launch_lanes(const DecLaunch &a)
             constexpr int B = decltype(by)::value;
             if constexpr (kCanWin) {
                 if (a.win) return go_lanes<BS, B, false, 4, false, true>(a, g);
+                if (a.chunks) return go_lanes<BS, B, false, 4, false, false, true>(a, g);
             }
             if (kp == 2) go_lanes<BS, B, SEG, 2, SUMS, false>(a, g);
             else if (kp == 4) go_lanes<BS, B, SEG, 4, SUMS, false>(a, g);
@@ -1651,6 +1730,7 @@ void dec_part_wave(const DecLaunch &a)
     with_container_bytes(c, [&](auto by) {
         constexpr int B = decltype(by)::value;
         if (a.win) go_wave<BS, B, true>(a, g);
+        else if (a.chunks) go_wave<BS, B, false, true>(a, g);
         else go_wave<BS, B, false>(a, g);
     });
 #ifdef AEC_TUNING
@@ -1720,6 +1800,7 @@ static void launch_redo(bool seg, const DecLaunch &a)
     g.waves = 1;
     g.grid = (uint32_t)(waves < 2048 ? waves : 2048);
     if (a.win) go_redo<false, true>(a, g);
+    else if (a.chunks) go_redo<false, false, true>(a, g);
     else if (seg) go_redo<true, false>(a, g);
     else go_redo<false, false>(a, g);
 }
@@ -1857,6 +1938,51 @@ bool launch_decode_segments(const Cfg &c, const uint8_t *d_in, size_t in_bytes, 
     a.total_blocks = total_blocks;
     a.out = d_out;
     return launch_decode_items(c, d_in, in_bytes, true, a, d_res, st, prof);
+}
+
+// ---- a batch of unequal chunks (aec_dchunks.h) -------------------------------------------------------------------
+// The host's descriptors into what the CHUNKS kernels read: the chunk of every item; and with the caller's table
+// (records != nullptr) the chunks' records as an index pass would leave them, from what the chunks announce.
+__global__ void __launch_bounds__(256)
+k_dchunks_setup(const Cfg c, const DChunkDesc *__restrict__ desc, uint64_t n, uint64_t items, uint32_t *__restrict__ item_chunk,
+                DecResult *__restrict__ records)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < items) item_chunk[t] = (uint32_t)dchunk_of_item(desc, n, t);
+    if (records && t < n) {
+        DecResult r;
+        dchunk_announced(desc[t], c.rsi, &r.n_rsi, &r.tail_blocks);
+        r.end_bit = 0;
+        r.status = DEC_OK;
+        r.pad = 0;
+        r.bad_rsi = ~0ull;
+        records[t] = r;
+    }
+}
+
+void launch_dchunks_setup(const Cfg &c, const DChunkDesc *d_desc, uint64_t n, uint64_t items, uint32_t *d_item_chunk,
+                          DecResult *d_records, hipStream_t st)
+{
+    const uint64_t threads = items > n ? items : n;
+    if (!threads) return;
+    hipLaunchKernelGGL(k_dchunks_setup, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, c, d_desc, n, items,
+                       d_item_chunk, d_records);
+}
+
+bool launch_decode_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off,
+                          const DChunkDesc *d_desc, const uint32_t *d_item_chunk, uint64_t items, uint64_t avg_cds_hint,
+                          uint8_t *d_out, DecResult *d_records, DecResult *d_res, hipStream_t st, const PhaseEvents *prof)
+{
+    DecLaunch a;
+    a.rsi_off = d_rsi_off;
+    a.n_items = items;
+    a.total_blocks = items * c.rsi;
+    a.out = d_out;
+    a.batch = d_records;
+    a.chunks = d_desc;
+    a.item_chunk = d_item_chunk;
+    a.ba.avg_hint = avg_cds_hint;
+    return launch_decode_items(c, d_in, in_bytes, false, a, d_res, st, prof);
 }
 
 void launch_decode_partial(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DecResult *d_idx, uint8_t *d_out,

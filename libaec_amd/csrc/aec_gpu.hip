@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "aec_chunks.h"
+#include "aec_dchunks.h"
 #include "aec_kernels.h"
 
 using namespace aec;
@@ -49,8 +50,8 @@ struct aec_gpu_ctx {
     size_t fused_bytes;
     void *range_ws;        // whole blocks of a range decode whose window does not start on an RSI / end on a block
     size_t range_ws_bytes;
-    // aec_gpu_encode_chunks_async: the chunk descriptors and the per-wave table on the device, and the pinned buffers
-    // the descriptors are written to on the host -- two, taken in turn, each guarded by the event of its last transfer
+    // aec_gpu_encode_chunks_async / aec_gpu_decode_chunks_async: the chunk descriptors and the per-wave / per-item table
+    // on the device, and the pinned buffers the descriptors are written to on the host -- two, taken in turn, each guarded by the event of its last transfer
     void *chunks_d;
     size_t chunks_d_bytes;
     static constexpr unsigned kChunkStages = 2;
@@ -854,6 +855,132 @@ int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
                          sh.waves, sh.spw};
     launch_encode_chunks(sh.c, static_cast<const uint8_t *>(d_in), k, static_cast<uint8_t *>(d_out), out_cap, ws,
                          reinterpret_cast<BatchChunk *>(d_chunks), d_rsi_bit_offsets, reinterpret_cast<EncResult *>(d_result), st);
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+}
+
+// ---- a batch of unequal chunks decoded as one launch (aec_dchunks.h) ----------------------------------------------------
+namespace {
+struct DChunksShape {
+    Cfg c;
+    uint64_t items, entries, blocks;
+    size_t out_bytes, desc_bytes, table_bytes;
+};
+// The most items a launch addresses: k_decode_wave takes a workgroup of two wavefronts per two items and a grid has at
+// most 2^31 - 1 workgroups; the item table holds 32-bit chunk numbers, so as many chunks at most.
+constexpr uint64_t kDChunksMaxItems = 0x7FFFFFFFull;
+
+// host arithmetic of a batch; with desc (n + 1 entries) the descriptors are written too (packed rooms where out_offsets
+// is NULL).  false = refused.
+bool dchunks_shape(const aec_gpu_params *p, const uint64_t *in_offsets, const uint64_t *in_bytes_each,
+                   const uint64_t *out_offsets, const uint64_t *out_bytes, uint64_t n, DChunksShape *sh, DChunkDesc *desc)
+{
+    Cfg &c = sh->c;
+    if (cfg_from(p, 0, false, &c) != RC_OK || (n && !out_bytes) || n > kDChunksMaxItems) return false;
+    const uint64_t blk_bytes = (uint64_t)c.bs * c.bytes;
+    uint64_t items = 0, blocks = 0, packed = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const DChunkCounts k = dchunk_counts(out_bytes[i], c.bytes, c.bs, c.rsi);
+        if (k.rsis > kDChunksMaxItems) return false;
+        if (desc)
+            desc[i] = DChunkDesc{in_offsets ? in_offsets[i] : 0, in_bytes_each ? in_bytes_each[i] : 0,
+                                 out_offsets ? out_offsets[i] : packed, items, (uint32_t)k.rsis, k.last_blocks};
+        items += k.rsis;
+        blocks += k.blocks;
+        packed += dchunk_room(k.blocks, blk_bytes);
+        if (items > kDChunksMaxItems || packed >> 48) return false;
+    }
+    if (desc) desc[n] = DChunkDesc{0, 0, packed, items, 0u, 0u};
+    sh->items = items;
+    sh->entries = items + n;
+    sh->blocks = blocks;
+    sh->out_bytes = (size_t)packed;
+    sh->desc_bytes = up256((size_t)(n + 1) * sizeof(DChunkDesc));
+    sh->table_bytes = up256((size_t)(items ? items : 1) * 4);
+    return true;
+}
+}  // namespace
+
+int aec_gpu_decode_chunks_plan(const aec_gpu_params *p, const uint64_t *out_bytes, uint64_t n_chunks,
+                               aec_gpu_dchunks_plan *plan)
+{
+    DChunksShape sh;
+    if (!p || !plan || !dchunks_shape(p, nullptr, nullptr, nullptr, out_bytes, n_chunks, &sh, nullptr)) return 0;
+    plan->items = sh.items;
+    plan->rsi_entries = sh.entries;
+    plan->out_bytes = sh.out_bytes;
+    plan->workspace_bytes = sh.desc_bytes + sh.table_bytes;
+    return 1;
+}
+
+int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                                const uint64_t *in_offsets, const uint64_t *in_bytes_each, const uint64_t *out_offsets,
+                                const uint64_t *out_bytes, uint64_t n_chunks, uint64_t *d_rsi_bit_offsets, int have_table,
+                                void *d_out, aec_gpu_dec_result *d_results, aec_gpu_dec_result *d_result, void *stream)
+{
+    if (aec_gpu_check_params(p, 0) != RC_OK) return RC_CONF_ERROR;
+    if (n_chunks == 0) return RC_OK;
+    if (!out_offsets || !out_bytes || !d_rsi_bit_offsets || !d_results || !d_result || (reinterpret_cast<uintptr_t>(d_in) & 3u) ||
+        (!have_table && (!in_offsets || !in_bytes_each)))
+        return RC_CONF_ERROR;
+    for (uint64_t i = 0; i < n_chunks; i++) {
+        if (out_offsets[i] & 15u) return RC_CONF_ERROR;
+        if (!have_table && (in_offsets[i] > in_bytes || in_bytes_each[i] > in_bytes - in_offsets[i])) return RC_CONF_ERROR;
+    }
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // the descriptors: through the pinned buffers and the device buffer aec_gpu_encode_chunks_async uses (same turns,
+    // same events: a context's calls are enqueued on one stream, so the copy below waits for the kernels in front)
+    const unsigned slot = ctx->chunks_calls++ % aec_gpu_ctx::kChunkStages;
+    const size_t h_need = (size_t)(n_chunks + 1) * sizeof(DChunkDesc);
+    if (!ctx->chunks_ev[slot] && hipEventCreateWithFlags(&ctx->chunks_ev[slot], hipEventDisableTiming) != hipSuccess) {
+        ctx->chunks_ev[slot] = nullptr;
+        (void)hipGetLastError();
+        return RC_MEM_ERROR;
+    }
+    if (ctx->chunks_h[slot] && hipEventSynchronize(ctx->chunks_ev[slot]) != hipSuccess) return RC_MEM_ERROR;
+    if (h_need > ctx->chunks_h_bytes[slot]) {
+        if (ctx->chunks_h[slot]) (void)hipHostFree(ctx->chunks_h[slot]);
+        ctx->chunks_h[slot] = nullptr;
+        ctx->chunks_h_bytes[slot] = 0;
+        const size_t want = h_need + h_need / 4 + 4096;
+        if (hipHostMalloc(&ctx->chunks_h[slot], want, hipHostMallocDefault) != hipSuccess) {
+            ctx->chunks_h[slot] = nullptr;
+            (void)hipGetLastError();
+            return RC_MEM_ERROR;
+        }
+        ctx->chunks_h_bytes[slot] = want;
+    }
+    DChunkDesc *h_desc = static_cast<DChunkDesc *>(ctx->chunks_h[slot]);
+    DChunksShape sh;
+    if (!dchunks_shape(p, in_offsets, in_bytes_each, out_offsets, out_bytes, n_chunks, &sh, h_desc)) return RC_CONF_ERROR;
+    if (sh.desc_bytes + sh.table_bytes > ctx->chunks_d_bytes) {
+        if (ctx->chunks_d) (void)hipFree(ctx->chunks_d);           // (synchronises: no kernel still reads it)
+        ctx->chunks_d = nullptr;
+        ctx->chunks_d_bytes = 0;
+        const size_t want = up256(sh.desc_bytes + sh.table_bytes + (sh.desc_bytes + sh.table_bytes) / 4);
+        if (hipMalloc(&ctx->chunks_d, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return RC_MEM_ERROR;
+        }
+        ctx->chunks_d_bytes = want;
+    }
+    (void)hipGetLastError();
+    uint8_t *cd = static_cast<uint8_t *>(ctx->chunks_d);
+    if (hipMemcpyAsync(cd, h_desc, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipEventRecord(ctx->chunks_ev[slot], st) != hipSuccess)
+        return RC_MEM_ERROR;
+    const DChunkDesc *d_desc = reinterpret_cast<const DChunkDesc *>(cd);
+    uint32_t *d_item_chunk = reinterpret_cast<uint32_t *>(cd + sh.desc_bytes);
+    DecResult *records = reinterpret_cast<DecResult *>(d_results);
+    launch_dchunks_setup(sh.c, d_desc, n_chunks, sh.items, d_item_chunk, have_table ? records : nullptr, st);
+    if (!have_table)
+        launch_index_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_desc, n_chunks, d_rsi_bit_offsets, records, st);
+    // (bits per coded data set, from what the chunks announce: sizes the rings of the lane kernel)
+    const uint64_t avg = sh.blocks ? (uint64_t)in_bytes * 8 / sh.blocks : 0;
+    if (!launch_decode_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, d_desc, d_item_chunk,
+                              sh.items, avg, static_cast<uint8_t *>(d_out), records, reinterpret_cast<DecResult *>(d_result), st,
+                              ctx->dec_events()))
+        return RC_MEM_ERROR;
     return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
 }
 

@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "aec_dchunks.h"
 #include "aec_kernels.h"
 #include "aec_lane.h"
 #include "aec_spec.h"
@@ -2366,6 +2367,10 @@ struct LdsWindowFetch {
 // chunk_off != nullptr: workgroup s walks the independent stream that occupies bytes
 // [chunk_off[s], chunk_off[s+1]) of the buffer and writes rsi_off[s*max_rsi ..], res[s]; offsets are
 // absolute bit positions in the buffer, so ONE k_decode launch decodes the RSIs of all streams.
+// streams != nullptr (a batch of unequal chunks, aec_dchunks.h): workgroup s walks the stream of streams[s].in_bytes bytes
+// at byte streams[s].in_off -- any byte, the next stream may begin on the byte behind it, so the end bound is the only
+// thing that ends the walk of a stream cut short -- to at most streams[s].rsis RSIs, and writes their starts from entry
+// streams[s].item0 + s of the table on; res[s] as for chunk_off.
 __global__ void __launch_bounds__(64)
 k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64_t end_bit,
         uint64_t start_bit, uint64_t *__restrict__ rsi_off, uint64_t max_rsi, DecResult *res,
@@ -2374,7 +2379,8 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
         const TwTables sp, ChunkEntry *__restrict__ centry, const SparseTables s2,
         uint32_t *__restrict__ batch_nhops = nullptr, uint64_t stop_near = 0,
         const uint32_t *__restrict__ skip_if = nullptr, const SparseTables s2d = SparseTables{},
-        uint32_t serial_cap = 0, uint32_t *__restrict__ delivered = nullptr)
+        uint32_t serial_cap = 0, uint32_t *__restrict__ delivered = nullptr,
+        const DChunkDesc *__restrict__ streams = nullptr)
 {
     if (skip_if && *skip_if) return;                 // (the phase-locked chains have delivered everything: launch_index_locked)
     // serial_cap / delivered (launch_index_sparse, a small stream in one span): the tables resolve most RSIs of the streams
@@ -2393,7 +2399,15 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
     __shared__ uint16_t prank[kIdxPieceWords + 2];
     __shared__ uint16_t ones[kIdxPieceWords * 32];
     uint64_t r = 0;
-    if (chunk_off) {
+    const bool batch = chunk_off || streams;
+    if (streams) {
+        const DChunkDesc e = streams[blockIdx.x];
+        start_bit = e.in_off * 8u;
+        end_bit = (e.in_off + e.in_bytes) * 8u;
+        rsi_off += e.item0 + blockIdx.x;
+        max_rsi = e.rsis;
+        res += blockIdx.x;
+    } else if (chunk_off) {
         start_bit = chunk_off[blockIdx.x] * 8u;
         end_bit = chunk_off[blockIdx.x + 1] * 8u;
         rsi_off += (uint64_t)blockIdx.x * max_rsi;
@@ -2403,7 +2417,7 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
         return;
     }
     // the first walk of a call starts the result record (there is no separate init launch)
-    if (!chunk_off && first && threadIdx.x == 0) {
+    if (!batch && first && threadIdx.x == 0) {
         res->n_rsi = 0;
         res->tail_blocks = 0;
         res->end_bit = start_bit;
@@ -2420,7 +2434,7 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
         r = carry->r;
     }
     const uint32_t lane = threadIdx.x;
-    if (carry && !chunk_off && lane == 0) carry->r_prev = r;
+    if (carry && !batch && lane == 0) carry->r_prev = r;
     const bool pp = c.flags & F_PREPROCESS;
     const uint32_t maxw = (c.id_len + 1 + c.bps + c.bs * c.bps) / 32 + 4;   // words one CDS can touch
 
@@ -2555,7 +2569,7 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
     // Resumed walk (streaming callers): start_bit is a CDS boundary inside an RSI that began at
     // rsi_start and of which start_block blocks lie before start_bit.
     uint64_t cur_start = start_bit;          // start of the RSI being walked
-    if (first && !chunk_off && start_block) {
+    if (first && !batch && start_block) {
         b = start_block;
         cur_start = rsi_start;
         if (lane == 0 && max_rsi) rsi_off[0] = rsi_start;
@@ -2857,12 +2871,12 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
     if (lane == 0 && delivered) *delivered = 1u;
     if (lane == 0) {
         // streaming callers: where the trailing partial RSI began, in a slot of its own behind the table
-        if (tail_slot && !chunk_off) rsi_off[max_rsi] = cur_start;
+        if (tail_slot && !batch) rsi_off[max_rsi] = cur_start;
         res->n_rsi = r;
         res->tail_blocks = b;
         res->end_bit = good;
-        if (!chunk_off) res->pad = status == DEC_NEED_INPUT ? 1u : 0u;
-        if (chunk_off) {               // per-stream records are written in full (no init kernel)
+        if (!batch) res->pad = status == DEC_NEED_INPUT ? 1u : 0u;
+        if (batch) {               // per-stream records are written in full (no init kernel)
             res->status = status == DEC_DATA_ERROR ? DEC_DATA_ERROR : DEC_OK;
             res->pad = 0;
             res->bad_rsi = status == DEC_DATA_ERROR ? r : ~0ull;
@@ -3151,6 +3165,7 @@ void side_give(const SideStream &s)
 struct IdxVary {
     const uint32_t *skip_if = nullptr;
     const uint64_t *chunk_off = nullptr;   // a batch: n_chunks + 1 byte offsets, a workgroup per stream
+    const DChunkDesc *streams = nullptr;   // a batch of unequal chunks: n_chunks descriptors, a workgroup per stream
     uint64_t n_chunks = 1, stop_near = 0;
     IdxHop *hops = nullptr;                // the hops taken over the tables, for the expansion behind
     IdxCarry *carry = nullptr;             // spans of tables: the walker's state between them
@@ -3167,7 +3182,7 @@ void go_index(const IdxWalk &w, const IdxVary &v)
     hipLaunchKernelGGL(k_index, dim3((uint32_t)v.n_chunks), dim3(64), 0, w.st, w.c, w.words, w.nwords, w.end_bit, w.start_bit,
                        w.d_rsi_off, w.max_rsi, w.d_res, v.chunk_off, v.hops, v.hop_cap, v.carry, v.first, v.last, w.start_block,
                        w.rsi_start, w.tail_slot, v.tw, v.centry, v.s2, v.batch_nhops, v.stop_near, v.skip_if, v.dense,
-                       v.serial_cap, v.delivered);
+                       v.serial_cap, v.delivered, v.streams);
 }
 
 // The window tables of nwin windows from bit lo in the set of tables at tb (dense: the dense fallback's, behind them).
@@ -5711,6 +5726,19 @@ void launch_index_batch(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
                  .batch_nhops = nhops});
     hipLaunchKernelGGL(k_expand2, dim3((uint32_t)(((uint64_t)n_chunks * hop_cap + 255) / 256)), dim3(256), 0, st, t,
                        (const IdxCarry *)nullptr, hops, nhops, (uint32_t)n_chunks, hop_cap, d_rsi_off, rsi_per_chunk);
+}
+
+// The bare streams of a batch of unequal chunks (aec_dchunks.h): one wavefront per stream, the serial walk alone, from
+// the stream's first byte to its last; chunk s's RSI starts go to the table from entry d_desc[s].item0 + s on, its
+// record to d_res[s].
+void launch_index_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DChunkDesc *d_desc, uint64_t n_chunks,
+                         uint64_t *d_rsi_off, DecResult *d_res, hipStream_t st)
+{
+    if (n_chunks == 0) return;
+    idx_tuning_sync();
+    const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, 0, d_rsi_off,
+                    0, d_res, st, 0u, 0u, 0, nullptr, 0};
+    go_index(w, {.streams = d_desc, .n_chunks = n_chunks});
 }
 
 }  // namespace aec

@@ -144,6 +144,22 @@ bool launch_decode_range(const Cfg &c, const uint8_t *d_in, size_t in_bytes, con
                          bool next_entry, uint64_t total_blocks, uint8_t *d_out, DecResult *d_res, hipStream_t stream,
                          const PhaseEvents *prof = nullptr);
 
+// A batch of unequal chunks as ONE decode launch (aec_dchunks.h; aec_gpu_decode_chunks_async).  d_desc: the n + 1
+// descriptors on the device; launch_dchunks_setup fills d_item_chunk (one entry per item) and, when d_records is given,
+// the chunks' records from what the chunks announce (the caller's table) -- else launch_index_chunks (aec_idx.hip) walks
+// every chunk's bare stream, one wavefront each, and leaves table entries and records.  launch_decode_chunks then takes
+// every item's start from d_rsi_off (rsis_i + 1 entries per chunk), its block count from its chunk's record and what the
+// chunk announces, and its place from the chunk's out_off; a failing item raises its chunk's record to DEC_DATA_ERROR.
+struct DChunkDesc;
+void launch_dchunks_setup(const Cfg &c, const DChunkDesc *d_desc, uint64_t n, uint64_t items, uint32_t *d_item_chunk,
+                          DecResult *d_records, hipStream_t stream);
+void launch_index_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DChunkDesc *d_desc, uint64_t n_chunks,
+                         uint64_t *d_rsi_off, DecResult *d_res, hipStream_t stream);
+bool launch_decode_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off,
+                          const DChunkDesc *d_desc, const uint32_t *d_item_chunk, uint64_t items, uint64_t avg_cds_hint,
+                          uint8_t *d_out, DecResult *d_records, DecResult *d_res, hipStream_t stream,
+                          const PhaseEvents *prof = nullptr);
+
 // Samples of the coded data set the input ends in (single lane; see k_decode_partial): after
 // launch_decode with the same d_idx / d_out / d_res; their number is left in d_res->pad.
 void launch_decode_partial(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DecResult *d_idx,

@@ -20,6 +20,11 @@ class ChunksPlan(C.Structure):
                 ("waves", C.c_uint64)]
 
 
+class DChunksPlan(C.Structure):
+    _fields_ = [("items", C.c_uint64), ("rsi_entries", C.c_uint64), ("out_bytes", C.c_size_t),
+                ("workspace_bytes", C.c_size_t)]
+
+
 SEG_ENTRY_DTYPE = np.dtype([("bit", "<u8"), ("prev", "<u4"), ("pad", "<u4")])
 ENC_RESULT_DTYPE = np.dtype([("total_bits", "<u8"), ("k_out", "<u4"), ("overflow", "<u4"),
                              ("k_lo", "<u4"), ("k_hi", "<u4")])
@@ -81,6 +86,11 @@ def _lib():
         lib.aec_gpu_encode_chunks_plan.argtypes = [pp, vp, u64, C.POINTER(ChunksPlan)]
         lib.aec_gpu_encode_chunks_async.restype = C.c_int
         lib.aec_gpu_encode_chunks_async.argtypes = [vp, pp, vp, vp, vp, u64, vp, sz, vp, vp, vp, vp]
+        if hasattr(lib, "aec_gpu_decode_chunks_plan"):      # (AEC_AMD_LIB: a build from before the call)
+            lib.aec_gpu_decode_chunks_plan.restype = C.c_int
+            lib.aec_gpu_decode_chunks_plan.argtypes = [pp, vp, u64, C.POINTER(DChunksPlan)]
+            lib.aec_gpu_decode_chunks_async.restype = C.c_int
+            lib.aec_gpu_decode_chunks_async.argtypes = [vp, pp, vp, sz, vp, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp]
         lib.aec_gpu_index_async.restype = C.c_int
         lib.aec_gpu_index_async.argtypes = [vp, pp, vp, sz, u64, vp, u64, vp, vp]
         lib.aec_gpu_segments_per_rsi.restype = C.c_uint
@@ -145,6 +155,18 @@ def encode_chunks_plan(bits_per_sample, block_size, rsi, flags, sizes):
         return None
     return {"out_bound": int(plan.out_bound), "rsi_entries": int(plan.rsi_entries),
             "workspace_bytes": int(plan.workspace_bytes), "waves": int(plan.waves)}
+
+
+def decode_chunks_plan(bits_per_sample, block_size, rsi, flags, out_sizes):
+    """aec_gpu_decode_chunks_plan: host arithmetic of a batch of chunks that decode to `out_sizes` bytes.  Returns the dict
+    {items, rsi_entries, out_bytes, workspace_bytes}, or None where the batch would be refused."""
+    p = Params(bits_per_sample, block_size, rsi, flags)
+    a = np.ascontiguousarray(out_sizes, dtype=np.uint64)
+    plan = DChunksPlan()
+    if not _lib().aec_gpu_decode_chunks_plan(C.byref(p), C.c_void_p(a.ctypes.data), a.size, C.byref(plan)):
+        return None
+    return {"items": int(plan.items), "rsi_entries": int(plan.rsi_entries), "out_bytes": int(plan.out_bytes),
+            "workspace_bytes": int(plan.workspace_bytes)}
 
 
 class Codec:
@@ -386,6 +408,59 @@ class Codec:
         rec = d_rec.cpu().numpy().reshape(-1, 2)[:n]
         res = d_res.cpu().numpy().view(ENC_RESULT_DTYPE)[0]
         return d_out, rec, d_tab, res
+
+    def decode_chunks_plan(self, out_sizes):
+        return decode_chunks_plan(self.p.bits_per_sample, self.p.block_size, self.p.rsi, self.p.flags, out_sizes)
+
+    def decode_chunks_async(self, d_in, in_bytes, in_offsets, in_sizes, out_offsets, out_sizes, d_table, have_table, d_out,
+                            d_records, d_result, stream=None):
+        """aec_gpu_decode_chunks_async as it is: the four arrays are uint64 numpy arrays on the host (in_offsets / in_sizes
+        may be None with a table), d_table an int64 tensor of the plan's rsi_entries, d_records a uint8 tensor of 40 n
+        bytes, d_result one of 40 bytes.  Returns the call's return code."""
+        def host(a):
+            return C.c_void_p(a.ctypes.data) if a is not None else None
+        return self.lib.aec_gpu_decode_chunks_async(
+            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, host(in_offsets), host(in_sizes),
+            host(out_offsets), host(out_sizes), int(out_sizes.size), C.c_void_p(d_table.data_ptr()), int(have_table),
+            C.c_void_p(d_out.data_ptr()), C.c_void_p(d_records.data_ptr()), C.c_void_p(d_result.data_ptr()),
+            self._stream(stream))
+
+    def decode_chunks(self, d_in, in_bytes, out_sizes, d_table=None, in_offsets=None, in_sizes=None):
+        """Streams that decode to out_sizes[i] bytes, as one decode launch (include/aec_gpu.h:
+        aec_gpu_decode_chunks_async) into a packed output allocated here.  With d_table (the int64 RSI table of
+        encode_chunks(..., want_offsets=True), positions relative to d_in) no index pass runs; without it the streams are
+        in_sizes[i] bytes at byte in_offsets[i] of d_in and are walked first.  Returns (d_out, out_offsets, records,
+        result): chunk i's whole blocks at d_out[out_offsets[i]:], records the DEC_RESULT_DTYPE record per chunk, result
+        the overall one.  Synchronises."""
+        torch = self.torch
+        osz = np.ascontiguousarray(out_sizes, dtype=np.uint64)
+        plan = self.decode_chunks_plan(osz)
+        if plan is None:
+            raise ValueError("aec_gpu_decode_chunks_plan refuses this batch")
+        n = int(osz.size)
+        bps = self.p.bits_per_sample
+        nb = 4 if bps > 16 and not (bps <= 24 and self.p.flags & 2) else (3 if bps > 16 else (2 if bps > 8 else 1))
+        blk = self.p.block_size * nb
+        rooms = [((int(b) // nb + self.p.block_size - 1) // self.p.block_size * blk + 15) // 16 * 16 for b in osz]
+        ooff = np.zeros(n, dtype=np.uint64)
+        if n:
+            ooff[1:] = np.cumsum(rooms[:-1], dtype=np.uint64)
+        ioff = np.ascontiguousarray(in_offsets, dtype=np.uint64) if in_offsets is not None else None
+        isz = np.ascontiguousarray(in_sizes, dtype=np.uint64) if in_sizes is not None else None
+        if d_table is None and (ioff is None or isz is None or ioff.size != n or isz.size != n):
+            raise ValueError("bare streams need in_offsets and in_sizes, one entry per chunk")
+        have = d_table is not None
+        if not have:
+            d_table = torch.zeros(max(plan["rsi_entries"], 1), dtype=torch.int64, device=d_in.device)
+        d_out = torch.empty(plan["out_bytes"] + 16, dtype=torch.uint8, device=d_in.device)
+        d_rec = torch.zeros(max(n, 1) * DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
+        d_res = torch.zeros(DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
+        rc = self.decode_chunks_async(d_in, in_bytes, ioff, isz, ooff, osz, d_table, have, d_out, d_rec, d_res)
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_decode_chunks_async failed ({rc})")
+        rec = d_rec.cpu().numpy().view(DEC_RESULT_DTYPE)[:n]
+        res = d_res.cpu().numpy().view(DEC_RESULT_DTYPE)[0]
+        return d_out[: plan["out_bytes"]], ooff, rec, res
 
     # ---- convenience (synchronising) -------------------------------------------------------------
     def encode(self, d_in, start_bit=0, k_in=0):
