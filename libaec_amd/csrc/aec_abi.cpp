@@ -20,8 +20,10 @@
 //
 // The mechanisms every entry point shares are each stated once: a stream's device belongings (Kit: obtain_kit /
 // give_kit), the hand-out of what a batch produced (hand_out), the copy to the caller beside the next batch (SideCopy),
-// many chunks through pinned staging (stage_up / stage_down).  The arithmetic of a decode batch -- its bounds, the
-// verdict over its result records, the advance of the stream's position -- is pure and lives in aec_stream_plan.h.
+// many chunks through pinned staging (stage_up / stage_down).  The kit's device buffers are DevBufs (aec_devbuf.h, shared
+// with the context in aec_gpu.hip), grown by ensure(), which keeps their contents.  The arithmetic of a decode batch -- its
+// bounds, the verdict over its result records, the advance of the stream's position -- is pure and lives in
+// aec_stream_plan.h.
 //
 // There is no CPU codec in here: without a working HIP device every call fails with AEC_MEM_ERROR.
 #include <hip/hip_runtime.h>
@@ -41,6 +43,7 @@
 #include "../../include/aec_gpu.h"
 #include "../../include/libaec.h"
 #include "aec_cfg.h"
+#include "aec_devbuf.h"
 #include "aec_pool.h"
 #include "aec_stream_plan.h"
 #include "aec_tune.h"
@@ -63,37 +66,6 @@ int fail_at(int code, int line)
     return code;
 }
 #define AEC_FAIL(code) fail_at((code), __LINE__)
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    // keep: bytes at the front that must survive a reallocation (copied device to device)
-    bool ensure(size_t n, size_t keep = 0)
-    {
-        if (n <= cap) return true;
-        size_t want = n + n / 4 + 256;
-        want = (want + 255) & ~(size_t)255;
-        void *q = nullptr;
-        if (hipMalloc(&q, want) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (p && keep && hipMemcpy(q, p, keep, hipMemcpyDeviceToDevice) != hipSuccess) {
-            (void)hipFree(q);
-            return false;
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = want;
-        return true;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 // batching thresholds (kMinBatchOut and kPipeOut, which bound a decode batch: aec_stream_plan.h)
 constexpr size_t kEncBatchBytes = (size_t)1 << 20;   // staged input that is worth a launch without AEC_FLUSH

@@ -12,21 +12,20 @@
 
 #include "aec_chunks.h"
 #include "aec_dchunks.h"
+#include "aec_devbuf.h"
 #include "aec_kernels.h"
 
 using namespace aec;
 
 struct aec_gpu_ctx {
-    int device;
-    void *ws;          // encoder workspace
-    size_t ws_bytes;
-    bool profiling;    // record PhaseEvents around the kernels of the next calls
+    int device = 0;
+    bool profiling = false;    // record PhaseEvents around the kernels of the next calls
     // One event set per call, in a ring, so that a caller can time every launch of a loop without
     // synchronising inside it; aec_gpu_phase_ms() averages over the sets recorded since profiling
     // was switched on (the last kProfRing of them).
     static constexpr unsigned kProfRing = 32;
-    PhaseEvents ev[kProfRing];
-    unsigned enc_calls, dec_calls;
+    PhaseEvents ev[kProfRing] = {};
+    unsigned enc_calls = 0, dec_calls = 0;
     // an emit-only call continues the set its plan call opened (its "scan" then spans the host's
     // plan exchange between the two calls)
     const PhaseEvents *enc_events(uint32_t phases)
@@ -36,29 +35,31 @@ struct aec_gpu_ctx {
         return &ev[(enc_calls - 1) % kProfRing];
     }
     const PhaseEvents *dec_events() { return profiling ? &ev[dec_calls++ % kProfRing] : nullptr; }
-    SegEntry *seg_table;   // where the next encode / emit calls also leave the segment table (or null)
-    void *idx_ws;          // speculative index tables (aec_idx.hip), grown on demand
-    size_t idx_ws_bytes;
-    uint64_t idx_hint;     // caller's estimate of the coded RSI size in bits (0 = derive from max_rsi)
-    uint64_t idx_used_hint;  // ... and what the last index pass worked with (sizes the rings of the decode behind it)
-    bool seg_filled;       // the last index pass with a segment-start table filled it (it ran over the trunk tables)
-    uint64_t idx_stop_near;  // the next index pass is a piece of a longer stream (aec_gpu_set_index_piece)
-    void *dec_ws;          // workspace of the segment-wise decode of bare streams (aec_dec.hip: launch_decode_bare)
-    size_t dec_ws_bytes;
-    ShardCarry *carry;     // device record: what precedes this context's shard (emit_planned)
-    void *fused;           // control block of the single-pass encoder (ticket, fail flag, look-back granules)
-    size_t fused_bytes;
-    void *range_ws;        // whole blocks of a range decode whose window does not start on an RSI / end on a block
-    size_t range_ws_bytes;
-    // aec_gpu_encode_chunks_async / aec_gpu_decode_chunks_async: the chunk descriptors and the per-wave / per-item table
-    // on the device, and the pinned buffers the descriptors are written to on the host -- two, taken in turn, each guarded by the event of its last transfer
-    void *chunks_d;
-    size_t chunks_d_bytes;
+    SegEntry *seg_table = nullptr;   // where the next encode / emit calls also leave the segment table (or null)
+    uint64_t idx_hint = 0;     // caller's estimate of the coded RSI size in bits (0 = derive from max_rsi)
+    uint64_t idx_used_hint = 0;  // ... and what the last index pass worked with (sizes the rings of the decode behind it)
+    bool seg_filled = false;   // the last index pass with a segment-start table filled it (it ran over the trunk tables)
+    uint64_t idx_stop_near = 0;  // the next index pass is a piece of a longer stream (aec_gpu_set_index_piece)
+
+    // Device memory, grown on demand (aec_devbuf.h: replace) and kept between calls:
+    DevBuf ws;             // workspace of the two-pass encoder (plan / emit: per-block summaries, segment scan)
+    DevBuf fused;          // control block of the single-pass encoder (ticket, fail flag, look-back granules)
+    DevBuf idx_ws;         // speculative index tables (aec_idx.hip)
+    DevBuf dec_ws;         // workspace of the segment-wise decode of bare streams (aec_dec.hip: launch_decode_bare)
+    DevBuf range_ws;       // whole blocks of a range decode whose window does not start on an RSI / end on a block
+    DevBuf chunks_d;       // the chunk calls: the descriptors and the per-wave / per-item table
+    // ... of which aec_gpu_held_bytes counts, aec_gpu_trim frees and aec_gpu_destroy releases these: a new one goes here
+    // (pointers into the context itself, which is never copied)
+    DevBuf *const held[6] = {&ws, &fused, &idx_ws, &dec_ws, &range_ws, &chunks_d};
+    DevBuf carry;          // device record: what precedes this context's shard (emit_planned); a ShardCarry, never trimmed
+    // the pinned buffers the chunk calls write their descriptors to -- kChunkStages, taken in turn, each guarded by the
+    // event of its last transfer (stage_descriptors / send_descriptors); never trimmed
     static constexpr unsigned kChunkStages = 2;
-    void *chunks_h[kChunkStages];
-    size_t chunks_h_bytes[kChunkStages];
-    hipEvent_t chunks_ev[kChunkStages];
-    unsigned chunks_calls;
+    struct ChunkStage {
+        DevBuf h{true};
+        hipEvent_t ev = nullptr;
+    } stage[kChunkStages];
+    unsigned chunks_calls = 0;
 };
 static_assert(sizeof(aec_gpu_seg_entry) == sizeof(SegEntry), "segment table layout");
 
@@ -79,34 +80,6 @@ int aec_gpu_create(aec_gpu_ctx **out)
     aec_gpu_ctx *ctx = new (std::nothrow) aec_gpu_ctx;
     if (!ctx) return RC_MEM_ERROR;
     ctx->device = dev;
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-    ctx->profiling = false;
-    ctx->seg_table = nullptr;
-    ctx->idx_ws = nullptr;
-    ctx->idx_ws_bytes = 0;
-    ctx->idx_hint = 0;
-    ctx->idx_used_hint = 0;
-    ctx->seg_filled = false;
-    ctx->idx_stop_near = 0;
-    ctx->dec_ws = nullptr;
-    ctx->dec_ws_bytes = 0;
-    ctx->carry = nullptr;
-    ctx->fused = nullptr;
-    ctx->fused_bytes = 0;
-    ctx->range_ws = nullptr;
-    ctx->range_ws_bytes = 0;
-    ctx->enc_calls = ctx->dec_calls = 0;
-    for (auto &set : ctx->ev)
-        for (auto &e : set.ev) e = nullptr;
-    ctx->chunks_d = nullptr;
-    ctx->chunks_d_bytes = 0;
-    ctx->chunks_calls = 0;
-    for (unsigned i = 0; i < aec_gpu_ctx::kChunkStages; i++) {
-        ctx->chunks_h[i] = nullptr;
-        ctx->chunks_h_bytes[i] = 0;
-        ctx->chunks_ev[i] = nullptr;
-    }
     *out = ctx;
     return RC_OK;
 }
@@ -114,16 +87,11 @@ int aec_gpu_create(aec_gpu_ctx **out)
 void aec_gpu_destroy(aec_gpu_ctx *ctx)
 {
     if (!ctx) return;
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->idx_ws) (void)hipFree(ctx->idx_ws);
-    if (ctx->dec_ws) (void)hipFree(ctx->dec_ws);
-    if (ctx->carry) (void)hipFree(ctx->carry);
-    if (ctx->fused) (void)hipFree(ctx->fused);
-    if (ctx->range_ws) (void)hipFree(ctx->range_ws);
-    if (ctx->chunks_d) (void)hipFree(ctx->chunks_d);
-    for (unsigned i = 0; i < aec_gpu_ctx::kChunkStages; i++) {
-        if (ctx->chunks_h[i]) (void)hipHostFree(ctx->chunks_h[i]);
-        if (ctx->chunks_ev[i]) (void)hipEventDestroy(ctx->chunks_ev[i]);
+    for (DevBuf *b : ctx->held) b->release();
+    ctx->carry.release();
+    for (auto &s : ctx->stage) {
+        s.h.release();
+        if (s.ev) (void)hipEventDestroy(s.ev);
     }
     for (auto &set : ctx->ev)
         for (auto &e : set.ev)
@@ -158,35 +126,43 @@ uint64_t aec_gpu_block_count(const aec_gpu_params *p, size_t in_bytes)
     return c.total_blocks;
 }
 
-// workspace of the two-pass encoder (plan / emit: per-block summaries, segment scan)
-static int reserve_two_pass(aec_gpu_ctx *ctx, const Cfg &c)
+// reserves the workspace of the two-pass encoder for c (exactly what it needs) and points ws into it
+static int reserve_two_pass(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws)
 {
     size_t o[6];
     const size_t need = enc_workspace_bytes(c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]);
-    if (need > ctx->ws_bytes) {
-        if (ctx->ws) (void)hipFree(ctx->ws);
-        ctx->ws = nullptr;
-        ctx->ws_bytes = 0;
-        if (hipMalloc(&ctx->ws, need) != hipSuccess) return RC_MEM_ERROR;
-        ctx->ws_bytes = need;
-    }
+    if (!ctx->ws.replace(need, need)) return RC_MEM_ERROR;
+    uint8_t *base = static_cast<uint8_t *>(ctx->ws.p);
+    *ws = EncWorkspace{};
+    ws->meta = reinterpret_cast<uint32_t *>(base + o[0]);
+    ws->seg_bits = reinterpret_cast<uint32_t *>(base + o[1]);
+    ws->seg_clamp = reinterpret_cast<uint16_t *>(base + o[2]);
+    ws->seg_start = reinterpret_cast<uint64_t *>(base + o[3]);
+    ws->seg_kin = base + o[4];
+    ws->partials = reinterpret_cast<ScanPartial *>(base + o[5]);
     return RC_OK;
 }
 
-// control block of the single-pass encoder (16 bytes per 4..16 segments)
-static int reserve_fused(aec_gpu_ctx *ctx, const Cfg &c)
+// ... and the control block of the single-pass encoder (16 bytes per 4..16 segments)
+static int reserve_fused(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws)
 {
     const size_t need = fused_ctl_bytes(c);
-    if (need > ctx->fused_bytes) {
-        if (ctx->fused) (void)hipFree(ctx->fused);
-        ctx->fused = nullptr;
-        ctx->fused_bytes = 0;
-        const size_t want = need + need / 16;
-        if (hipMalloc(&ctx->fused, want) != hipSuccess) return RC_MEM_ERROR;
-        ctx->fused_bytes = want;
-    }
+    if (!ctx->fused.replace(need, need + need / 16)) return RC_MEM_ERROR;
+    *ws = EncWorkspace{};
+    ws->fused_ctl = ctx->fused.p;
     return RC_OK;
 }
+
+// the one condition every enqueueing call closes on: no launch of this call has failed
+static int launched() { return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR; }
+
+// the public records, tables and chunk records are the kernels' own (the static_asserts above and below)
+static EncResult *rec(aec_gpu_enc_result *r) { return reinterpret_cast<EncResult *>(r); }
+static const EncResult *rec(const aec_gpu_enc_result *r) { return reinterpret_cast<const EncResult *>(r); }
+static DecResult *rec(aec_gpu_dec_result *r) { return reinterpret_cast<DecResult *>(r); }
+static const DecResult *rec(const aec_gpu_dec_result *r) { return reinterpret_cast<const DecResult *>(r); }
+static const SegEntry *segs(const aec_gpu_seg_entry *t) { return reinterpret_cast<const SegEntry *>(t); }
+static BatchChunk *chunk_recs(aec_gpu_batch_chunk *c) { return reinterpret_cast<BatchChunk *>(c); }
 
 int aec_gpu_reserve(aec_gpu_ctx *ctx, const aec_gpu_params *p, size_t in_bytes)
 {
@@ -195,7 +171,8 @@ int aec_gpu_reserve(aec_gpu_ctx *ctx, const aec_gpu_params *p, size_t in_bytes)
     if (rc != RC_OK) return rc;
     // what aec_gpu_encode_async needs; the (much larger) workspace of the plan / emit pair is
     // allocated by the first plan call
-    return fused_supported(c) ? reserve_fused(ctx, c) : reserve_two_pass(ctx, c);
+    EncWorkspace ws;
+    return fused_supported(c) ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws);
 }
 
 static int encode_phases(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -210,28 +187,14 @@ static int encode_phases(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *
     if ((phases & ENC_EMIT) && ((reinterpret_cast<uintptr_t>(d_out) & 15u) || (out_cap & 15u) || out_cap < 16))
         return RC_CONF_ERROR;
     const bool fused = phases == ENC_ALL && !d_carry && fused_supported(c);
-    rc = fused ? reserve_fused(ctx, c) : reserve_two_pass(ctx, c);
+    EncWorkspace ws;
+    rc = fused ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws);
     if (rc != RC_OK) return rc;
     (void)hipGetLastError();   // only launch errors of THIS call are reported below
-    EncWorkspace ws{};
-    if (fused) {
-        ws.fused_ctl = ctx->fused;
-    } else {
-        size_t o[6];
-        enc_workspace_bytes(c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]);
-        uint8_t *base = static_cast<uint8_t *>(ctx->ws);
-        ws.meta = reinterpret_cast<uint32_t *>(base + o[0]);
-        ws.seg_bits = reinterpret_cast<uint32_t *>(base + o[1]);
-        ws.seg_clamp = reinterpret_cast<uint16_t *>(base + o[2]);
-        ws.seg_start = reinterpret_cast<uint64_t *>(base + o[3]);
-        ws.seg_kin = base + o[4];
-        ws.partials = reinterpret_cast<ScanPartial *>(base + o[5]);
-        ws.fused_ctl = nullptr;
-    }
     launch_encode(c, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), out_cap, start_bit,
-                  k_in, ws, d_rsi_bit_offsets, reinterpret_cast<EncResult *>(d_result),
-                  static_cast<hipStream_t>(stream), ctx->enc_events(phases), phases, ctx->seg_table, d_carry);
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+                  k_in, ws, d_rsi_bit_offsets, rec(d_result), static_cast<hipStream_t>(stream), ctx->enc_events(phases),
+                  phases, ctx->seg_table, d_carry);
+    return launched();
 }
 
 int aec_gpu_encode_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -262,15 +225,11 @@ int aec_gpu_encode_emit_planned_async(aec_gpu_ctx *ctx, const aec_gpu_params *p,
                                       void *stream)
 {
     if (!d_plans || rank >= 64) return RC_CONF_ERROR;
-    if (!ctx->carry && hipMalloc(reinterpret_cast<void **>(&ctx->carry), sizeof(ShardCarry)) != hipSuccess) {
-        ctx->carry = nullptr;
-        (void)hipGetLastError();
-        return RC_MEM_ERROR;
-    }
-    launch_shard_carry(reinterpret_cast<const EncResult *>(d_plans), rank, ctx->carry,
-                       static_cast<hipStream_t>(stream));
+    if (!ctx->carry.replace(sizeof(ShardCarry), sizeof(ShardCarry))) return RC_MEM_ERROR;
+    ShardCarry *carry = static_cast<ShardCarry *>(ctx->carry.p);
+    launch_shard_carry(rec(d_plans), rank, carry, static_cast<hipStream_t>(stream));
     return encode_phases(ctx, p, d_in, in_bytes, d_out, out_cap, 0, 0, d_rsi_bit_offsets, d_result, stream,
-                         ENC_EMIT, ctx->carry);
+                         ENC_EMIT, carry);
 }
 
 int aec_gpu_stitch_async(const void *d_gathered, size_t slot_bytes, const aec_gpu_enc_result *d_plans,
@@ -281,10 +240,9 @@ int aec_gpu_stitch_async(const void *d_gathered, size_t slot_bytes, const aec_gp
         (reinterpret_cast<uintptr_t>(d_gathered) & 15u) || (reinterpret_cast<uintptr_t>(d_stream) & 15u))
         return RC_CONF_ERROR;
     (void)hipGetLastError();
-    launch_stitch(static_cast<const uint8_t *>(d_gathered), slot_bytes, reinterpret_cast<const EncResult *>(d_plans),
-                  world, static_cast<uint8_t *>(d_stream), stream_cap, d_total_bytes,
-                  static_cast<hipStream_t>(stream));
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    launch_stitch(static_cast<const uint8_t *>(d_gathered), slot_bytes, rec(d_plans), world, static_cast<uint8_t *>(d_stream),
+                  stream_cap, d_total_bytes, static_cast<hipStream_t>(stream));
+    return launched();
 }
 
 int aec_gpu_decode_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -298,10 +256,9 @@ int aec_gpu_decode_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *
     if (n_rsi && (total_blocks > n_rsi * c.rsi || total_blocks <= (n_rsi - 1) * c.rsi)) return RC_CONF_ERROR;
     (void)hipGetLastError();
     if (!launch_decode(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, n_rsi, total_blocks,
-                       static_cast<uint8_t *>(d_out), reinterpret_cast<DecResult *>(d_result),
-                       static_cast<hipStream_t>(stream), ctx->dec_events()))
+                       static_cast<uint8_t *>(d_out), rec(d_result), static_cast<hipStream_t>(stream), ctx->dec_events()))
         return RC_MEM_ERROR;
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    return launched();
 }
 
 int aec_gpu_decode_range_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -314,13 +271,13 @@ int aec_gpu_decode_range_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const 
     if (reinterpret_cast<uintptr_t>(d_in) & 3u) return RC_CONF_ERROR;
     const uint64_t blk_bytes = (uint64_t)c.bs * c.bytes, rsi_bytes = blk_bytes * c.rsi;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    DecResult *res = reinterpret_cast<DecResult *>(d_result);
+    DecResult *res = rec(d_result);
     (void)hipGetLastError();
     if (size == 0) {
         if (!launch_decode_range(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, 0, false, 0, nullptr,
                                  res, st))
             return RC_MEM_ERROR;
-        return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+        return launched();
     }
     if (pos + size < pos) return RC_CONF_ERROR;
     // the RSIs the window needs, and its blocks from the first of them on: the last RSI ends behind the block that
@@ -335,25 +292,15 @@ int aec_gpu_decode_range_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const 
     const bool direct = pos == first && size % blk_bytes == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
     if (!direct) {
         const size_t need = (size_t)(total_blocks * blk_bytes);
-        if (ctx->range_ws_bytes < need) {
-            if (ctx->range_ws) (void)hipFree(ctx->range_ws);
-            ctx->range_ws = nullptr;
-            ctx->range_ws_bytes = 0;
-            const size_t want = (need + need / 4 + 255) & ~(size_t)255;
-            if (hipMalloc(&ctx->range_ws, want) != hipSuccess) {
-                (void)hipGetLastError();
-                return RC_MEM_ERROR;
-            }
-            ctx->range_ws_bytes = want;
-        }
-        out = static_cast<uint8_t *>(ctx->range_ws);
+        if (!ctx->range_ws.replace(need, (need + need / 4 + 255) & ~(size_t)255)) return RC_MEM_ERROR;
+        out = static_cast<uint8_t *>(ctx->range_ws.p);
     }
     if (!launch_decode_range(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets + r0, n_rsi,
                              r1 + 1 < n_offsets, total_blocks, out, res, st, ctx->dec_events()))
         return RC_MEM_ERROR;
     if (!direct && hipMemcpyAsync(d_out, out + (pos - first), (size_t)size, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return RC_MEM_ERROR;
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    return launched();
 }
 
 uint64_t aec_gpu_segment_count(const aec_gpu_params *p, size_t in_bytes)
@@ -380,12 +327,11 @@ int aec_gpu_decode_segments_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, con
     const uint64_t full = total_blocks / c.rsi, rem = total_blocks % c.rsi;
     if (n_seg != full * c.segs_per_rsi + (rem + 63) / 64) return RC_CONF_ERROR;
     (void)hipGetLastError();
-    if (!launch_decode_segments(c, static_cast<const uint8_t *>(d_in), in_bytes,
-                                reinterpret_cast<const SegEntry *>(d_seg_table), n_seg, total_blocks,
-                                static_cast<uint8_t *>(d_out), reinterpret_cast<DecResult *>(d_result),
-                                static_cast<hipStream_t>(stream), ctx->dec_events()))
+    if (!launch_decode_segments(c, static_cast<const uint8_t *>(d_in), in_bytes, segs(d_seg_table), n_seg, total_blocks,
+                                static_cast<uint8_t *>(d_out), rec(d_result), static_cast<hipStream_t>(stream),
+                                ctx->dec_events()))
         return RC_MEM_ERROR;
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    return launched();
 }
 
 static int index_common(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -405,35 +351,25 @@ static int index_common(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d
     const uint64_t hint = ctx->idx_hint ? ctx->idx_hint
                           : ((max_rsi && in_bits > start_bit) ? (in_bits - start_bit) / max_rsi : 0);
     const size_t need = index_workspace_bytes(c, in_bytes, start_bit, hint);
-    if (need > ctx->idx_ws_bytes) {
-        if (ctx->idx_ws) (void)hipFree(ctx->idx_ws);     // (synchronises: no walker still reads it)
-        ctx->idx_ws = nullptr;
-        ctx->idx_ws_bytes = 0;
-        const size_t want = need + need / 16;
-        if (hipMalloc(&ctx->idx_ws, want) == hipSuccess) {
-            ctx->idx_ws_bytes = want;
-        } else {
-            // (the every-bit scheme's tables are the largest by far for what they serve -- up to 270 MB for a 2 MiB
-            // stream: without them before the serial walk)
-            (void)hipGetLastError();
-            const size_t less = index_workspace_bytes_large(c, in_bytes, start_bit, hint);
-            if (less && less < need && hipMalloc(&ctx->idx_ws, less) == hipSuccess) ctx->idx_ws_bytes = less;
-            else (void)hipGetLastError();
-        }
+    if (!ctx->idx_ws.replace(need, need + need / 16)) {
+        // (the every-bit scheme's tables are the largest by far for what they serve -- up to 270 MB for a 2 MiB
+        // stream: without them before the serial walk)
+        const size_t less = index_workspace_bytes_large(c, in_bytes, start_bit, hint);
+        if (less && less < need) (void)ctx->idx_ws.replace(less, less);
     }
     ctx->idx_used_hint = hint;
     if (d_seg_bits && !decode_bare_supported(c)) d_seg_bits = nullptr;
     if (d_seg_bits && hipMemsetAsync(d_seg_bits, 0xFF, (size_t)(max_rsi + 1) * c.segs_per_rsi * 8, static_cast<hipStream_t>(stream)) != hipSuccess)
         return RC_MEM_ERROR;
     ctx->seg_filled = launch_index(c, static_cast<const uint8_t *>(d_in), in_bytes, start_bit, d_rsi_bit_offsets, max_rsi,
-                                   reinterpret_cast<DecResult *>(d_result), static_cast<hipStream_t>(stream), ctx->idx_ws,
-                                   ctx->idx_ws_bytes, hint, start_block, rsi_start_bit, tail_slot, d_seg_bits, ctx->idx_stop_near);
+                                   rec(d_result), static_cast<hipStream_t>(stream), ctx->idx_ws.p,
+                                   ctx->idx_ws.cap, hint, start_block, rsi_start_bit, tail_slot, d_seg_bits, ctx->idx_stop_near);
     ctx->idx_stop_near = 0;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess && getenv("AEC_ABI_TRACE"))
         fprintf(stderr, "aec_gpu_index_async: %s (in_bytes %zu start %llu max_rsi %llu hint %llu ws %zu)\n",
                 hipGetErrorString(e), in_bytes, (unsigned long long)start_bit, (unsigned long long)max_rsi,
-                (unsigned long long)hint, ctx->idx_ws_bytes);
+                (unsigned long long)hint, ctx->idx_ws.cap);
     return e == hipSuccess ? RC_OK : RC_MEM_ERROR;
 }
 
@@ -466,14 +402,12 @@ int aec_gpu_decode_indexed_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, cons
         return RC_CONF_ERROR;
     (void)hipGetLastError();
     if (!launch_decode(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, max_rsi,
-                       max_rsi * c.rsi, static_cast<uint8_t *>(d_out), reinterpret_cast<DecResult *>(d_result),
-                       static_cast<hipStream_t>(stream), ctx->dec_events(),
-                       reinterpret_cast<const DecResult *>(d_index_result)))
+                       max_rsi * c.rsi, static_cast<uint8_t *>(d_out), rec(d_result), static_cast<hipStream_t>(stream),
+                       ctx->dec_events(), rec(d_index_result)))
         return RC_MEM_ERROR;
-    launch_decode_partial(c, static_cast<const uint8_t *>(d_in), in_bytes,
-                          reinterpret_cast<const DecResult *>(d_index_result), static_cast<uint8_t *>(d_out),
-                          reinterpret_cast<DecResult *>(d_result), static_cast<hipStream_t>(stream));
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    launch_decode_partial(c, static_cast<const uint8_t *>(d_in), in_bytes, rec(d_index_result),
+                          static_cast<uint8_t *>(d_out), rec(d_result), static_cast<hipStream_t>(stream));
+    return launched();
 }
 
 unsigned int aec_gpu_segments_per_rsi(const aec_gpu_params *p)
@@ -505,24 +439,18 @@ int aec_gpu_decode_bare_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const v
     const bool seg = d_seg_bits && ctx->seg_filled && decode_bare_supported(c);
     if (seg) {
         const size_t need = decode_bare_workspace_bytes(c, max_rsi);
-        if (need > ctx->dec_ws_bytes) {
-            if (ctx->dec_ws) (void)hipFree(ctx->dec_ws);
-            ctx->dec_ws = nullptr;
-            ctx->dec_ws_bytes = 0;
-            if (hipMalloc(&ctx->dec_ws, need + need / 8) == hipSuccess) ctx->dec_ws_bytes = need + need / 8;
-            else (void)hipGetLastError();
-        }
+        (void)ctx->dec_ws.replace(need, need + need / 8);      // (a failure: every RSI by one lane)
     }
-    const DecResult *idx = reinterpret_cast<const DecResult *>(d_index_result);
+    const DecResult *idx = rec(d_index_result);
     if (!launch_decode_bare(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, seg ? d_seg_bits : nullptr,
                             max_rsi, idx ? max_rsi * c.rsi : total_blocks, static_cast<uint8_t *>(d_out),
-                            reinterpret_cast<DecResult *>(d_result), static_cast<hipStream_t>(stream), ctx->dec_events(),
-                            idx, ctx->dec_ws, ctx->dec_ws_bytes, ctx->idx_used_hint / c.rsi))
+                            rec(d_result), static_cast<hipStream_t>(stream), ctx->dec_events(),
+                            idx, ctx->dec_ws.p, ctx->dec_ws.cap, ctx->idx_used_hint / c.rsi))
         return RC_MEM_ERROR;
     if (idx)
         launch_decode_partial(c, static_cast<const uint8_t *>(d_in), in_bytes, idx, static_cast<uint8_t *>(d_out),
-                              reinterpret_cast<DecResult *>(d_result), static_cast<hipStream_t>(stream));
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+                              rec(d_result), static_cast<hipStream_t>(stream));
+    return launched();
 }
 
 void aec_gpu_set_index_hint(aec_gpu_ctx *ctx, uint64_t rsi_bits) { ctx->idx_hint = rsi_bits; }
@@ -555,43 +483,16 @@ int aec_gpu_index_plan(const aec_gpu_params *p, size_t in_bytes, uint64_t rsi_bi
 
 void aec_gpu_trim(aec_gpu_ctx *ctx, size_t keep_bytes)
 {
-    if (ctx->ws && ctx->ws_bytes > keep_bytes) {
-        (void)hipFree(ctx->ws);
-        ctx->ws = nullptr;
-        ctx->ws_bytes = 0;
-    }
-    if (ctx->range_ws && ctx->range_ws_bytes > keep_bytes) {
-        (void)hipFree(ctx->range_ws);
-        ctx->range_ws = nullptr;
-        ctx->range_ws_bytes = 0;
-    }
-    if (ctx->fused && ctx->fused_bytes > keep_bytes) {
-        (void)hipFree(ctx->fused);
-        ctx->fused = nullptr;
-        ctx->fused_bytes = 0;
-    }
-    if (ctx->idx_ws && ctx->idx_ws_bytes > keep_bytes) {
-        (void)hipFree(ctx->idx_ws);
-        ctx->idx_ws = nullptr;
-        ctx->idx_ws_bytes = 0;
-    }
-    if (ctx->dec_ws && ctx->dec_ws_bytes > keep_bytes) {
-        (void)hipFree(ctx->dec_ws);
-        ctx->dec_ws = nullptr;
-        ctx->dec_ws_bytes = 0;
-    }
-    if (ctx->chunks_d && ctx->chunks_d_bytes > keep_bytes) {
-        (void)hipFree(ctx->chunks_d);
-        ctx->chunks_d = nullptr;
-        ctx->chunks_d_bytes = 0;
-    }
+    for (DevBuf *b : ctx->held)
+        if (b->cap > keep_bytes) b->release();
 }
 
 size_t aec_gpu_held_bytes(const aec_gpu_ctx *ctx)
 {
-    return ctx ? ctx->ws_bytes + ctx->fused_bytes + ctx->idx_ws_bytes + ctx->dec_ws_bytes + ctx->range_ws_bytes +
-                     ctx->chunks_d_bytes
-               : 0;
+    size_t sum = 0;
+    if (ctx)
+        for (const DevBuf *b : ctx->held) sum += b->cap;
+    return sum;
 }
 
 int aec_gpu_index_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -605,9 +506,8 @@ int aec_gpu_index_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const v
     if ((reinterpret_cast<uintptr_t>(d_in) & 15u) || rsi_per_chunk == 0) return RC_CONF_ERROR;
     (void)hipGetLastError();
     launch_index_batch(c, static_cast<const uint8_t *>(d_in), in_bytes, d_chunk_offsets, n_chunks, rsi_per_chunk,
-                       d_rsi_bit_offsets, reinterpret_cast<DecResult *>(d_results),
-                       static_cast<hipStream_t>(stream));
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+                       d_rsi_bit_offsets, rec(d_results), static_cast<hipStream_t>(stream));
+    return launched();
 }
 
 int aec_gpu_batch_uses_tables(aec_gpu_ctx *ctx, const aec_gpu_params *p, size_t in_bytes, uint64_t n_chunks,
@@ -638,22 +538,15 @@ int aec_gpu_decode_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const 
     const size_t mean = in_bytes / n_chunks, max_chunk = mean * 2 + 65536;
     const uint64_t hint = ctx->idx_hint ? ctx->idx_hint : (uint64_t)mean * 8 / rsi_per_chunk;
     size_t need = mean >= ((size_t)16 << 10) ? index_batch_workspace_bytes(c, in_bytes, n_chunks, max_chunk, hint) : 0;
-    if (need > ctx->idx_ws_bytes) {
-        if (ctx->idx_ws) (void)hipFree(ctx->idx_ws);
-        ctx->idx_ws = nullptr;
-        ctx->idx_ws_bytes = 0;
-        if (hipMalloc(&ctx->idx_ws, need + need / 16) == hipSuccess) ctx->idx_ws_bytes = need + need / 16;
-        else (void)hipGetLastError();
-    }
+    (void)ctx->idx_ws.replace(need, need + need / 16);         // (a failure: the serial walk per stream)
     launch_index_batch(c, static_cast<const uint8_t *>(d_in), in_bytes, d_chunk_offsets, n_chunks, rsi_per_chunk,
-                       d_rsi_bit_offsets, reinterpret_cast<DecResult *>(d_results), static_cast<hipStream_t>(stream),
-                       need ? ctx->idx_ws : nullptr, ctx->idx_ws_bytes, max_chunk, hint);
+                       d_rsi_bit_offsets, rec(d_results), static_cast<hipStream_t>(stream),
+                       need ? ctx->idx_ws.p : nullptr, ctx->idx_ws.cap, max_chunk, hint);
     if (!launch_decode(c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, n_chunks * rsi_per_chunk,
-                       n_chunks * rsi_per_chunk * c.rsi, static_cast<uint8_t *>(d_out),
-                       reinterpret_cast<DecResult *>(d_result), static_cast<hipStream_t>(stream), ctx->dec_events(),
-                       nullptr, reinterpret_cast<const DecResult *>(d_results), (uint32_t)rsi_per_chunk))
+                       n_chunks * rsi_per_chunk * c.rsi, static_cast<uint8_t *>(d_out), rec(d_result),
+                       static_cast<hipStream_t>(stream), ctx->dec_events(), nullptr, rec(d_results), (uint32_t)rsi_per_chunk))
         return RC_MEM_ERROR;
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    return launched();
 }
 
 int aec_gpu_encode_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in,
@@ -689,23 +582,13 @@ int aec_gpu_encode_uniform_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p
     rc = cfg_from(p, chunk_bytes * n_chunks, true, &c);
     if (rc != RC_OK) return rc;
     if (!batch_uniform_ok(c, one.total_segs)) return RC_CONF_ERROR;          // (aec_gpu_uniform_batch_ok says so beforehand)
-    rc = reserve_two_pass(ctx, c);
+    EncWorkspace ws;
+    rc = reserve_two_pass(ctx, c, &ws);
     if (rc != RC_OK) return rc;
     (void)hipGetLastError();
-    size_t o[6];
-    enc_workspace_bytes(c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]);
-    uint8_t *base = static_cast<uint8_t *>(ctx->ws);
-    EncWorkspace ws{};
-    ws.meta = reinterpret_cast<uint32_t *>(base + o[0]);
-    ws.seg_bits = reinterpret_cast<uint32_t *>(base + o[1]);
-    ws.seg_clamp = reinterpret_cast<uint16_t *>(base + o[2]);
-    ws.seg_start = reinterpret_cast<uint64_t *>(base + o[3]);
-    ws.seg_kin = base + o[4];
-    ws.partials = reinterpret_cast<ScanPartial *>(base + o[5]);
     launch_encode_uniform_batch(c, static_cast<const uint8_t *>(d_in), one.total_segs, static_cast<uint8_t *>(d_out),
-                                out_cap, ws, reinterpret_cast<BatchChunk *>(d_chunks),
-                                reinterpret_cast<EncResult *>(d_result), static_cast<hipStream_t>(stream));
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+                                out_cap, ws, chunk_recs(d_chunks), rec(d_result), static_cast<hipStream_t>(stream));
+    return launched();
 }
 
 int aec_gpu_uniform_batch_ok(const aec_gpu_params *p, size_t chunk_bytes, uint64_t n_chunks)
@@ -715,6 +598,36 @@ int aec_gpu_uniform_batch_ok(const aec_gpu_params *p, size_t chunk_bytes, uint64
     if (chunk_bytes % ((size_t)one.rsi * one.bs * one.bytes)) return 0;
     if (cfg_from(p, chunk_bytes * n_chunks, true, &c) != RC_OK) return 0;
     return batch_uniform_ok(c, one.total_segs) ? 1 : 0;
+}
+
+// ---- the descriptors of the chunk calls: host to device ------------------------------------------------------------------
+// Both chunk calls write their descriptors to a pinned buffer of the context and send it to chunks_d in stream order.  The
+// pinned buffers are taken in turn, whichever of the two calls comes (a context's calls are enqueued on one stream, so the
+// copy waits for the kernels in front); the event of a buffer's last transfer says when that transfer has left it.
+// Step 1: the pinned buffer whose turn it is, with room for h_need bytes and free to write.  null: no memory.
+static aec_gpu_ctx::ChunkStage *stage_descriptors(aec_gpu_ctx *ctx, size_t h_need)
+{
+    aec_gpu_ctx::ChunkStage &s = ctx->stage[ctx->chunks_calls++ % aec_gpu_ctx::kChunkStages];
+    if (!s.ev && hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) {
+        s.ev = nullptr;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    if (s.h.p && hipEventSynchronize(s.ev) != hipSuccess) return nullptr;
+    return s.h.replace(h_need, h_need + h_need / 4 + 4096) ? &s : nullptr;
+}
+
+// Step 2, once the descriptors are written: h_need bytes of the buffer to chunks_d, which has room for d_need bytes
+// (descriptors and the table behind them).  Growing chunks_d synchronises the device -- no kernel still reads it -- hence
+// after the host's work and before the copy.  Returns chunks_d, null where there is no memory or the copy failed.
+static uint8_t *send_descriptors(aec_gpu_ctx *ctx, aec_gpu_ctx::ChunkStage *s, size_t h_need, size_t d_need, hipStream_t st)
+{
+    if (!ctx->chunks_d.replace(d_need, (d_need + d_need / 4 + 255) & ~(size_t)255)) return nullptr;
+    (void)hipGetLastError();   // only errors of THIS call are reported by it
+    if (hipMemcpyAsync(ctx->chunks_d.p, s->h.p, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipEventRecord(s->ev, st) != hipSuccess)
+        return nullptr;
+    return static_cast<uint8_t *>(ctx->chunks_d.p);
 }
 
 // ---- a batch of unequal chunks as one launch set (aec_chunks.h) -------------------------------------------------------
@@ -798,64 +711,21 @@ int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
         if (chunk_offsets[i] & 15u) return RC_CONF_ERROR;
     const hipStream_t st = static_cast<hipStream_t>(stream);
 
-    // the descriptors: written to a pinned buffer of the context (the one whose last transfer lies furthest back; its
-    // event says when that transfer has left it), then one copy to the device in stream order
-    const unsigned slot = ctx->chunks_calls++ % aec_gpu_ctx::kChunkStages;
     const size_t h_need = (size_t)(n_chunks + 1) * sizeof(ChunkDesc);
-    if (!ctx->chunks_ev[slot] && hipEventCreateWithFlags(&ctx->chunks_ev[slot], hipEventDisableTiming) != hipSuccess) {
-        ctx->chunks_ev[slot] = nullptr;
-        (void)hipGetLastError();
-        return RC_MEM_ERROR;
-    }
-    if (ctx->chunks_h[slot] && hipEventSynchronize(ctx->chunks_ev[slot]) != hipSuccess) return RC_MEM_ERROR;
-    if (h_need > ctx->chunks_h_bytes[slot]) {
-        if (ctx->chunks_h[slot]) (void)hipHostFree(ctx->chunks_h[slot]);
-        ctx->chunks_h[slot] = nullptr;
-        ctx->chunks_h_bytes[slot] = 0;
-        const size_t want = h_need + h_need / 4 + 4096;
-        if (hipHostMalloc(&ctx->chunks_h[slot], want, hipHostMallocDefault) != hipSuccess) {
-            ctx->chunks_h[slot] = nullptr;
-            (void)hipGetLastError();
-            return RC_MEM_ERROR;
-        }
-        ctx->chunks_h_bytes[slot] = want;
-    }
-    ChunkDesc *h_desc = static_cast<ChunkDesc *>(ctx->chunks_h[slot]);
+    aec_gpu_ctx::ChunkStage *stage = stage_descriptors(ctx, h_need);
+    if (!stage) return RC_MEM_ERROR;
     ChunksShape sh;
-    if (!chunks_shape(p, chunk_offsets, chunk_bytes, n_chunks, &sh, h_desc)) return RC_CONF_ERROR;
-    int rc = reserve_two_pass(ctx, sh.c);
+    if (!chunks_shape(p, chunk_offsets, chunk_bytes, n_chunks, &sh, static_cast<ChunkDesc *>(stage->h.p))) return RC_CONF_ERROR;
+    EncWorkspace ws;
+    const int rc = reserve_two_pass(ctx, sh.c, &ws);
     if (rc != RC_OK) return rc;
-    if (sh.desc_bytes + sh.table_bytes > ctx->chunks_d_bytes) {
-        if (ctx->chunks_d) (void)hipFree(ctx->chunks_d);           // (synchronises: no kernel still reads it)
-        ctx->chunks_d = nullptr;
-        ctx->chunks_d_bytes = 0;
-        const size_t want = up256(sh.desc_bytes + sh.table_bytes + (sh.desc_bytes + sh.table_bytes) / 4);
-        if (hipMalloc(&ctx->chunks_d, want) != hipSuccess) {
-            (void)hipGetLastError();
-            return RC_MEM_ERROR;
-        }
-        ctx->chunks_d_bytes = want;
-    }
-    (void)hipGetLastError();
-    uint8_t *cd = static_cast<uint8_t *>(ctx->chunks_d);
-    if (hipMemcpyAsync(cd, h_desc, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipEventRecord(ctx->chunks_ev[slot], st) != hipSuccess)
-        return RC_MEM_ERROR;
-    size_t o[6];
-    enc_workspace_bytes(sh.c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]);
-    uint8_t *base = static_cast<uint8_t *>(ctx->ws);
-    EncWorkspace ws{};
-    ws.meta = reinterpret_cast<uint32_t *>(base + o[0]);
-    ws.seg_bits = reinterpret_cast<uint32_t *>(base + o[1]);
-    ws.seg_clamp = reinterpret_cast<uint16_t *>(base + o[2]);
-    ws.seg_start = reinterpret_cast<uint64_t *>(base + o[3]);
-    ws.seg_kin = base + o[4];
-    ws.partials = reinterpret_cast<ScanPartial *>(base + o[5]);
+    uint8_t *cd = send_descriptors(ctx, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
+    if (!cd) return RC_MEM_ERROR;
     const ChunksLaunch k{reinterpret_cast<const ChunkDesc *>(cd), reinterpret_cast<uint32_t *>(cd + sh.desc_bytes), n_chunks,
                          sh.waves, sh.spw};
     launch_encode_chunks(sh.c, static_cast<const uint8_t *>(d_in), k, static_cast<uint8_t *>(d_out), out_cap, ws,
-                         reinterpret_cast<BatchChunk *>(d_chunks), d_rsi_bit_offsets, reinterpret_cast<EncResult *>(d_result), st);
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+                         chunk_recs(d_chunks), d_rsi_bit_offsets, rec(d_result), st);
+    return launched();
 }
 
 // ---- a batch of unequal chunks decoded as one launch (aec_dchunks.h) ----------------------------------------------------
@@ -928,60 +798,27 @@ int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
     }
     const hipStream_t st = static_cast<hipStream_t>(stream);
 
-    // the descriptors: through the pinned buffers and the device buffer aec_gpu_encode_chunks_async uses (same turns,
-    // same events: a context's calls are enqueued on one stream, so the copy below waits for the kernels in front)
-    const unsigned slot = ctx->chunks_calls++ % aec_gpu_ctx::kChunkStages;
     const size_t h_need = (size_t)(n_chunks + 1) * sizeof(DChunkDesc);
-    if (!ctx->chunks_ev[slot] && hipEventCreateWithFlags(&ctx->chunks_ev[slot], hipEventDisableTiming) != hipSuccess) {
-        ctx->chunks_ev[slot] = nullptr;
-        (void)hipGetLastError();
-        return RC_MEM_ERROR;
-    }
-    if (ctx->chunks_h[slot] && hipEventSynchronize(ctx->chunks_ev[slot]) != hipSuccess) return RC_MEM_ERROR;
-    if (h_need > ctx->chunks_h_bytes[slot]) {
-        if (ctx->chunks_h[slot]) (void)hipHostFree(ctx->chunks_h[slot]);
-        ctx->chunks_h[slot] = nullptr;
-        ctx->chunks_h_bytes[slot] = 0;
-        const size_t want = h_need + h_need / 4 + 4096;
-        if (hipHostMalloc(&ctx->chunks_h[slot], want, hipHostMallocDefault) != hipSuccess) {
-            ctx->chunks_h[slot] = nullptr;
-            (void)hipGetLastError();
-            return RC_MEM_ERROR;
-        }
-        ctx->chunks_h_bytes[slot] = want;
-    }
-    DChunkDesc *h_desc = static_cast<DChunkDesc *>(ctx->chunks_h[slot]);
+    aec_gpu_ctx::ChunkStage *stage = stage_descriptors(ctx, h_need);
+    if (!stage) return RC_MEM_ERROR;
     DChunksShape sh;
-    if (!dchunks_shape(p, in_offsets, in_bytes_each, out_offsets, out_bytes, n_chunks, &sh, h_desc)) return RC_CONF_ERROR;
-    if (sh.desc_bytes + sh.table_bytes > ctx->chunks_d_bytes) {
-        if (ctx->chunks_d) (void)hipFree(ctx->chunks_d);           // (synchronises: no kernel still reads it)
-        ctx->chunks_d = nullptr;
-        ctx->chunks_d_bytes = 0;
-        const size_t want = up256(sh.desc_bytes + sh.table_bytes + (sh.desc_bytes + sh.table_bytes) / 4);
-        if (hipMalloc(&ctx->chunks_d, want) != hipSuccess) {
-            (void)hipGetLastError();
-            return RC_MEM_ERROR;
-        }
-        ctx->chunks_d_bytes = want;
-    }
-    (void)hipGetLastError();
-    uint8_t *cd = static_cast<uint8_t *>(ctx->chunks_d);
-    if (hipMemcpyAsync(cd, h_desc, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipEventRecord(ctx->chunks_ev[slot], st) != hipSuccess)
-        return RC_MEM_ERROR;
+    if (!dchunks_shape(p, in_offsets, in_bytes_each, out_offsets, out_bytes, n_chunks, &sh, static_cast<DChunkDesc *>(stage->h.p)))
+        return RC_CONF_ERROR;
+    uint8_t *cd = send_descriptors(ctx, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
+    if (!cd) return RC_MEM_ERROR;
     const DChunkDesc *d_desc = reinterpret_cast<const DChunkDesc *>(cd);
     uint32_t *d_item_chunk = reinterpret_cast<uint32_t *>(cd + sh.desc_bytes);
-    DecResult *records = reinterpret_cast<DecResult *>(d_results);
+    DecResult *records = rec(d_results);
     launch_dchunks_setup(sh.c, d_desc, n_chunks, sh.items, d_item_chunk, have_table ? records : nullptr, st);
     if (!have_table)
         launch_index_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_desc, n_chunks, d_rsi_bit_offsets, records, st);
     // (bits per coded data set, from what the chunks announce: sizes the rings of the lane kernel)
     const uint64_t avg = sh.blocks ? (uint64_t)in_bytes * 8 / sh.blocks : 0;
     if (!launch_decode_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, d_desc, d_item_chunk,
-                              sh.items, avg, static_cast<uint8_t *>(d_out), records, reinterpret_cast<DecResult *>(d_result), st,
+                              sh.items, avg, static_cast<uint8_t *>(d_out), records, rec(d_result), st,
                               ctx->dec_events()))
         return RC_MEM_ERROR;
-    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
+    return launched();
 }
 
 int aec_gpu_profile(aec_gpu_ctx *ctx, int enable)

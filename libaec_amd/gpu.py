@@ -108,17 +108,33 @@ def _lib():
     return lib
 
 
+def _ptr(t):
+    """the address of a tensor's data as a c_void_p; None is the NULL pointer"""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _call(fn, *args):
+    """calls an entry point of the library; a return code other than 0 raises"""
+    rc = fn(*args)
+    if rc != 0:
+        raise RuntimeError(f"{fn.__name__} failed ({rc})")
+
+
+def bytes_per_sample(bits_per_sample, flags):
+    """bytes a sample takes in memory: 1, 2, 4, or 3 for 17 to 24 bits with AEC_DATA_3BYTE (flag 2)"""
+    if bits_per_sample > 16:
+        return 3 if bits_per_sample <= 24 and flags & 2 else 4
+    return 2 if bits_per_sample > 8 else 1
+
+
 def stitch_async(d_gathered, slot, d_plans, world, d_stream, d_total=None, stream=None):
     """aec_gpu_stitch_async: compact the all-gathered slices (world slots of `slot` bytes in d_gathered,
     16 readable bytes behind the last) into one stream at d_stream, on the device."""
     import torch
     lib = _lib()
     st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
-    rc = lib.aec_gpu_stitch_async(C.c_void_p(d_gathered.data_ptr()), slot, C.c_void_p(d_plans.data_ptr()), world,
-                                  C.c_void_p(d_stream.data_ptr()), d_stream.numel(),
-                                  C.c_void_p(d_total.data_ptr()) if d_total is not None else None, st)
-    if rc != 0:
-        raise RuntimeError(f"aec_gpu_stitch_async failed ({rc})")
+    _call(lib.aec_gpu_stitch_async, _ptr(d_gathered), slot, _ptr(d_plans), world, _ptr(d_stream), d_stream.numel(),
+          _ptr(d_total), st)
 
 
 INDEX_SCHEMES = ("serial walk", "phase-locked chains", "window tables", "trunk", "every bit parsed (small streams)",
@@ -185,9 +201,7 @@ class Codec:
         self.ctx = C.c_void_p()
         torch.cuda.current_device()
         torch.zeros(1, device="cuda")          # make sure the HIP context of this device is current
-        rc = self.lib.aec_gpu_create(C.byref(self.ctx))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_create failed ({rc})")
+        _call(self.lib.aec_gpu_create, C.byref(self.ctx))
 
     def close(self):
         if self.ctx:
@@ -216,15 +230,11 @@ class Codec:
     def set_segment_table(self, d_table):
         """d_table: uint8 CUDA tensor of segment_count * 16 bytes (or None): filled by later encodes"""
         self._seg_table = d_table          # keep it alive
-        self.lib.aec_gpu_set_segment_table(self.ctx, C.c_void_p(d_table.data_ptr()) if d_table is not None else None)
+        self.lib.aec_gpu_set_segment_table(self.ctx, _ptr(d_table))
 
     def decode_segments_async(self, d_in, in_bytes, d_table, n_seg, total_blocks, d_out, d_result, stream=None):
-        rc = self.lib.aec_gpu_decode_segments_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, C.c_void_p(d_table.data_ptr()),
-            n_seg, total_blocks, C.c_void_p(d_out.data_ptr()), C.c_void_p(d_result.data_ptr()),
-            self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_decode_segments_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_decode_segments_async, stream, _ptr(d_in), in_bytes, _ptr(d_table), n_seg, total_blocks,
+                      _ptr(d_out), _ptr(d_result))
 
     def reserve(self, in_bytes):
         rc = self.lib.aec_gpu_reserve(self.ctx, C.byref(self.p), in_bytes)
@@ -235,79 +245,49 @@ class Codec:
         return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
 
     # ---- enqueue -------------------------------------------------------------------------------
+    def _enqueue(self, fn, stream, *args):
+        """fn(context, parameters, args..., stream): every *_async entry point has this shape"""
+        _call(fn, self.ctx, C.byref(self.p), *args, self._stream(stream))
+
     def encode_async(self, d_in, in_bytes, d_out, d_offsets, d_result, start_bit=0, k_in=0, stream=None):
         """d_in/d_out: uint8 CUDA tensors; d_offsets: int64 tensor with rsi_count+1 entries or None;
         d_result: uint8 tensor of >= 16 bytes."""
-        rc = self.lib.aec_gpu_encode_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, C.c_void_p(d_out.data_ptr()),
-            d_out.numel(), start_bit, k_in,
-            C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_encode_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_encode_async, stream, _ptr(d_in), in_bytes, _ptr(d_out), d_out.numel(), start_bit, k_in,
+                      _ptr(d_offsets), _ptr(d_result))
 
     def encode_plan_async(self, d_in, in_bytes, d_result, stream=None):
         """first half of an encode: leaves total_bits and (k_lo, k_hi) in d_result"""
-        rc = self.lib.aec_gpu_encode_plan_async(self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes,
-                                                C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_encode_plan_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_encode_plan_async, stream, _ptr(d_in), in_bytes, _ptr(d_result))
 
     def encode_emit_async(self, d_in, in_bytes, d_out, d_offsets, d_result, start_bit, k_in, stream=None):
         """second half: writes the stream at bit `start_bit` of d_out[0] with carried k `k_in`"""
-        rc = self.lib.aec_gpu_encode_emit_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, C.c_void_p(d_out.data_ptr()),
-            d_out.numel(), start_bit, k_in,
-            C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_encode_emit_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_encode_emit_async, stream, _ptr(d_in), in_bytes, _ptr(d_out), d_out.numel(), start_bit,
+                      k_in, _ptr(d_offsets), _ptr(d_result))
 
     def encode_emit_planned_async(self, d_in, in_bytes, d_out, d_offsets, d_result, d_plans, rank, stream=None):
         """second half without a host round trip: d_plans = the all-gathered 24-byte plan records of
         all shards (uint8 tensor, world * 24 bytes), rank = this shard's index; start bit and carried
         k are computed on the device"""
-        rc = self.lib.aec_gpu_encode_emit_planned_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, C.c_void_p(d_out.data_ptr()),
-            d_out.numel(), C.c_void_p(d_plans.data_ptr()), rank,
-            C.c_void_p(d_offsets.data_ptr()) if d_offsets is not None else None,
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_encode_emit_planned_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_encode_emit_planned_async, stream, _ptr(d_in), in_bytes, _ptr(d_out), d_out.numel(),
+                      _ptr(d_plans), rank, _ptr(d_offsets), _ptr(d_result))
 
     def index_resume_async(self, d_in, in_bytes, start_bit, start_block, rsi_start_bit, d_offsets, max_rsi,
                            d_result, stream=None):
         """d_offsets needs max_rsi + 1 entries (the last receives the start of the trailing partial RSI)"""
-        rc = self.lib.aec_gpu_index_resume_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, start_bit, start_block,
-            rsi_start_bit, C.c_void_p(d_offsets.data_ptr()), max_rsi, C.c_void_p(d_result.data_ptr()),
-            self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_index_resume_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_index_resume_async, stream, _ptr(d_in), in_bytes, start_bit, start_block, rsi_start_bit,
+                      _ptr(d_offsets), max_rsi, _ptr(d_result))
 
     def decode_indexed_async(self, d_in, in_bytes, d_offsets, max_rsi, d_index_result, d_out, d_result, stream=None):
-        rc = self.lib.aec_gpu_decode_indexed_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, C.c_void_p(d_offsets.data_ptr()),
-            max_rsi, C.c_void_p(d_index_result.data_ptr()), C.c_void_p(d_out.data_ptr()),
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_decode_indexed_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_decode_indexed_async, stream, _ptr(d_in), in_bytes, _ptr(d_offsets), max_rsi,
+                      _ptr(d_index_result), _ptr(d_out), _ptr(d_result))
 
     def decode_async(self, d_in, in_bytes, d_offsets, n_rsi, total_blocks, d_out, d_result, stream=None):
-        rc = self.lib.aec_gpu_decode_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes,
-            C.c_void_p(d_offsets.data_ptr()), n_rsi, total_blocks, C.c_void_p(d_out.data_ptr()),
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_decode_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_decode_async, stream, _ptr(d_in), in_bytes, _ptr(d_offsets), n_rsi, total_blocks,
+                      _ptr(d_out), _ptr(d_result))
 
     def index_async(self, d_in, in_bytes, start_bit, d_offsets, max_rsi, d_result, stream=None):
-        rc = self.lib.aec_gpu_index_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, start_bit,
-            C.c_void_p(d_offsets.data_ptr()), max_rsi, C.c_void_p(d_result.data_ptr()),
-            self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_index_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_index_async, stream, _ptr(d_in), in_bytes, start_bit, _ptr(d_offsets), max_rsi,
+                      _ptr(d_result))
 
     def segments_per_rsi(self):
         return int(self.lib.aec_gpu_segments_per_rsi(C.byref(self.p)))
@@ -316,35 +296,22 @@ class Codec:
                              start_block=0, rsi_start_bit=0):
         """index pass that also leaves the segment starts: d_offsets int64 (max_rsi + 1), d_seg_bits int64
         ((max_rsi + 1) * segments_per_rsi())"""
-        rc = self.lib.aec_gpu_index_segments_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, start_bit, start_block, rsi_start_bit,
-            C.c_void_p(d_offsets.data_ptr()), C.c_void_p(d_seg_bits.data_ptr()), max_rsi,
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_index_segments_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_index_segments_async, stream, _ptr(d_in), in_bytes, start_bit, start_block, rsi_start_bit,
+                      _ptr(d_offsets), _ptr(d_seg_bits), max_rsi, _ptr(d_result))
 
     def decode_bare_async(self, d_in, in_bytes, d_offsets, d_seg_bits, max_rsi, total_blocks, d_index_result, d_out,
                           d_result, stream=None):
         """decode behind index_segments_async, a lane per segment where the index pass found the segment starts;
         d_index_result: the index record (counts taken on the device) or None (max_rsi RSIs, total_blocks blocks)"""
-        rc = self.lib.aec_gpu_decode_bare_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, C.c_void_p(d_offsets.data_ptr()),
-            C.c_void_p(d_seg_bits.data_ptr()) if d_seg_bits is not None else None, max_rsi, total_blocks,
-            C.c_void_p(d_index_result.data_ptr()) if d_index_result is not None else None,
-            C.c_void_p(d_out.data_ptr()), C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_decode_bare_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_decode_bare_async, stream, _ptr(d_in), in_bytes, _ptr(d_offsets), _ptr(d_seg_bits), max_rsi,
+                      total_blocks, _ptr(d_index_result), _ptr(d_out), _ptr(d_result))
 
     def index_batch_async(self, d_in, in_bytes, d_chunk_offsets, n_chunks, rsi_per_chunk, d_offsets, d_results,
                           stream=None):
         """d_chunk_offsets: int64 tensor (n_chunks + 1 byte offsets, multiples of 16);
         d_offsets: int64 tensor (n_chunks * rsi_per_chunk); d_results: uint8 tensor (n_chunks * 40)"""
-        rc = self.lib.aec_gpu_index_batch_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes,
-            C.c_void_p(d_chunk_offsets.data_ptr()), n_chunks, rsi_per_chunk, C.c_void_p(d_offsets.data_ptr()),
-            C.c_void_p(d_results.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_index_batch_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_index_batch_async, stream, _ptr(d_in), in_bytes, _ptr(d_chunk_offsets), n_chunks,
+                      rsi_per_chunk, _ptr(d_offsets), _ptr(d_results))
 
     def encode_uniform_batch(self, d_in, chunk_bytes, n_chunks):
         """n equal chunks of whole RSIs, back to back in d_in, as one launch set (include/aec_gpu.h:
@@ -357,12 +324,8 @@ class Codec:
         d_out = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
         d_rec = torch.zeros(n_chunks * 2, dtype=torch.int64, device=d_in.device)
         d_res = torch.zeros(ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
-        rc = self.lib.aec_gpu_encode_uniform_batch_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), chunk_bytes, n_chunks,
-            C.c_void_p(d_out.data_ptr()), cap, C.c_void_p(d_rec.data_ptr()), C.c_void_p(d_res.data_ptr()),
-            self._stream(None))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_encode_uniform_batch_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_encode_uniform_batch_async, None, _ptr(d_in), chunk_bytes, n_chunks, _ptr(d_out), cap,
+                      _ptr(d_rec), _ptr(d_res))
         rec = d_rec.cpu().numpy().reshape(n_chunks, 2)
         res = d_res.cpu().numpy().view(ENC_RESULT_DTYPE)[0]
         if res["overflow"]:
@@ -375,13 +338,9 @@ class Codec:
     def encode_chunks_async(self, d_in, offsets, sizes, d_out, out_cap, d_records, d_table, d_result, stream=None):
         """aec_gpu_encode_chunks_async as it is: offsets / sizes are uint64 numpy arrays on the host, d_records an int64
         tensor of 2 n entries, d_table an int64 tensor of the plan's rsi_entries (or None), d_result 24 bytes"""
-        rc = self.lib.aec_gpu_encode_chunks_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), C.c_void_p(offsets.ctypes.data),
-            C.c_void_p(sizes.ctypes.data), int(sizes.size), C.c_void_p(d_out.data_ptr()), out_cap,
-            C.c_void_p(d_records.data_ptr()), C.c_void_p(d_table.data_ptr()) if d_table is not None else None,
-            C.c_void_p(d_result.data_ptr()), self._stream(stream))
-        if rc != 0:
-            raise RuntimeError(f"aec_gpu_encode_chunks_async failed ({rc})")
+        self._enqueue(self.lib.aec_gpu_encode_chunks_async, stream, _ptr(d_in), C.c_void_p(offsets.ctypes.data),
+                      C.c_void_p(sizes.ctypes.data), int(sizes.size), _ptr(d_out), out_cap, _ptr(d_records), _ptr(d_table),
+                      _ptr(d_result))
 
     def encode_chunks(self, d_in, offsets, sizes, want_offsets=False, out_cap=None, d_out=None):
         """Chunks of sizes[i] bytes at byte offsets[i] (multiples of 16) of d_in, each a stream of its own, as one launch
@@ -420,9 +379,8 @@ class Codec:
         def host(a):
             return C.c_void_p(a.ctypes.data) if a is not None else None
         return self.lib.aec_gpu_decode_chunks_async(
-            self.ctx, C.byref(self.p), C.c_void_p(d_in.data_ptr()), in_bytes, host(in_offsets), host(in_sizes),
-            host(out_offsets), host(out_sizes), int(out_sizes.size), C.c_void_p(d_table.data_ptr()), int(have_table),
-            C.c_void_p(d_out.data_ptr()), C.c_void_p(d_records.data_ptr()), C.c_void_p(d_result.data_ptr()),
+            self.ctx, C.byref(self.p), _ptr(d_in), in_bytes, host(in_offsets), host(in_sizes), host(out_offsets),
+            host(out_sizes), int(out_sizes.size), _ptr(d_table), int(have_table), _ptr(d_out), _ptr(d_records), _ptr(d_result),
             self._stream(stream))
 
     def decode_chunks(self, d_in, in_bytes, out_sizes, d_table=None, in_offsets=None, in_sizes=None):
@@ -438,8 +396,7 @@ class Codec:
         if plan is None:
             raise ValueError("aec_gpu_decode_chunks_plan refuses this batch")
         n = int(osz.size)
-        bps = self.p.bits_per_sample
-        nb = 4 if bps > 16 and not (bps <= 24 and self.p.flags & 2) else (3 if bps > 16 else (2 if bps > 8 else 1))
+        nb = bytes_per_sample(self.p.bits_per_sample, self.p.flags)
         blk = self.p.block_size * nb
         rooms = [((int(b) // nb + self.p.block_size - 1) // self.p.block_size * blk + 15) // 16 * 16 for b in osz]
         ooff = np.zeros(n, dtype=np.uint64)
@@ -480,8 +437,7 @@ class Codec:
 
     def decode(self, d_in, in_bytes, d_offsets, n_rsi, total_blocks):
         torch = self.torch
-        bps = self.p.bits_per_sample
-        nb = 4 if bps > 16 and not (bps <= 24 and self.p.flags & 2) else (3 if bps > 16 else (2 if bps > 8 else 1))
+        nb = bytes_per_sample(self.p.bits_per_sample, self.p.flags)
         d_out = torch.empty(total_blocks * self.p.block_size * nb + 16, dtype=torch.uint8, device=d_in.device)
         d_res = torch.zeros(DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
         self.decode_async(d_in, in_bytes, d_offsets, n_rsi, total_blocks, d_out, d_res)
