@@ -18,6 +18,10 @@
 //               coalesced byte-swapped copy to HBM; only the first/last word of a segment can be
 //               shared with a neighbour and uses a global atomic OR.
 //
+//   k_encode_local / k_encode_redo / k_place   large encodes of blocks held in registers code every block ONCE
+//               (aec_enc_local.h): analysis and emission together into a slot per wavefront with a guessed carried k,
+//               the scan, the runs whose guess missed coded again, the slots shifted to their places in the stream.
+//
 //   k_analyze_chunks / k_pack_chunks   the same bodies (aec_enc_analyze.inc / aec_enc_pack.inc) behind a prologue that
 //               gives a wave ONE chunk of a batch of unequal chunks; k_chunks_* is the scan that restarts at every
 //               chunk (aec_chunks.h).
@@ -30,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "aec_chunks.h"
+#include "aec_enc_local.h"
 #include "aec_kernels.h"
 #include "aec_lane.h"
 #include "aec_tune.h"
@@ -47,6 +52,16 @@ struct FusedGeom {
 // The launches of one block size's kernels (defined in the object compiled with -DAEC_ENC_PART=BS)
 template <int BS> void enc_part(bool pack, const Cfg &c, const uint8_t *in, const EncWorkspace &ws, uint32_t *out_words,
                                 uint64_t cap_words, uint32_t fast_ok, hipStream_t st);
+struct LocalLaunch {
+    uint32_t *image;         // [waves * slot_words]
+    uint16_t *seg_first;     // [total_segs] own clamp of the segment's first k-updating block (kLocalNoClamp: none)
+    uint8_t *seg_kused;      // [total_segs] the k carried into the segment as k_encode_local had it
+    uint32_t slot_words, segs_per_wave, k_in, guess;
+};
+
+// (defined for the block sizes that have a DIRECT instantiation: 8, 16, 32)
+template <int BS> void enc_part_local(bool redo, const Cfg &c, const uint8_t *in, const EncWorkspace &ws, const LocalLaunch &l,
+                                      uint32_t fast_ok, hipStream_t st);
 template <int BS> void enc_part_fused(const Cfg &c, const uint8_t *in, uint32_t *out_words, uint64_t cap_words,
                                       const FusedGeom &g, void *ctl, uint32_t start_bit, uint32_t k_in, uint64_t *rsi_off,
                                       SegEntry *seg_table, EncResult *res, uint32_t fast_ok, hipStream_t st);
@@ -537,6 +552,9 @@ __device__ __forceinline__ void load_segment_generic(const Cfg &c, const uint8_t
     }
 }
 
+// the shapes of the direct path (Feeder::DIRECT; the host asks too: local_plan)
+constexpr bool direct_shape(uint32_t bs, uint32_t bytes) { return bs > 0 && (bytes == 1 || bytes == 2) && bs * bytes <= 32; }
+
 // Segment feeder: owns the prefetched registers of the NEXT segment.  fast == templated block
 // size, 1/2/4-byte containers, 16-byte aligned RSIs; everything else takes the generic loader.
 template <int BS, int BYTES>
@@ -566,7 +584,7 @@ struct Feeder {
     }
     // ---- direct path (see DirectSeg): kernels that take it prefetch with prefetch_direct and fall back to
     // feed_now for the segments it does not cover (end-of-data padding, no preprocessing)
-    static constexpr bool DIRECT = FAST_T && Rows<BS, BYTES>::HALF && BS * BYTES <= 32;
+    static constexpr bool DIRECT = FAST_T && Rows<BS, BYTES>::HALF && direct_shape(BS, BYTES);
     DirectSeg<(DIRECT ? BS : 8), (DIRECT ? BYTES : 1)> pre_direct;
     uint64_t max_blk;
     __device__ __forceinline__ bool direct_ok(const Cfg &c, const Seg &g) const
@@ -1247,6 +1265,77 @@ k_seg_table(const Cfg c, const uint8_t *__restrict__ in, const uint64_t *__restr
     }
     table[sg] = SegEntry{seg_start[sg], prev, 0u};
 }
+
+// The slots of k_encode_local to their places in the stream (aec_enc_local.h): a wavefront takes kPlaceSlots consecutive
+// slots.  A run starts where the scan put its first segment and ends where the next run starts (the last one: at the end
+// of the stream); its words are shifted by the start's position in a 32-bit word, byte-swapped and stored, the first and
+// the last by atomic OR where the run does not own them alone -- k_scan_apply zeroed those, and the words behind cap_words
+// are nobody's, as in k_pack.
+// A lane takes four slot words at a time (the slots are 128-byte aligned) and the word in front of them from the lane
+// below.  A run is a few hundred words: the first loads of all the wavefront's slots are issued before anything waits, and
+// a round's successor is in flight while its words are shifted and stored -- one wavefront per slot that waits for every
+// 64 words in turn spends its life on HBM round trips (0.84 ms at C2 against 0.62 with the second and 0.58 - 0.62 with both).
+constexpr uint32_t kPlaceSlots = 4;
+
+__global__ void __launch_bounds__(256)
+k_place(const uint32_t *__restrict__ image, uint32_t slot_words, const uint64_t *__restrict__ seg_start, uint64_t nseg,
+        uint32_t segs_per_wave, uint64_t nslots, uint32_t start_bit, const EncResult *__restrict__ res,
+        uint32_t *__restrict__ out_words, uint64_t cap_words)
+{
+    typedef uint32_t words4 __attribute__((ext_vector_type(4), aligned(4)));
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t first = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wave) * kPlaceSlots;
+    if (first >= nslots) return;
+    const uint32_t quads = slot_words / 4u;
+    uint64_t edge[kPlaceSlots + 1];           // where the runs start; the last entry: where the last one ends
+    uint4 head[kPlaceSlots];
+#pragma unroll
+    for (uint32_t g = 0; g <= kPlaceSlots; g++) {
+        const uint64_t s = (first + g) * segs_per_wave;
+        edge[g] = first + g > nslots ? 0u : (s < nseg ? seg_start[s] : (uint64_t)start_bit + res->total_bits);
+    }
+#pragma unroll
+    for (uint32_t g = 0; g < kPlaceSlots; g++)
+        head[g] = first + g < nslots && lane < quads ? reinterpret_cast<const uint4 *>(image + (first + g) * slot_words)[lane]
+                                                     : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (uint32_t g = 0; g < kPlaceSlots; g++) {
+        if (first + g >= nslots || edge[g + 1] <= edge[g]) continue;
+        const LocalSpan sp = local_span(edge[g], edge[g + 1] - edge[g]);
+        const uint4 *__restrict__ slot = reinterpret_cast<const uint4 *>(image + (first + g) * slot_words);
+        uint32_t carry = 0u;                                       // the slot word in front of this round's first
+        uint4 cur = head[g];
+        for (uint32_t base = 0; base < sp.nwords; base += 4u * kWave) {
+            const uint32_t j0 = base + 4u * lane, qn = (base >> 2) + kWave + lane;
+            uint4 nxt = make_uint4(0u, 0u, 0u, 0u);       // (a value, not a reference to an object in memory)
+            if (base + 4u * kWave < sp.nwords && qn < quads) nxt = slot[qn];
+            // (what lies behind the run's last slot word is stale)
+            const uint32_t a0 = j0 < sp.nslot ? cur.x : 0u, a1 = j0 + 1 < sp.nslot ? cur.y : 0u,
+                           a2 = j0 + 2 < sp.nslot ? cur.z : 0u, a3 = j0 + 3 < sp.nslot ? cur.w : 0u;
+            const uint32_t before = wave_shr1(a3, carry);
+            carry = wave_last(a3);
+            const uint32_t v0 = local_word(sp, before, a0), v1 = local_word(sp, a0, a1), v2 = local_word(sp, a1, a2),
+                           v3 = local_word(sp, a2, a3);
+            const uint64_t idx = sp.word0 + j0;
+            const bool inner = (j0 != 0 || !sp.head_shared) &&
+                               (j0 + 4 < sp.nwords || (j0 + 4 == sp.nwords && !sp.tail_shared)) && idx + 4 <= cap_words;
+            auto one = [&](uint32_t q, uint32_t v) {        // a word at an end of the run, or of the buffer
+                if (j0 + q < sp.nwords && idx + q < cap_words) {
+                    if (!local_word_shared(sp, j0 + q))
+                        out_words[idx + q] = bswap32(v);
+                    else if (v != 0)
+                        __hip_atomic_fetch_or(&out_words[idx + q], bswap32(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            };
+            if (inner) {
+                *reinterpret_cast<words4 *>(out_words + idx) = words4{bswap32(v0), bswap32(v1), bswap32(v2), bswap32(v3)};
+            } else {
+                one(0, v0); one(1, v1); one(2, v2); one(3, v3);
+            }
+            cur = nxt;
+        }
+    }
+}
 #endif
 
 // Emission of one segment into its LDS image (rows in LDS, block summaries in registers): offsets
@@ -1351,6 +1440,129 @@ k_pack_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDesc 
 #define AEC_WAVE_INDEX cw.wave
 #include "aec_enc_pack.inc"
 #undef AEC_WAVE_INDEX
+}
+
+// ----------------------------------------------------------------------------------------------
+// K1 and the emission of K3 on the block while it is in registers (aec_enc_local.h)
+// ----------------------------------------------------------------------------------------------
+// A wavefront analyses segments [wave * segs_per_wave, + segs_per_wave) as k_analyze does and emits each of them at once,
+// as k_pack does, into its own slot of `image`, from bit 0 of the slot on.  The k carried into the run is a guess
+// (local_guess), inside the run the carry is exact given the guess.  REDO: the same text after the scan, for the runs
+// where the guess made a block take another k than the true one (local_missed) -- the carry then comes from seg_kin,
+// the positions inside the slot from seg_start, and nothing is written but the slot, whose layout the carried k does
+// not move.
+template <int BS, int BYTES, bool REDO>
+__global__ void __launch_bounds__(256)
+k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict__ seg_bits,
+               uint16_t *__restrict__ seg_clamp, const uint8_t *__restrict__ seg_kin,
+               const uint64_t *__restrict__ seg_start, const LocalLaunch l,
+               uint32_t obuf_words, uint32_t fast_ok)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr uint32_t stride = Rows<BS, BYTES>::stride_words(BS);
+    const uint32_t per_wave = 64u * stride + obuf_words;
+    uint32_t *rows = smem + (size_t)wave * per_wave;
+    uint32_t *obuf = rows + 64u * stride;
+    const bool pp = c.flags & F_PREPROCESS, msb = c.flags & F_MSB;
+
+    const uint64_t gwave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    uint64_t sg = gwave * l.segs_per_wave;
+    uint64_t sg_end = sg + l.segs_per_wave;
+    if (sg_end > c.total_segs) sg_end = c.total_segs;
+    if (sg >= sg_end) return;
+    uint32_t *__restrict__ slot = l.image + gwave * l.slot_words;
+    uint32_t pending = 0;        // open tail word of the previous segment
+    uint32_t pos = 0;            // bits of the run so far = where the segment starts in the slot
+    bool merge_tail = false;     // REDO: the last segment coded again ends in a word that goes on with an untouched one
+    if (REDO) {
+        bool miss = false;
+        const uint64_t s = sg + lane;
+        if (s < sg_end) miss = local_missed(l.seg_first[s], l.seg_kused[s], seg_kin[s]);
+        const uint64_t missed = __ballot(miss);
+        if (!missed) return;
+        // only the segments from the first to the last miss (aec_enc_local.h): positions from the scan, the open words
+        // at both ends shared with what stays in the slot
+        const LocalRedo range = local_redo_range(missed);
+        const uint64_t run0 = sg;
+        merge_tail = run0 + range.end < sg_end;
+        sg_end = run0 + range.end;
+        sg = run0 + range.first;
+        pos = (uint32_t)(seg_start[sg] - seg_start[run0]);
+        if (pos & 31u) pending = local_redo_head(slot[pos >> 5], pos);
+    }
+
+    Feeder<BS, BYTES> feeder;
+    feeder.init(c, fast_ok);
+    Seg gnext = seg_geom(c, sg);
+    feeder.prefetch_direct(c, in, gnext, lane);
+    uint32_t k = l.k_in;         // carried k (exact from the first k-updating block on)
+    bool have_k = gwave == 0;    // ... or from the start, for the call's first wavefront
+    for (uint32_t w = lane; w < obuf_words; w += kWave) obuf[w] = 0u;
+
+    auto do_segment = [&](const Seg &g, uint32_t ref_sample, uint64_t sgi, const uint32_t *direct) {
+        wave_lds_fence();
+        uint32_t tot, cl;
+        const uint32_t m = analyze_segment<BS, BYTES>(c, g, rows, stride, lane, tot, cl, direct);
+        const uint32_t opt = meta_opt(m);
+        const uint64_t upd = __ballot(lane < g.nv && opt != OPT_ZERO && opt != OPT_ZCONT && c.id_len > 1);
+        // (the summary of the FIRST block that updates k holds that block's own clamp: nothing is composed in front)
+        uint32_t first = kLocalNoClamp;
+        if (upd) first = __builtin_amdgcn_readlane(__builtin_amdgcn_perm(0u, m, 0x0c0c0302u), (int)__builtin_ctzll(upd));
+        uint32_t kin;
+        if (REDO) {
+            kin = seg_kin[sgi];
+        } else {
+            if (!have_k && upd) {
+                k = local_guess(first, l.guess);
+                have_k = true;
+            }
+            kin = k;
+            if (lane == 0) {
+                seg_bits[sgi] = tot;
+                seg_clamp[sgi] = (uint16_t)cl;
+                l.seg_first[sgi] = (uint16_t)first;
+                l.seg_kused[sgi] = (uint8_t)kin;
+            }
+            k = kclamp_apply(clamp_unpack(cl), k);
+        }
+        const uint32_t lead = pos & 31u;
+        uint32_t total;
+        emit_segment<BS, BYTES>(c, g, rows, stride, obuf, lane, m, kin, lead, ref_sample, pending, total, direct);
+        // copy-out as k_pack's, without its shared words: the slot is this wavefront's alone
+        const uint32_t nwords = (lead + total + 31u) >> 5, gw = pos >> 5;
+        const bool carry_tail = ((lead + total) & 31u) != 0 && sgi + 1 != sg_end && nwords > 0;
+        const uint32_t tail_word = carry_tail ? obuf[nwords - 1] : 0u;
+        const uint32_t tail = (lead + total) & 31u;
+        for (uint32_t w = lane; w < nwords; w += kWave) {
+            uint32_t v = obuf[w];
+            obuf[w] = 0u;
+            if (REDO && merge_tail && tail != 0 && sgi + 1 == sg_end && w == nwords - 1)
+                v = local_redo_tail(v, slot[gw + w], tail);
+            if (!(carry_tail && w == nwords - 1)) slot[gw + w] = v;
+        }
+        pending = tail_word;
+        pos += total;
+        wave_lds_fence();
+    };
+
+    for (; sg < sg_end; sg++) {
+        const auto cur = feeder.pre_direct;
+        const Seg g = gnext;
+        uint32_t ref_sample = 0;
+        if (pp && g.b0 == 0 && lane == 0)
+            ref_sample = load_sample_bytes(in + g.samp0 * c.bytes, c.bytes, msb) & low_mask32(c.bps);
+        if (sg + 1 < sg_end) gnext = seg_next(c, gnext);
+        feeder.prefetch_direct(c, in, gnext, lane);       // the next segment's loads fly during this one
+        if (feeder.direct_ok(c, g)) {
+            uint32_t w[BS / 2];
+            direct_finish<BS, BYTES>(c, g, cur, lane, w);
+            do_segment(g, ref_sample, sg, w);
+        } else {
+            feeder.feed_now(c, in, g, rows, stride, lane);
+            do_segment(g, ref_sample, sg, nullptr);
+        }
+    }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1748,6 +1960,26 @@ void launch_pack_t(const Cfg &c, const uint8_t *in, const EncWorkspace &ws, uint
 }
 
 template <int BS, int BYTES>
+void launch_local_t(bool redo, const Cfg &c, const uint8_t *in, const EncWorkspace &ws, const LocalLaunch &l, uint32_t fast_ok,
+                    hipStream_t st)
+{
+    if constexpr (Feeder<BS, BYTES>::DIRECT) {
+        const LaunchGeom g = make_geom(c, true);
+        const uint64_t waves = (c.total_segs + l.segs_per_wave - 1) / l.segs_per_wave;
+        const uint32_t grid = (uint32_t)((waves + g.waves_per_block - 1) / g.waves_per_block);
+        if (redo)
+            hipLaunchKernelGGL((k_encode_local<BS, BYTES, true>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, c,
+                               in, ws.seg_bits, ws.seg_clamp, ws.seg_kin, ws.seg_start, l, g.obuf_words, fast_ok);
+        else
+            hipLaunchKernelGGL((k_encode_local<BS, BYTES, false>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, c,
+                               in, ws.seg_bits, ws.seg_clamp, ws.seg_kin, ws.seg_start, l, g.obuf_words, fast_ok);
+    } else {
+        // local_plan opens the route for direct_shape() only: a launch without a kernel leaves the call's launch error set
+        (void)hipLaunchKernel(nullptr, dim3(1), dim3(1), nullptr, 0, st);
+    }
+}
+
+template <int BS, int BYTES>
 void launch_chunks_t(bool pack, const Cfg &c, const uint8_t *in, const ChunksLaunch &k, const EncWorkspace &ws,
                      uint32_t *out_words, uint64_t cap_words, uint32_t fast_ok, hipStream_t st)
 {
@@ -1900,6 +2132,17 @@ void enc_part_chunks(bool pack, const Cfg &c, const uint8_t *in, const ChunksLau
 }
 template void enc_part_chunks<AEC_ENC_PART>(bool, const Cfg &, const uint8_t *, const ChunksLaunch &, const EncWorkspace &,
                                             uint32_t *, uint64_t, uint32_t, hipStream_t);
+#if AEC_ENC_PART == 8 || AEC_ENC_PART == 16 || AEC_ENC_PART == 32
+template <int BS>
+void enc_part_local(bool redo, const Cfg &c, const uint8_t *in, const EncWorkspace &ws, const LocalLaunch &l, uint32_t fast_ok,
+                    hipStream_t st)
+{
+    if (c.bytes == 1) launch_local_t<BS, 1>(redo, c, in, ws, l, fast_ok, st);
+    else launch_local_t<BS, 2>(redo, c, in, ws, l, fast_ok, st);
+}
+template void enc_part_local<AEC_ENC_PART>(bool, const Cfg &, const uint8_t *, const EncWorkspace &, const LocalLaunch &, uint32_t,
+                                           hipStream_t);
+#endif
 #if AEC_ENC_PART != 0
 template void enc_part_fused<AEC_ENC_PART>(const Cfg &, const uint8_t *, uint32_t *, uint64_t, const FusedGeom &, void *,
                                            uint32_t, uint32_t, uint64_t *, SegEntry *, EncResult *, uint32_t, hipStream_t);
@@ -1915,6 +2158,12 @@ AEC_ENC_EXTERN(0) AEC_ENC_EXTERN(8) AEC_ENC_EXTERN(16) AEC_ENC_EXTERN(32) AEC_EN
     extern template void enc_part_fused<BS>(const Cfg &, const uint8_t *, uint32_t *, uint64_t, const FusedGeom &, void *,    \
                                             uint32_t, uint32_t, uint64_t *, SegEntry *, EncResult *, uint32_t, hipStream_t);
 AEC_ENC_EXTERN(8) AEC_ENC_EXTERN(16) AEC_ENC_EXTERN(32) AEC_ENC_EXTERN(64)
+#undef AEC_ENC_EXTERN
+
+#define AEC_ENC_EXTERN(BS)                                                                                                  \
+    extern template void enc_part_local<BS>(bool, const Cfg &, const uint8_t *, const EncWorkspace &, const LocalLaunch &,    \
+                                            uint32_t, hipStream_t);
+AEC_ENC_EXTERN(8) AEC_ENC_EXTERN(16) AEC_ENC_EXTERN(32)
 #undef AEC_ENC_EXTERN
 
 #define AEC_ENC_EXTERN(BS)                                                                                                  \
@@ -1968,18 +2217,63 @@ size_t fused_ctl_bytes(const Cfg &c)
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ---- the route that codes every block once (aec_enc_local.h) ------------------------------------------------------------
+// Open to a plain whole encode (launch_encode: ENC_ALL, no ShardCarry) of a shape whose kernels hold the block in the
+// lane's registers (Feeder::DIRECT, preprocessor on).  Taken where it was measured to win (profiles/r11/README.md):
+// 16-bit samples in blocks of 16 in RSIs of whole segments (rsi a multiple of 64: every segment has its 64 blocks, as at
+// the measured rsi 128), from kLocalMinSegs such segments (256 MiB) on -- below, the additional launch and the copy of
+// the stream cost more than the second feed of the input.  8-bit samples in blocks of 8 lose at every size (their runs
+// are a quarter as long, and the placement pays per run); RSIs of part segments have shorter runs still and were not
+// measured.  The tuning build takes it for every open shape with AEC_ENC_LOCAL=1.
+static const uint64_t kLocalMinSegs = 131072;
+
+struct LocalPlan {
+    bool on;
+    uint32_t segs_per_wave, slot_words, guess;
+    uint64_t waves;
+    size_t off_first, off_kused, bytes;        // inside the area: the image at 0, then the two per-segment arrays
+};
+
+static LocalPlan local_plan(const Cfg &c)
+{
+    LocalPlan p{};
+    const bool direct = (c.bs == 8 || c.bs == 16 || c.bs == 32) && direct_shape(c.bs, c.bytes);
+    const uint32_t force = tune("AEC_ENC_LOCAL", 2);
+    const bool wins = c.bs == 16 && c.bytes == 2 && c.rsi % 64 == 0 && c.total_segs >= kLocalMinSegs;
+    p.on = direct && (c.flags & F_PREPROCESS) && c.total_segs != 0 && force != 0 && (force == 1 || wins);
+    if (!p.on) return p;
+    p.segs_per_wave = make_geom(c, true).segs_per_wave;
+    const uint32_t spw = tune("AEC_ENC_LOCAL_SPW", 0);
+    if (spw == 1 || spw == 2 || spw == 4 || spw == 8) p.segs_per_wave = spw;
+    p.guess = tune_set("AEC_ENC_LOCAL_GUESS") ? tune("AEC_ENC_LOCAL_GUESS", 0) & 0xFFu : kLocalGuessRule;
+    p.slot_words = local_slot_words(c.id_len, c.bs, c.bps, c.rsi, p.segs_per_wave);
+    p.waves = (c.total_segs + p.segs_per_wave - 1) / p.segs_per_wave;
+    p.off_first = align_up((size_t)p.waves * p.slot_words * 4, 256);
+    p.off_kused = align_up(p.off_first + c.total_segs * 2, 256);
+    p.bytes = align_up(p.off_kused + c.total_segs, 256);
+    return p;
+}
+
+// off_local (optional): the caller is a plain whole encode.  Where that takes the route above, *off_local is where its
+// area starts (image, first clamps, used k: 17.4 KiB per 16 KiB of input at 16 bits, block 16 -- 4.66 GB at 4 GiB) and
+// the per-block summaries, which it does not write, take no room; 0 otherwise.
 size_t enc_workspace_bytes(const Cfg &c, size_t *off_meta, size_t *off_bits, size_t *off_clamp,
-                           size_t *off_start, size_t *off_kin, size_t *off_part)
+                           size_t *off_start, size_t *off_kin, size_t *off_part, size_t *off_local)
 {
     size_t o = 0;
     const uint64_t nseg = c.total_segs ? c.total_segs : 1;
     const uint64_t nchunks = (nseg + kScanChunk - 1) / kScanChunk + 1;
-    *off_meta = o;  o = align_up(o + (c.total_blocks + 1) * 4, 256);
+    const LocalPlan lp = off_local ? local_plan(c) : LocalPlan{};
+    *off_meta = o;  o = align_up(o + (lp.on ? 1 : c.total_blocks + 1) * 4, 256);
     *off_bits = o;  o = align_up(o + nseg * 4, 256);
     *off_clamp = o; o = align_up(o + nseg * 2, 256);
     *off_start = o; o = align_up(o + nseg * 8, 256);
     *off_kin = o;   o = align_up(o + nseg, 256);
     *off_part = o;  o = align_up(o + nchunks * sizeof(ScanPartial), 256);
+    if (off_local) {
+        *off_local = lp.on ? o : 0;
+        o += lp.bytes;
+    }
     return o;
 }
 
@@ -2011,6 +2305,39 @@ void launch_encode(const Cfg &c, const uint8_t *d_in, uint8_t *d_out, size_t out
         case 32: enc_part_fused<32>(c, d_in, out_words, cap_words, g, ws.fused_ctl, start_bit, k_in, d_rsi_off, d_seg_table, d_res, fast_ok, st); break;
         default: enc_part_fused<64>(c, d_in, out_words, cap_words, g, ws.fused_ctl, start_bit, k_in, d_rsi_off, d_seg_table, d_res, fast_ok, st); break;
         }
+        mark(4);
+        return;
+    }
+    if (phases == ENC_ALL && ws.local && !d_carry) {
+        // every block coded once: local encode | scan | redo of the missed runs | placement
+        const LocalPlan lp = local_plan(c);
+        const LocalLaunch l{reinterpret_cast<uint32_t *>(ws.local), reinterpret_cast<uint16_t *>(ws.local + lp.off_first),
+                            ws.local + lp.off_kused, lp.slot_words, lp.segs_per_wave, k_in, lp.guess};
+        auto part = [&](bool redo) {
+            switch (c.bs) {
+            case 8: enc_part_local<8>(redo, c, d_in, ws, l, fast_ok, st); break;
+            case 16: enc_part_local<16>(redo, c, d_in, ws, l, fast_ok, st); break;
+            default: enc_part_local<32>(redo, c, d_in, ws, l, fast_ok, st); break;
+            }
+        };
+        mark(0);
+        part(false);
+        mark(1);
+        hipLaunchKernelGGL(k_scan_reduce, dim3((uint32_t)nchunks), dim3(256), 0, st, ws.seg_bits, ws.seg_clamp, nseg,
+                           ws.partials);
+        hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, st, ws.partials, nchunks, start_bit, k_in, d_res);
+        hipLaunchKernelGGL(k_scan_apply, dim3((uint32_t)nchunks), dim3(256), 0, st, ws.seg_bits, ws.seg_clamp, nseg,
+                           ws.partials, start_bit, k_in, c.segs_per_rsi, c.rsi_count, ws.seg_start, ws.seg_kin, d_rsi_off,
+                           d_res, out_words, cap_words, lp.segs_per_wave, d_carry);
+        if (d_seg_table)
+            hipLaunchKernelGGL(k_seg_table, dim3((uint32_t)((nseg + 255) / 256)), dim3(256), 0, st, c, d_in, ws.seg_start,
+                               d_seg_table);
+        mark(2);
+        part(true);
+        mark(3);
+        hipLaunchKernelGGL(k_place, dim3((uint32_t)((lp.waves + 4 * kPlaceSlots - 1) / (4 * kPlaceSlots))), dim3(256), 0, st,
+                           l.image, lp.slot_words, ws.seg_start, nseg, lp.segs_per_wave, lp.waves, start_bit, d_res,
+                           out_words, cap_words);
         mark(4);
         return;
     }

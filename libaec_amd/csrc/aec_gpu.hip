@@ -127,11 +127,17 @@ uint64_t aec_gpu_block_count(const aec_gpu_params *p, size_t in_bytes)
 }
 
 // reserves the workspace of the two-pass encoder for c (exactly what it needs) and points ws into it
-static int reserve_two_pass(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws)
+// (whole: for a plain whole encode, which may code every block once and then needs that route's area: aec_enc_local.h)
+static int reserve_two_pass(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws, bool whole = false)
 {
-    size_t o[6];
-    const size_t need = enc_workspace_bytes(c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5]);
-    if (!ctx->ws.replace(need, need)) return RC_MEM_ERROR;
+    size_t o[6], local = 0;
+    const size_t need = enc_workspace_bytes(c, &o[0], &o[1], &o[2], &o[3], &o[4], &o[5], whole ? &local : nullptr);
+    if (!ctx->ws.replace(need, need)) {
+        // no room for the route's area: the analyze / scan / pack kernels, which need an eighth of the input
+        if (!local) return RC_MEM_ERROR;
+        (void)hipGetLastError();
+        return reserve_two_pass(ctx, c, ws, false);
+    }
     uint8_t *base = static_cast<uint8_t *>(ctx->ws.p);
     *ws = EncWorkspace{};
     ws->meta = reinterpret_cast<uint32_t *>(base + o[0]);
@@ -140,6 +146,7 @@ static int reserve_two_pass(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws)
     ws->seg_start = reinterpret_cast<uint64_t *>(base + o[3]);
     ws->seg_kin = base + o[4];
     ws->partials = reinterpret_cast<ScanPartial *>(base + o[5]);
+    if (local) ws->local = base + local;
     return RC_OK;
 }
 
@@ -172,7 +179,7 @@ int aec_gpu_reserve(aec_gpu_ctx *ctx, const aec_gpu_params *p, size_t in_bytes)
     // what aec_gpu_encode_async needs; the (much larger) workspace of the plan / emit pair is
     // allocated by the first plan call
     EncWorkspace ws;
-    return fused_supported(c) ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws);
+    return fused_supported(c) ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws, true);
 }
 
 static int encode_phases(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -188,7 +195,7 @@ static int encode_phases(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *
         return RC_CONF_ERROR;
     const bool fused = phases == ENC_ALL && !d_carry && fused_supported(c);
     EncWorkspace ws;
-    rc = fused ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws);
+    rc = fused ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws, phases == ENC_ALL && !d_carry);
     if (rc != RC_OK) return rc;
     (void)hipGetLastError();   // only launch errors of THIS call are reported below
     launch_encode(c, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), out_cap, start_bit,

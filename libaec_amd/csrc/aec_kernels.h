@@ -57,6 +57,7 @@ struct EncWorkspace {
     uint8_t *seg_kin;        // [total_segs]     k carried into the segment
     ScanPartial *partials;   // [ceil(total_segs / 2048) + 1]
     void *fused_ctl;         // single-pass encoder: ticket, fail flag, look-back granules (fused_ctl_bytes)
+    uint8_t *local;          // the route that codes every block once: its area (enc_workspace_bytes), null = not taken
 };
 
 // Single-pass encoder (aec_enc.hip k_encode_fused): available for the templated block sizes.
@@ -72,8 +73,10 @@ struct PhaseEvents {
 
 static const uint32_t kScanChunk = 2048;   // segments per scan workgroup (256 threads x 8)
 
+// off_local (optional, asked for by a plain whole encode): where the area of the route that codes every block once
+// starts (aec_enc_local.h), 0 = this call does not take it
 size_t enc_workspace_bytes(const Cfg &c, size_t *off_meta, size_t *off_bits, size_t *off_clamp,
-                           size_t *off_start, size_t *off_kin, size_t *off_part);
+                           size_t *off_start, size_t *off_kin, size_t *off_part, size_t *off_local = nullptr);
 
 // Enqueues analyze -> scan -> clear -> pack on `stream`.  d_out must be 4-byte aligned and hold
 // out_cap bytes; bit `start_bit` (0..7) of d_out[0] is where the stream continues, k_in is the
