@@ -62,13 +62,8 @@ AEC_GPU_API int aec_gpu_sz_unmarshal_async(const SZ_com_t *sz, const void *d_cod
  * 1 when the one-call forms below take such a batch: the layout is valid and aec_gpu_uniform_batch_ok holds for
  * (coder, coder_bytes, n_chunks).  A stride coder_bytes that is not a multiple of 16 is SERVED: the encoder's fast
  * loads need 16-byte aligned RSIs and it takes its byte-wise loader otherwise, the decoder stores whole blocks from a
- * 16-byte aligned base whatever the RSI size.  When 0 (a chunk of more than 2048 segments of 64 blocks, ...):
- *     aec_gpu_sz_layout(sz, chunk_bytes, &L);
- *     aec_gpu_sz_marshal_async(sz, d_src, chunk_bytes, n, d_work, stream);         (skip when L.passthrough)
- *     offsets[i] = i * L.coder_bytes  (host array; chunk by chunk where coder_bytes is not a multiple of 16)
- *     aec_gpu_encode_batch_async(ctx, &L.coder, d_work, offsets, n, d_out, slot_bytes, d_results, stream);
- * or, where coder_bytes is a multiple of 16, as one launch set for all chunks (aec_gpu.h):
- *     aec_gpu_encode_chunks_async(ctx, &L.coder, d_work, offsets, sizes, n, d_out, cap, d_chunks, NULL, d_result, stream);
+ * 16-byte aligned base whatever the RSI size.  When 0 (a chunk of more than 2048 segments of 64 blocks, ...), or when
+ * the chunks differ in size: aec_gpu_sz_compress_chunks_async below takes any batch in one call.
  */
 AEC_GPU_API int aec_gpu_sz_batch_ok(const SZ_com_t *sz, size_t chunk_bytes, uint64_t n_chunks);
 
@@ -97,6 +92,71 @@ AEC_GPU_API int aec_gpu_sz_decompress_batch_async(aec_gpu_ctx *ctx, const SZ_com
                                                   size_t chunk_bytes, uint64_t *d_rsi_bit_offsets, void *d_work,
                                                   void *d_dst, aec_gpu_dec_result *d_results,
                                                   aec_gpu_dec_result *d_result, void *stream);
+
+/*
+ * Chunks of ANY size under one SZ_com_t, in one call: the marshalling above per chunk around the chunk coder of
+ * aec_gpu.h (aec_gpu_encode_chunks_async / aec_gpu_decode_chunks_async: one launch set for the whole batch, no limit on
+ * a chunk's segments, and the encoder's RSI table, with which the decoder needs no index pass).  Every array argument
+ * is a HOST array of n_chunks entries and is free again when the call returns.
+ *
+ * aec_gpu_sz_chunks_plan is host arithmetic only (1 = the batch is taken, 0 = it would be refused).  Chunk i has
+ * coder_bytes_i = aec_gpu_sz_layout(sz, chunk_bytes[i]).coder_bytes and a room of its own in d_work at work_offsets[i],
+ * the running sum of up16(coder_bytes_j), j < i (work_offsets is optional).  Refused, and AEC_CONF_ERROR from the two
+ * calls with nothing enqueued: an SZ_com_t aec_gpu_sz_layout rejects; a chunk without a whole pixel; a batch
+ * aec_gpu_encode_chunks_plan refuses; totals a launch cannot count -- a chunk of 2^35 bytes or more, or more than 2^25
+ * wavefronts of 64 lanes, a lane per 16 bytes of max(coder_bytes_i, chunk_bytes_i) + 30 and every chunk rounded up to
+ * whole wavefronts (no launch then counts beyond 2^31 lanes); a missing or misaligned d_work where one is needed.
+ * n_chunks == 0: AEC_OK, nothing is enqueued.
+ */
+typedef struct aec_gpu_sz_chunks_plan_s {
+    aec_gpu_params coder;     /* as aec_gpu_sz_layout gives it (the encoder's flags) */
+    size_t   work_bytes;      /* d_work: the sum of up16(coder_bytes_i) */
+    size_t   out_bound;       /* = aec_gpu_encode_chunks_plan(coder, coder_bytes[]).out_bound: an out_cap that never overflows */
+    uint64_t rsi_entries;     /* the sum of lines_i + 1 (= that plan's rsi_entries): entries of d_rsi_bit_offsets */
+    size_t   workspace_bytes; /* device memory the context holds for such a batch: the coder's and this layer's
+                                 descriptors and wavefront table (aec_gpu_held_bytes counts it, aec_gpu_trim releases it) */
+    unsigned direct;          /* 1: every chunk's layout says passthrough */
+} aec_gpu_sz_chunks_plan_t;
+AEC_GPU_API int aec_gpu_sz_chunks_plan(const SZ_com_t *sz, const uint64_t *chunk_bytes, uint64_t n_chunks,
+                                       aec_gpu_sz_chunks_plan_t *plan, uint64_t *work_offsets);
+
+/*
+ * SZ_BufftoBuffCompress of n_chunks chunks in one enqueue.  Chunk i is chunk_bytes[i] bytes at d_src + src_offsets[i]:
+ * any byte offset, any order; chunks do not overlap and nothing between them is read.  Stream i is byte for byte what
+ * SZ_BufftoBuffCompress returns for chunk i; the streams lie back to back in d_out in chunk order.  d_out, out_cap
+ * (overflow; nothing is written at or beyond out_cap), d_chunks and d_result: exactly as aec_gpu_encode_chunks_async
+ * defines them.  d_rsi_bit_offsets (optional, plan.rsi_entries entries) receives that call's table.
+ * d_work (plan.work_bytes bytes, 16-byte aligned): after the call d_work + work_offsets[i] holds chunk i's coder input,
+ * coder_bytes_i bytes; the up to 15 bytes between that and the next room are not written, nor is anything outside
+ * [d_work, d_work + work_bytes).  When plan.direct holds and every d_src + src_offsets[i] is 16-byte aligned the chunks
+ * are coded where they lie and d_work may be NULL.
+ * Per chunk: planes are split in registers when the chunk's own layout allows it (see above) and the chunk lies at a
+ * 16-byte aligned address; every other chunk of the batch moves by 16-byte groups and bytes.  One odd chunk does not
+ * slow the others.  The call synchronises the device only where a buffer of the context grows.
+ */
+AEC_GPU_API int aec_gpu_sz_compress_chunks_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, const void *d_src,
+                                                 const uint64_t *src_offsets, const uint64_t *chunk_bytes,
+                                                 uint64_t n_chunks, void *d_work, void *d_out, size_t out_cap,
+                                                 aec_gpu_batch_chunk *d_chunks, uint64_t *d_rsi_bit_offsets,
+                                                 aec_gpu_enc_result *d_result, void *stream);
+
+/*
+ * SZ_BufftoBuffDecompress of n_chunks streams in one enqueue.  d_in, in_bytes, have_table, in_offsets, in_bytes_each,
+ * d_rsi_bit_offsets, d_results and d_result are exactly those of aec_gpu_decode_chunks_async with out_bytes[i] =
+ * coder_bytes_i and out_offsets[i] = work_offsets[i]: with have_table != 0 the table is the one the compress call wrote,
+ * no index pass runs and in_offsets / in_bytes_each may be NULL.  Exactly chunk_bytes[i] bytes are written at
+ * d_dst + dst_offsets[i] (any byte offset) and nothing outside them; a trailing fraction of a pixel comes back zero.
+ * The bytes of a chunk whose record is not clean are unspecified, every other chunk is exact.  The decode goes to d_work
+ * (plan.work_bytes bytes, 16-byte aligned), or straight to d_dst when plan.direct holds and every d_dst + dst_offsets[i]
+ * is 16-byte aligned (d_work may then be NULL).
+ */
+AEC_GPU_API int aec_gpu_sz_decompress_chunks_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, const void *d_in,
+                                                   size_t in_bytes, const uint64_t *in_offsets,
+                                                   const uint64_t *in_bytes_each, const uint64_t *dst_offsets,
+                                                   const uint64_t *chunk_bytes, uint64_t n_chunks,
+                                                   uint64_t *d_rsi_bit_offsets, int have_table, void *d_work, void *d_dst,
+                                                   aec_gpu_dec_result *d_results, aec_gpu_dec_result *d_result,
+                                                   void *stream);
 
 #ifdef __cplusplus
 }

@@ -48,9 +48,11 @@ struct aec_gpu_ctx {
     DevBuf dec_ws;         // workspace of the segment-wise decode of bare streams (aec_dec.hip: launch_decode_bare)
     DevBuf range_ws;       // whole blocks of a range decode whose window does not start on an RSI / end on a block
     DevBuf chunks_d;       // the chunk calls: the descriptors and the per-wave / per-item table
+    DevBuf sz_d;           // the SZIP chunk calls (aec_sz.hip): their descriptors and per-wave table, which must outlive
+                           // the coder call in between (that call re-sends into chunks_d and may free it to grow it)
     // ... of which aec_gpu_held_bytes counts, aec_gpu_trim frees and aec_gpu_destroy releases these: a new one goes here
     // (pointers into the context itself, which is never copied)
-    DevBuf *const held[6] = {&ws, &fused, &idx_ws, &dec_ws, &range_ws, &chunks_d};
+    DevBuf *const held[7] = {&ws, &fused, &idx_ws, &dec_ws, &range_ws, &chunks_d, &sz_d};
     DevBuf carry;          // device record: what precedes this context's shard (emit_planned); a ShardCarry, never trimmed
     // the pinned buffers the chunk calls write their descriptors to -- kChunkStages, taken in turn, each guarded by the
     // event of its last transfer (stage_descriptors / send_descriptors); never trimmed
@@ -624,18 +626,34 @@ static aec_gpu_ctx::ChunkStage *stage_descriptors(aec_gpu_ctx *ctx, size_t h_nee
     return s.h.replace(h_need, h_need + h_need / 4 + 4096) ? &s : nullptr;
 }
 
-// Step 2, once the descriptors are written: h_need bytes of the buffer to chunks_d, which has room for d_need bytes
-// (descriptors and the table behind them).  Growing chunks_d synchronises the device -- no kernel still reads it -- hence
-// after the host's work and before the copy.  Returns chunks_d, null where there is no memory or the copy failed.
-static uint8_t *send_descriptors(aec_gpu_ctx *ctx, aec_gpu_ctx::ChunkStage *s, size_t h_need, size_t d_need, hipStream_t st)
+// Step 2, once the descriptors are written: h_need bytes of the buffer to chunks_d (the SZIP layer: to sz_d), which has
+// room for d_need bytes (descriptors and the table behind them).  Growing it synchronises the device -- no kernel still
+// reads it -- hence after the host's work and before the copy.  Returns the buffer, null where there is no memory or the
+// copy failed.
+static uint8_t *send_descriptors(DevBuf &d, aec_gpu_ctx::ChunkStage *s, size_t h_need, size_t d_need, hipStream_t st)
 {
-    if (!ctx->chunks_d.replace(d_need, (d_need + d_need / 4 + 255) & ~(size_t)255)) return nullptr;
+    if (!d.replace(d_need, (d_need + d_need / 4 + 255) & ~(size_t)255)) return nullptr;
     (void)hipGetLastError();   // only errors of THIS call are reported by it
-    if (hipMemcpyAsync(ctx->chunks_d.p, s->h.p, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
+    if (hipMemcpyAsync(d.p, s->h.p, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipEventRecord(s->ev, st) != hipSuccess)
         return nullptr;
-    return static_cast<uint8_t *>(ctx->chunks_d.p);
+    return static_cast<uint8_t *>(d.p);
 }
+
+// the same two steps for aec_sz.hip, which does not see the context (aec_kernels.h)
+extern "C++" {
+void *aec::ctx_sz_stage(aec_gpu_ctx *ctx, size_t h_need, void **h)
+{
+    aec_gpu_ctx::ChunkStage *s = stage_descriptors(ctx, h_need);
+    if (s) *h = s->h.p;
+    return s;
+}
+
+uint8_t *aec::ctx_sz_send(aec_gpu_ctx *ctx, void *stage, size_t h_need, size_t d_need, hipStream_t st)
+{
+    return send_descriptors(ctx->sz_d, static_cast<aec_gpu_ctx::ChunkStage *>(stage), h_need, d_need, st);
+}
+}  // extern "C++"
 
 // ---- a batch of unequal chunks as one launch set (aec_chunks.h) -------------------------------------------------------
 namespace {
@@ -726,7 +744,7 @@ int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
     EncWorkspace ws;
     const int rc = reserve_two_pass(ctx, sh.c, &ws);
     if (rc != RC_OK) return rc;
-    uint8_t *cd = send_descriptors(ctx, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
+    uint8_t *cd = send_descriptors(ctx->chunks_d, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
     if (!cd) return RC_MEM_ERROR;
     const ChunksLaunch k{reinterpret_cast<const ChunkDesc *>(cd), reinterpret_cast<uint32_t *>(cd + sh.desc_bytes), n_chunks,
                          sh.waves, sh.spw};
@@ -811,7 +829,7 @@ int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
     DChunksShape sh;
     if (!dchunks_shape(p, in_offsets, in_bytes_each, out_offsets, out_bytes, n_chunks, &sh, static_cast<DChunkDesc *>(stage->h.p)))
         return RC_CONF_ERROR;
-    uint8_t *cd = send_descriptors(ctx, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
+    uint8_t *cd = send_descriptors(ctx->chunks_d, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
     if (!cd) return RC_MEM_ERROR;
     const DChunkDesc *d_desc = reinterpret_cast<const DChunkDesc *>(cd);
     uint32_t *d_item_chunk = reinterpret_cast<uint32_t *>(cd + sh.desc_bytes);

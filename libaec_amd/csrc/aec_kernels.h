@@ -6,6 +6,8 @@
 
 #include "aec_cfg.h"
 
+struct aec_gpu_ctx;
+
 namespace aec {
 
 // One entry per 2048 segments for the three-phase scan of (bit length, k clamp).
@@ -259,5 +261,13 @@ void launch_index_batch(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
 // are not the low-entropy kind, or too much for one span of tables: every stream is walked serially)
 size_t index_batch_workspace_bytes(const Cfg &c, size_t in_bytes, uint64_t n_chunks, size_t max_chunk_bytes,
                                    uint64_t rsi_bits_hint);
+
+// ---- the context's descriptor transfer, for the SZIP chunk calls (aec_gpu.hip; used by aec_sz.hip) ------------------------
+// Step 1: the pinned buffer of the context whose turn it is (the chunk calls' own stages, guarded by their events), with
+// room for h_need bytes and free to write: *h.  Returns the stage for step 2, null where there is no memory.
+// Step 2: h_need bytes of it, in stream order, to the context's device buffer of the SZIP layer, which gets room for
+// d_need bytes (it grows like chunks_d, is counted by aec_gpu_held_bytes and released by aec_gpu_trim).  null = failed.
+void *ctx_sz_stage(::aec_gpu_ctx *ctx, size_t h_need, void **h);
+uint8_t *ctx_sz_send(::aec_gpu_ctx *ctx, void *stage, size_t h_need, size_t d_need, hipStream_t st);
 
 }  // namespace aec

@@ -13,7 +13,11 @@
 //           chunks is written by k_sz_fill.
 #include <hip/hip_runtime.h>
 
+#include <memory>
+#include <new>
+
 #include "../../include/aec_gpu_sz.h"
+#include "aec_kernels.h"
 #include "aec_szmap.h"
 
 using namespace aec;
@@ -30,15 +34,19 @@ struct SzGroup {
     bool whole;
 };
 
-__device__ __forceinline__ bool sz_group(uint64_t total, uint32_t head, SzGroup &g)
+__device__ __forceinline__ bool sz_group_at(uint64_t i, uint64_t total, uint32_t head, SzGroup &g)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * kSzBlock + threadIdx.x;
     g.lo = (int64_t)(i * 16u) - (int64_t)head;
     if (g.lo >= (int64_t)total) return false;
     g.first = g.lo < 0 ? 0u : (uint64_t)g.lo;
     g.end = (uint64_t)(g.lo + 16) < total ? (uint64_t)(g.lo + 16) : total;
     g.whole = g.lo >= 0 && (uint64_t)(g.lo + 16) <= total;
     return true;
+}
+
+__device__ __forceinline__ bool sz_group(uint64_t total, uint32_t head, SzGroup &g)
+{
+    return sz_group_at((uint64_t)blockIdx.x * kSzBlock + threadIdx.x, total, head, g);
 }
 
 __device__ __forceinline__ void sz_store_group(uint8_t *out, const SzGroup &g, const uint32_t (&w)[4])
@@ -177,6 +185,162 @@ k_sz_fill(const SzLayout L, const uint8_t *__restrict__ src, uint8_t *__restrict
     }
 }
 
+// ---- batches of unequal chunks (aec_szmap.h: SzChunk) ----------------------------------------------------------------------
+// The same two paths, chosen per chunk.  A chunk owns whole wavefronts of its path's launch; a wavefront reads its chunk's
+// number from the table k_sz_chunks_setup wrote (one uint32_t per wavefront: the byte path's wavefronts, then the plane
+// path's), so the chunk is wave-uniform, its descriptor is read once per wavefront through the scalar cache and no lane
+// searches in front of its 16-byte move.
+constexpr uint32_t kSzWaves = kSzBlock / 64;
+
+__global__ void __launch_bounds__(256)
+k_sz_chunks_setup(const SzChunk *__restrict__ desc, uint64_t n, uint64_t byte_waves, uint64_t plane_waves,
+                  uint32_t *__restrict__ wave_chunk)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < byte_waves + plane_waves; i += stride)
+        wave_chunk[i] = i < byte_waves ? (uint32_t)sz_chunk_of_wave(desc, n, kSzBytes, i)
+                                       : (uint32_t)sz_chunk_of_wave(desc, n, kSzPlanes, i - byte_waves);
+}
+
+// this wavefront's chunk and the lane's number within the chunk; false behind the last wavefront
+__device__ __forceinline__ bool sz_wave_chunk(const SzChunk *__restrict__ desc, const uint32_t *__restrict__ wave_chunk,
+                                              uint64_t nwaves, int path, SzChunk &D, uint64_t &lane)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * kSzWaves + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (w >= nwaves) return false;
+    D = desc[(uint32_t)__builtin_amdgcn_readfirstlane((int)wave_chunk[w])];
+    lane = (w - D.wave0[path]) * 64u + (threadIdx.x & 63u);
+    return true;
+}
+
+// chunks -> their rooms in the work buffer (rooms are 16-byte aligned: only a chunk's last group can be partial)
+__global__ void __launch_bounds__(kSzBlock)
+k_sz_marshal_chunks(const SzLayout L, const SzChunk *__restrict__ desc, const uint32_t *__restrict__ wave_chunk, uint64_t nwaves,
+                    const uint8_t *__restrict__ src, uint8_t *__restrict__ work)
+{
+    SzChunk D;
+    uint64_t lane;
+    SzGroup g;
+    if (!sz_wave_chunk(desc, wave_chunk, nwaves, kSzBytes, D, lane) || !sz_group_at(lane, D.coder_bytes, 0u, g)) return;
+    uint8_t *out = work + D.work_off;
+    SzInCursor c;
+    sz_in_seek(L, D, g.first, c);
+    if (g.whole) {
+        const uint64_t at = sz_in_straight(L, D, c);
+        if (at != kSzZero && (reinterpret_cast<uintptr_t>(src + at) & 15u) == 0) {
+            *reinterpret_cast<uint4 *>(out + g.lo) = *reinterpret_cast<const uint4 *>(src + at);
+            return;
+        }
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        if (g.lo + i >= (int64_t)g.first && g.lo + i < (int64_t)g.end) {
+            w[i >> 2] |= (uint32_t)sz_in_byte(L, D, src, c) << (8 * (i & 3));
+            sz_in_next(L, D, c);
+        }
+    }
+    sz_store_group(out, g, w);
+}
+
+// rooms of the work buffer -> chunks: every chunk has its own head, its first and last groups store bytes (two chunks
+// that share a 16-byte line of the destination write disjoint bytes of it)
+__global__ void __launch_bounds__(kSzBlock)
+k_sz_unmarshal_chunks(const SzLayout L, const SzChunk *__restrict__ desc, const uint32_t *__restrict__ wave_chunk,
+                      uint64_t nwaves, const uint8_t *__restrict__ work, uint8_t *__restrict__ dst)
+{
+    SzChunk D;
+    uint64_t lane;
+    SzGroup g;
+    if (!sz_wave_chunk(desc, wave_chunk, nwaves, kSzBytes, D, lane) || !sz_group_at(lane, D.chunk_bytes, D.head, g)) return;
+    uint8_t *out = dst + D.off;
+    uint64_t d = g.first;
+    if (g.whole) {
+        const uint64_t at = sz_out_straight(L, D, d);
+        if (at != kSzZero && (reinterpret_cast<uintptr_t>(work + at) & 15u) == 0) {
+            *reinterpret_cast<uint4 *>(out + g.lo) = *reinterpret_cast<const uint4 *>(work + at);
+            return;
+        }
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        if (g.lo + i >= (int64_t)g.first && g.lo + i < (int64_t)g.end)
+            w[i >> 2] |= (uint32_t)sz_out_byte(L, D, work, d++) << (8 * (i & 3));
+    sz_store_group(out, g, w);
+}
+
+template <int WORD>
+__global__ void __launch_bounds__(kSzBlock)
+k_sz_split_chunks(const SzLayout L, const SzChunk *__restrict__ desc, const uint32_t *__restrict__ wave_chunk, uint64_t nwaves,
+                  const uint8_t *__restrict__ src, uint8_t *__restrict__ work)
+{
+    SzChunk D;
+    uint64_t m;
+    if (!sz_wave_chunk(desc, wave_chunk, nwaves, kSzPlanes, D, m) || m >= D.pixels / 4u) return;
+    const uint4 *p = reinterpret_cast<const uint4 *>(src + D.off + m * (4u * WORD));
+    uint32_t piece[WORD];
+    if constexpr (WORD == 4) {
+        const uint4 a = p[0];
+        sz_transpose4(a.x, a.y, a.z, a.w, piece);
+    } else {
+        const uint4 a = p[0], b = p[1];
+        sz_transpose4(a.x, a.z, b.x, b.z, piece);
+        sz_transpose4(a.y, a.w, b.y, b.w, piece + 4);
+    }
+#pragma unroll
+    for (int j = 0; j < WORD; j++) *reinterpret_cast<uint32_t *>(work + sz_piece_at(L, D, (uint32_t)j, m)) = piece[j];
+}
+
+template <int WORD>
+__global__ void __launch_bounds__(kSzBlock)
+k_sz_merge_chunks(const SzLayout L, const SzChunk *__restrict__ desc, const uint32_t *__restrict__ wave_chunk, uint64_t nwaves,
+                  const uint8_t *__restrict__ work, uint8_t *__restrict__ dst)
+{
+    SzChunk D;
+    uint64_t m;
+    if (!sz_wave_chunk(desc, wave_chunk, nwaves, kSzPlanes, D, m) || m >= D.pixels / 4u) return;
+    uint32_t piece[WORD];
+#pragma unroll
+    for (int j = 0; j < WORD; j++) piece[j] = *reinterpret_cast<const uint32_t *>(work + sz_piece_at(L, D, (uint32_t)j, m));
+    uint4 *p = reinterpret_cast<uint4 *>(dst + D.off + m * (4u * WORD));
+    uint32_t lo[4];
+    sz_transpose4(piece[0], piece[1], piece[2], piece[3], lo);
+    if constexpr (WORD == 4) {
+        p[0] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    } else {
+        uint32_t hi[4];
+        sz_transpose4(piece[4], piece[5], piece[6], piece[7], hi);
+        p[0] = make_uint4(lo[0], hi[0], lo[1], hi[1]);
+        p[1] = make_uint4(lo[2], hi[2], lo[3], hi[3]);
+    }
+}
+
+// the padding of the plane path's chunks: the chunk's wavefronts take its scan lines in turn, a lane writes 4 bytes
+__global__ void __launch_bounds__(kSzBlock)
+k_sz_fill_chunks(const SzLayout L, const SzChunk *__restrict__ desc, const uint32_t *__restrict__ wave_chunk, uint64_t nwaves,
+                 const uint8_t *__restrict__ src, uint8_t *__restrict__ work)
+{
+    SzChunk D;
+    uint64_t lane;
+    if (!sz_wave_chunk(desc, wave_chunk, nwaves, kSzPlanes, D, lane) || D.coder_bytes == D.coded_bytes) return;
+    SzInCursor c;
+    c.chunk = 0;
+    for (c.l = lane >> 6; c.l < D.lines; c.l += sz_quad_waves(D)) {
+        c.take = sz_take(L, D, c.l);
+        uint8_t *row = work + D.work_off + c.l * L.padded_line;
+        for (uint64_t k = c.take + 4u * (lane & 63u); k < L.padded_line; k += 4u * 64u) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                c.k = k + i;
+                w |= (uint32_t)sz_in_byte(L, D, src, c) << (8 * i);
+            }
+            *reinterpret_cast<uint32_t *>(row + k) = w;
+        }
+    }
+}
+
 int layout_of(const SZ_com_t *sz, size_t chunk_bytes, SzLayout *L)
 {
     if (!sz) return RC_CONF_ERROR;
@@ -235,6 +399,94 @@ bool sizes_ok(const SzLayout &L, uint64_t n)
     const uint64_t most = L.coder_bytes > L.chunk_bytes ? L.coder_bytes : L.chunk_bytes;
     return n <= (1ull << 35) / most && n <= (1ull << 25) / L.lines;
 }
+
+// ---- batches of unequal chunks: host side ---------------------------------------------------------------------------------
+// No launch counts beyond 2^31 lanes: the wavefronts of a batch -- per chunk, the 16-byte groups of the larger of its
+// coder bytes and its chunk bytes behind a head of 15, rounded up to whole wavefronts; the plane path's quads are never
+// more than these -- are at most 2^25, and a chunk has less than 2^35 bytes.
+constexpr uint64_t kSzMaxWaves = 1ull << 25, kSzMaxChunk = 1ull << 35;
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// host arithmetic of a batch under one SZ_com_t: the plan, and (each optional, n entries) the chunks' rooms and coder
+// sizes.  false = refused.
+bool chunks_shape(const SZ_com_t *sz, const uint64_t *chunk_bytes, uint64_t n, SzLayout *L, aec_gpu_sz_chunks_plan_t *plan,
+                  uint64_t *work_offsets, uint64_t *coder_bytes)
+{
+    if (layout_of(sz, 64, L) != RC_OK || (n && !chunk_bytes) || n > 0x7FFFFFFFull) return false;   // (64: whole pixels of any width)
+    std::unique_ptr<uint64_t[]> own;
+    if (!coder_bytes && n) {
+        own.reset(new (std::nothrow) uint64_t[n]);
+        if (!(coder_bytes = own.get())) return false;
+    }
+    uint64_t work = 0, waves = 0;
+    unsigned direct = 1;
+    for (uint64_t i = 0; i < n; i++) {
+        SzChunk D;
+        if (chunk_bytes[i] >= kSzMaxChunk || !sz_chunk_sizes(*L, chunk_bytes[i], D)) return false;
+        if (work_offsets) work_offsets[i] = work;
+        coder_bytes[i] = D.coder_bytes;
+        work += (D.coder_bytes + 15u) & ~(uint64_t)15u;
+        waves += sz_group_waves(D.coder_bytes > D.chunk_bytes ? D.coder_bytes : D.chunk_bytes, 15u);
+        if (waves > kSzMaxWaves) return false;
+        direct &= sz_chunk_passthrough(*L, D) ? 1u : 0u;
+    }
+    const aec_gpu_params p = coder_of(*L, true);
+    aec_gpu_chunks_plan cp;
+    if (!aec_gpu_encode_chunks_plan(&p, coder_bytes, n, &cp)) return false;
+    plan->coder = p;
+    plan->work_bytes = (size_t)work;
+    plan->out_bound = cp.out_bound;
+    plan->rsi_entries = cp.rsi_entries;
+    plan->workspace_bytes = cp.workspace_bytes + up256((size_t)(n + 1) * sizeof(SzChunk)) + up256((size_t)(waves ? waves : 1) * 4);
+    plan->direct = direct;
+    return true;
+}
+
+bool all_aligned(const void *base, const uint64_t *offsets, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; i++)
+        if ((reinterpret_cast<uintptr_t>(base) + offsets[i]) & 15u) return false;
+    return true;
+}
+
+// the descriptors of a batch on the device and the wavefront table behind them, filled (one transfer, one launch)
+struct SzChunksOnDevice {
+    const SzChunk *desc;
+    const uint32_t *wave_chunk;         // the byte path's wavefronts, then the plane path's
+    uint64_t waves[2];
+    bool fill;                          // a chunk of the plane path has padding
+};
+
+int send_chunks(aec_gpu_ctx *ctx, const SzLayout &L, const void *base, const uint64_t *offsets, const uint64_t *chunk_bytes,
+                uint64_t n, bool unmarshal, hipStream_t st, SzChunksOnDevice *on)
+{
+    const size_t h_need = (size_t)(n + 1) * sizeof(SzChunk);
+    void *h = nullptr;
+    void *stage = ctx_sz_stage(ctx, h_need, &h);
+    if (!stage) return RC_MEM_ERROR;
+    SzChunk *d = static_cast<SzChunk *>(h);
+    if (!sz_make_chunks(L, reinterpret_cast<uintptr_t>(base), offsets, chunk_bytes, n, unmarshal, d)) return RC_CONF_ERROR;
+    on->waves[kSzBytes] = d[n].wave0[kSzBytes];
+    on->waves[kSzPlanes] = d[n].wave0[kSzPlanes];
+    on->fill = false;
+    for (uint64_t i = 0; i < n; i++) on->fill |= d[i].planes && d[i].coder_bytes != d[i].coded_bytes;
+    const uint64_t waves = on->waves[kSzBytes] + on->waves[kSzPlanes];
+    const size_t desc_bytes = up256(h_need);
+    uint8_t *cd = ctx_sz_send(ctx, stage, h_need, desc_bytes + up256((size_t)(waves ? waves : 1) * 4), st);
+    if (!cd) return RC_MEM_ERROR;
+    on->desc = reinterpret_cast<const SzChunk *>(cd);
+    uint32_t *table = reinterpret_cast<uint32_t *>(cd + desc_bytes);
+    on->wave_chunk = table;
+    if (waves) {
+        const uint64_t grid = (waves + 255) / 256;
+        hipLaunchKernelGGL(k_sz_chunks_setup, dim3((uint32_t)(grid < 4096 ? grid : 4096)), dim3(256), 0, st, on->desc, n,
+                           on->waves[kSzBytes], on->waves[kSzPlanes], table);
+    }
+    return RC_OK;
+}
+
+uint32_t wave_blocks(uint64_t waves) { return (uint32_t)((waves + kSzWaves - 1) / kSzWaves); }
 
 }  // namespace
 
@@ -327,6 +579,103 @@ int aec_gpu_sz_decompress_batch_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, cons
     if (rc != RC_OK || direct) return rc;
     return unmarshal(L, static_cast<const uint8_t *>(d_work), n_chunks, static_cast<uint8_t *>(d_dst),
                      static_cast<hipStream_t>(stream));
+}
+
+int aec_gpu_sz_chunks_plan(const SZ_com_t *sz, const uint64_t *chunk_bytes, uint64_t n_chunks, aec_gpu_sz_chunks_plan_t *plan,
+                           uint64_t *work_offsets)
+{
+    SzLayout L;
+    return plan && chunks_shape(sz, chunk_bytes, n_chunks, &L, plan, work_offsets, nullptr) ? 1 : 0;
+}
+
+int aec_gpu_sz_compress_chunks_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, const void *d_src, const uint64_t *src_offsets,
+                                     const uint64_t *chunk_bytes, uint64_t n_chunks, void *d_work, void *d_out, size_t out_cap,
+                                     aec_gpu_batch_chunk *d_chunks, uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result,
+                                     void *stream)
+{
+    SzLayout L;
+    if (layout_of(sz, 64, &L) != RC_OK) return RC_CONF_ERROR;
+    if (n_chunks == 0) return RC_OK;
+    if (!ctx || !d_src || !src_offsets || !chunk_bytes || !d_out || !d_chunks || !d_result || !aligned(d_out, 16) ||
+        (out_cap & 15u) || out_cap < 16 || n_chunks > 0x7FFFFFFFull)
+        return RC_CONF_ERROR;
+    // (host arrays of the call: coder sizes, rooms, and the chunks' offsets from a 16-byte aligned base when coded in place)
+    std::unique_ptr<uint64_t[]> arrays(new (std::nothrow) uint64_t[3 * n_chunks]);
+    if (!arrays) return RC_MEM_ERROR;
+    uint64_t *coder_bytes = arrays.get(), *work_offsets = coder_bytes + n_chunks, *in_place = work_offsets + n_chunks;
+    aec_gpu_sz_chunks_plan_t plan;
+    if (!chunks_shape(sz, chunk_bytes, n_chunks, &L, &plan, work_offsets, coder_bytes)) return RC_CONF_ERROR;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t *src = static_cast<const uint8_t *>(d_src);
+    if (plan.direct && all_aligned(d_src, src_offsets, n_chunks)) {
+        const uint64_t skew = reinterpret_cast<uintptr_t>(d_src) & 15u;
+        for (uint64_t i = 0; i < n_chunks; i++) in_place[i] = src_offsets[i] + skew;
+        return aec_gpu_encode_chunks_async(ctx, &plan.coder, src - skew, in_place, coder_bytes, n_chunks, d_out, out_cap,
+                                           d_chunks, d_rsi_bit_offsets, d_result, stream);
+    }
+    if (!d_work || !aligned(d_work, 16)) return RC_CONF_ERROR;
+    uint8_t *work = static_cast<uint8_t *>(d_work);
+    SzChunksOnDevice on;
+    const int rc = send_chunks(ctx, L, d_src, src_offsets, chunk_bytes, n_chunks, false, st, &on);
+    if (rc != RC_OK) return rc;
+    const uint64_t nb = on.waves[kSzBytes], np = on.waves[kSzPlanes];
+    if (np) {
+        if (L.word == 4)
+            hipLaunchKernelGGL(k_sz_split_chunks<4>, dim3(wave_blocks(np)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk + nb, np, src, work);
+        else
+            hipLaunchKernelGGL(k_sz_split_chunks<8>, dim3(wave_blocks(np)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk + nb, np, src, work);
+        if (on.fill)
+            hipLaunchKernelGGL(k_sz_fill_chunks, dim3(wave_blocks(np)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk + nb, np, src, work);
+    }
+    if (nb)
+        hipLaunchKernelGGL(k_sz_marshal_chunks, dim3(wave_blocks(nb)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk, nb, src, work);
+    if (hipGetLastError() != hipSuccess) return RC_MEM_ERROR;
+    return aec_gpu_encode_chunks_async(ctx, &plan.coder, d_work, work_offsets, coder_bytes, n_chunks, d_out, out_cap, d_chunks,
+                                       d_rsi_bit_offsets, d_result, stream);
+}
+
+int aec_gpu_sz_decompress_chunks_async(aec_gpu_ctx *ctx, const SZ_com_t *sz, const void *d_in, size_t in_bytes,
+                                       const uint64_t *in_offsets, const uint64_t *in_bytes_each, const uint64_t *dst_offsets,
+                                       const uint64_t *chunk_bytes, uint64_t n_chunks, uint64_t *d_rsi_bit_offsets,
+                                       int have_table, void *d_work, void *d_dst, aec_gpu_dec_result *d_results,
+                                       aec_gpu_dec_result *d_result, void *stream)
+{
+    SzLayout L;
+    if (layout_of(sz, 64, &L) != RC_OK) return RC_CONF_ERROR;
+    if (n_chunks == 0) return RC_OK;
+    if (!ctx || !d_in || !d_dst || !dst_offsets || !chunk_bytes || n_chunks > 0x7FFFFFFFull) return RC_CONF_ERROR;
+    std::unique_ptr<uint64_t[]> arrays(new (std::nothrow) uint64_t[3 * n_chunks]);
+    if (!arrays) return RC_MEM_ERROR;
+    uint64_t *coder_bytes = arrays.get(), *work_offsets = coder_bytes + n_chunks, *in_place = work_offsets + n_chunks;
+    aec_gpu_sz_chunks_plan_t plan;
+    if (!chunks_shape(sz, chunk_bytes, n_chunks, &L, &plan, work_offsets, coder_bytes)) return RC_CONF_ERROR;
+    const aec_gpu_params p = coder_of(L, false);
+    uint8_t *dst = static_cast<uint8_t *>(d_dst);
+    if (plan.direct && all_aligned(d_dst, dst_offsets, n_chunks)) {
+        const uint64_t skew = reinterpret_cast<uintptr_t>(d_dst) & 15u;
+        for (uint64_t i = 0; i < n_chunks; i++) in_place[i] = dst_offsets[i] + skew;
+        return aec_gpu_decode_chunks_async(ctx, &p, d_in, in_bytes, in_offsets, in_bytes_each, in_place, coder_bytes, n_chunks,
+                                           d_rsi_bit_offsets, have_table, dst - skew, d_results, d_result, stream);
+    }
+    if (!d_work || !aligned(d_work, 16)) return RC_CONF_ERROR;
+    int rc = aec_gpu_decode_chunks_async(ctx, &p, d_in, in_bytes, in_offsets, in_bytes_each, work_offsets, coder_bytes, n_chunks,
+                                         d_rsi_bit_offsets, have_table, d_work, d_results, d_result, stream);
+    if (rc != RC_OK) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t *work = static_cast<const uint8_t *>(d_work);
+    SzChunksOnDevice on;
+    rc = send_chunks(ctx, L, d_dst, dst_offsets, chunk_bytes, n_chunks, true, st, &on);
+    if (rc != RC_OK) return rc;
+    const uint64_t nb = on.waves[kSzBytes], np = on.waves[kSzPlanes];
+    if (np) {
+        if (L.word == 4)
+            hipLaunchKernelGGL(k_sz_merge_chunks<4>, dim3(wave_blocks(np)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk + nb, np, work, dst);
+        else
+            hipLaunchKernelGGL(k_sz_merge_chunks<8>, dim3(wave_blocks(np)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk + nb, np, work, dst);
+    }
+    if (nb)
+        hipLaunchKernelGGL(k_sz_unmarshal_chunks, dim3(wave_blocks(nb)), dim3(kSzBlock), 0, st, L, on.desc, on.wave_chunk, nb, work, dst);
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR;
 }
 
 }  // extern "C"

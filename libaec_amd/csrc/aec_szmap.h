@@ -211,4 +211,175 @@ inline bool sz_planes_fast(const SzLayout &L)
            L.padded_line % 4 == 0;
 }
 
+// ---- batches of UNEQUAL chunks under one SZ_com_t (aec_gpu_sz_*_chunks_async) -----------------------------------------
+// The SZ_com_t fixes line, padded_line, pixel, word and repeat (an SzLayout made for any chunk size holds them); a
+// chunk's size fixes the rest, which travels in a descriptor per chunk.  Every chunk has a room of its own in the work
+// buffer, at a 16-byte aligned offset.  A chunk owns whole wavefronts of a launch: on the byte path one lane per 16-byte
+// group of what is written, on the plane path one lane per four pixels; wave0 holds the running sums of both, so a chunk
+// that takes the other path owns no wavefront of this one.  The maps below are those above with the descriptor in place
+// of chunk * L.chunk_bytes / chunk * L.coder_bytes: they give bytes of the caller's buffer and of the work buffer.
+// tests/emul/sz_chunks_emul.cpp runs them on the CPU.
+constexpr int kSzBytes = 0, kSzPlanes = 1;              // the two paths
+
+struct SzChunk {
+    uint64_t off;               // the chunk in the caller's buffer (d_src / d_dst): any byte offset
+    uint64_t chunk_bytes;
+    uint64_t work_off;          // its room in the work buffer: the running sum of up16(coder_bytes)
+    uint64_t coded_bytes, pixels, lines, coder_bytes;   // as in SzLayout, of this chunk
+    uint64_t wave0[2];          // its first wavefront on the byte path / on the plane path (entry n: the totals)
+    uint32_t planes;            // 1: the chunk takes the plane path in this call
+    uint32_t head;              // un-marshal: (d_dst + off) & 15, the bytes in front of the chunk in its first group
+};
+
+// what the chunk's size fixes (sz_make_layout's arithmetic); false for a chunk without a whole pixel
+AEC_HD bool sz_chunk_sizes(const SzLayout &L, uint64_t chunk_bytes, SzChunk &D)
+{
+    D.chunk_bytes = chunk_bytes;
+    D.coded_bytes = chunk_bytes - chunk_bytes % (L.word ? L.word : L.pixel);
+    D.pixels = L.word ? D.coded_bytes / L.word : 0;
+    D.lines = (D.coded_bytes + L.line - 1) / L.line;
+    D.coder_bytes = D.lines * L.padded_line;
+    return D.coded_bytes != 0;
+}
+
+AEC_HD bool sz_chunk_passthrough(const SzLayout &L, const SzChunk &D)
+{
+    return !L.word && L.padded_line == L.line && D.coded_bytes % L.line == 0 && D.coded_bytes == D.chunk_bytes;
+}
+
+// sz_planes_fast of this chunk (its base alignment is the caller's to check)
+AEC_HD bool sz_chunk_planes_fast(const SzLayout &L, const SzChunk &D)
+{
+    return L.word && D.coded_bytes == D.chunk_bytes && D.chunk_bytes % 16 == 0 && D.pixels % 4 == 0 && L.line % 4 == 0 &&
+           L.padded_line % 4 == 0;
+}
+
+// wavefronts of 64 lanes a chunk owns: groups of `bytes` output bytes that start `head` bytes into a group / quads
+AEC_HD uint64_t sz_group_waves(uint64_t bytes, uint32_t head) { return ((head + bytes + 15u) / 16u + 63u) / 64u; }
+AEC_HD uint64_t sz_quad_waves(const SzChunk &D) { return (D.pixels / 4u + 63u) / 64u; }
+
+// the chunk that owns wavefront w of a path: the LAST chunk whose first wavefront is <= w (chunks that own none share
+// the first wavefront of the next one that does).  w must be below d[n].wave0[path].
+AEC_HD uint64_t sz_chunk_of_wave(const SzChunk *d, uint64_t n, int path, uint64_t w)
+{
+    uint64_t lo = 0, hi = n;            // invariant: d[lo].wave0 <= w < d[hi].wave0
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (d[mid].wave0[path] <= w) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+AEC_HD uint64_t sz_planar_to_chunk(const SzLayout &L, const SzChunk &D, uint64_t q)
+{
+    if (!L.word) return q;
+    uint64_t j, i;
+    sz_divmod(q, D.pixels, j, i);
+    return i * L.word + j;
+}
+
+AEC_HD uint64_t sz_take(const SzLayout &L, const SzChunk &D, uint64_t l)
+{
+    const uint64_t left = D.coded_bytes - l * L.line;
+    return left < L.line ? left : L.line;
+}
+
+// map 1: byte k of scan line l of the chunk's coder input -> byte of the caller's buffer, or kSzZero
+AEC_HD uint64_t sz_src_at(const SzLayout &L, const SzChunk &D, uint64_t l, uint64_t k, uint64_t take)
+{
+    if (k < take) return D.off + sz_planar_to_chunk(L, D, l * L.line + k);
+    if (!L.repeat) return kSzZero;
+    return D.off + sz_planar_to_chunk(L, D, l * L.line + take - L.pixel + (k & (L.pixel - 1u)));
+}
+
+// map 2: byte d of the chunk -> byte of the work buffer (the coder's output), or kSzZero
+AEC_HD uint64_t sz_dst_from(const SzLayout &L, const SzChunk &D, uint64_t d)
+{
+    if (d >= D.coded_bytes) return kSzZero;
+    uint64_t q = d;
+    if (L.word) {
+        const uint64_t i = L.word == 8 ? d >> 3 : d >> 2, j = d & (L.word - 1u);
+        q = j * D.pixels + i;
+    }
+    uint64_t l, k;
+    sz_divmod(q, L.line, l, k);
+    return D.work_off + l * L.padded_line + k;
+}
+
+// the cursor over the coder input of ONE chunk (c.chunk is not used: a lane never leaves its chunk)
+AEC_HD void sz_in_seek(const SzLayout &L, const SzChunk &D, uint64_t r, SzInCursor &c)    // r: byte of the chunk's coder input
+{
+    c.chunk = 0;
+    sz_divmod(r, L.padded_line, c.l, c.k);
+    c.take = sz_take(L, D, c.l);
+}
+
+AEC_HD uint8_t sz_in_byte(const SzLayout &L, const SzChunk &D, const uint8_t *src, const SzInCursor &c)
+{
+    const uint64_t s = sz_src_at(L, D, c.l, c.k, c.take);
+    return s == kSzZero ? (uint8_t)0 : src[s];
+}
+
+AEC_HD void sz_in_next(const SzLayout &L, const SzChunk &D, SzInCursor &c)
+{
+    if (++c.k < L.padded_line) return;
+    c.k = 0;
+    if (++c.l < D.lines) c.take = sz_take(L, D, c.l);       // (behind the last line: the end of the chunk's input)
+}
+
+AEC_HD uint64_t sz_in_straight(const SzLayout &L, const SzChunk &D, const SzInCursor &c)
+{
+    if (L.word || c.k + 16u > c.take) return kSzZero;
+    return D.off + c.l * L.line + c.k;
+}
+
+AEC_HD uint8_t sz_out_byte(const SzLayout &L, const SzChunk &D, const uint8_t *coder_out, uint64_t d)
+{
+    const uint64_t s = sz_dst_from(L, D, d);
+    return s == kSzZero ? (uint8_t)0 : coder_out[s];
+}
+
+AEC_HD uint64_t sz_out_straight(const SzLayout &L, const SzChunk &D, uint64_t d)
+{
+    if (L.word || d + 16u > D.coded_bytes) return kSzZero;
+    uint64_t l, k;
+    sz_divmod(d, L.line, l, k);
+    if (k + 16u > L.line) return kSzZero;
+    return D.work_off + l * L.padded_line + k;
+}
+
+// where the 4-byte piece of plane j that starts at pixel 4 m of the chunk lies in the work buffer
+AEC_HD uint64_t sz_piece_at(const SzLayout &L, const SzChunk &D, uint32_t j, uint64_t m)
+{
+    uint64_t l, k;
+    sz_divmod(j * D.pixels + 4u * m, L.line, l, k);
+    return D.work_off + l * L.padded_line + k;
+}
+
+// The descriptors of a batch: sizes, rooms, paths and the two wavefront prefixes; d[n] holds the totals.  base: the
+// caller's buffer (its low four bits decide alignment and heads); unmarshal: groups are cut on the destination.
+// false for a chunk without a whole pixel.
+inline bool sz_make_chunks(const SzLayout &L, uint64_t base, const uint64_t *offsets, const uint64_t *chunk_bytes, uint64_t n,
+                           bool unmarshal, SzChunk *d)
+{
+    uint64_t work = 0, waves[2] = {0, 0};
+    for (uint64_t i = 0; i < n; i++) {
+        SzChunk &D = d[i];
+        if (!sz_chunk_sizes(L, chunk_bytes[i], D)) return false;
+        D.off = offsets[i];
+        D.work_off = work;
+        const uint32_t low = (uint32_t)((base + D.off) & 15u);
+        D.planes = sz_chunk_planes_fast(L, D) && low == 0 ? 1u : 0u;
+        D.head = unmarshal ? low : 0u;
+        D.wave0[kSzBytes] = waves[kSzBytes];
+        D.wave0[kSzPlanes] = waves[kSzPlanes];
+        if (D.planes) waves[kSzPlanes] += sz_quad_waves(D);
+        else waves[kSzBytes] += unmarshal ? sz_group_waves(D.chunk_bytes, D.head) : sz_group_waves(D.coder_bytes, 0u);
+        work += (D.coder_bytes + 15u) & ~(uint64_t)15u;
+    }
+    d[n] = SzChunk{0, 0, work, 0, 0, 0, 0, {waves[kSzBytes], waves[kSzPlanes]}, 0u, 0u};
+    return true;
+}
+
 }  // namespace aec

@@ -20,6 +20,12 @@ class Layout(C.Structure):
                 ("coder_bytes", C.c_uint64), ("coded_bytes", C.c_uint64)]
 
 
+class ChunksPlan(C.Structure):
+    """aec_gpu_sz_chunks_plan_t"""
+    _fields_ = [("coder", gpu.Params), ("work_bytes", C.c_size_t), ("out_bound", C.c_size_t), ("rsi_entries", C.c_uint64),
+                ("workspace_bytes", C.c_size_t), ("direct", C.c_uint)]
+
+
 BATCH_CHUNK_DTYPE = np.dtype([("base_bits", "<u8"), ("bits", "<u8")])
 
 _bound = False
@@ -45,8 +51,41 @@ def _lib():
         lib.aec_gpu_sz_decompress_batch_async.argtypes = [vp, ps, vp, sz, vp, u64, sz, vp, vp, vp, vp, vp, vp]
         lib.aec_gpu_encode_batch_async.restype = C.c_int
         lib.aec_gpu_encode_batch_async.argtypes = [vp, C.POINTER(gpu.Params), vp, C.POINTER(u64), u64, vp, sz, vp, vp]
+        if hasattr(lib, "aec_gpu_sz_chunks_plan"):          # (AEC_AMD_LIB: a build from before the calls)
+            lib.aec_gpu_sz_chunks_plan.restype = C.c_int
+            lib.aec_gpu_sz_chunks_plan.argtypes = [ps, vp, u64, C.POINTER(ChunksPlan), vp]
+            lib.aec_gpu_sz_compress_chunks_async.restype = C.c_int
+            lib.aec_gpu_sz_compress_chunks_async.argtypes = [vp, ps, vp, vp, vp, u64, vp, vp, sz, vp, vp, vp, vp]
+            lib.aec_gpu_sz_decompress_chunks_async.restype = C.c_int
+            lib.aec_gpu_sz_decompress_chunks_async.argtypes = [vp, ps, vp, sz, vp, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp,
+                                                               vp, vp]
         _bound = True
     return lib
+
+
+def _u64(a):
+    """a host array of uint64 for a call (None stays None); the array must outlive the call, so it is returned"""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _host(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def chunks_plan(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline, sizes):
+    """aec_gpu_sz_chunks_plan (host arithmetic, no device needed) for chunks of `sizes` bytes under one SZ_com_t.  Returns
+    the dict {coder, work_bytes, out_bound, rsi_entries, workspace_bytes, direct, work_offsets}, or None where the batch
+    would be refused."""
+    lib = _lib()
+    p = SZ_com_t(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline)
+    sizes = _u64(sizes)
+    offs = np.zeros(max(1, sizes.size), dtype=np.uint64)
+    plan = ChunksPlan()
+    if not lib.aec_gpu_sz_chunks_plan(C.byref(p), _host(sizes), sizes.size, C.byref(plan), _host(offs)):
+        return None
+    return dict(coder=(plan.coder.bits_per_sample, plan.coder.block_size, plan.coder.rsi, plan.coder.flags),
+                work_bytes=int(plan.work_bytes), out_bound=int(plan.out_bound), rsi_entries=int(plan.rsi_entries),
+                workspace_bytes=int(plan.workspace_bytes), direct=int(plan.direct), work_offsets=offs[:sizes.size])
 
 
 def layout(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline, chunk_bytes):
@@ -154,6 +193,87 @@ class SzCodec:
             if rc != 0:
                 return rc
         return 0
+
+    # ---- chunks of any size, one call (aec_gpu_sz_*_chunks_async) ---------------------------------
+    def chunks_plan(self, sizes):
+        s = self.sz
+        return chunks_plan(s.options_mask, s.bits_per_pixel, s.pixels_per_block, s.pixels_per_scanline, sizes)
+
+    def compress_chunks_async(self, d_src, src_offsets, sizes, d_work, d_out, out_cap, d_chunks, d_table, d_result, stream=None):
+        """src_offsets / sizes: uint64 arrays on the host; d_work: the plan's work_bytes, 16-byte aligned (None when the
+        chunks are coded where they lie); d_chunks: n * 16 bytes (BATCH_CHUNK_DTYPE); d_table: int64 tensor of the plan's
+        rsi_entries, or None; d_result: 24 bytes.  Returns the call's return code."""
+        offs, sizes = _u64(src_offsets), _u64(sizes)
+        return self.lib.aec_gpu_sz_compress_chunks_async(self.ctx, C.byref(self.sz), _ptr(d_src), _host(offs), _host(sizes),
+                                                         sizes.size, _ptr(d_work), _ptr(d_out), out_cap, _ptr(d_chunks),
+                                                         _ptr(d_table), _ptr(d_result), self._stream(stream))
+
+    def decompress_chunks_async(self, d_in, in_bytes, in_offsets, in_sizes, dst_offsets, sizes, d_table, have_table, d_work,
+                                d_dst, d_results, d_result, stream=None):
+        """in_offsets / in_sizes (None with a table), dst_offsets, sizes: uint64 arrays on the host; d_table: int64 tensor
+        of the plan's rsi_entries; d_results: n * 40 bytes, d_result: 40 bytes.  Returns the call's return code."""
+        ino, ins, dso, sizes = _u64(in_offsets), _u64(in_sizes), _u64(dst_offsets), _u64(sizes)
+        return self.lib.aec_gpu_sz_decompress_chunks_async(self.ctx, C.byref(self.sz), _ptr(d_in), in_bytes, _host(ino),
+                                                           _host(ins), _host(dso), _host(sizes), sizes.size, _ptr(d_table),
+                                                           int(bool(have_table)), _ptr(d_work), _ptr(d_dst), _ptr(d_results),
+                                                           _ptr(d_result), self._stream(stream))
+
+    def held_bytes(self):
+        self.lib.aec_gpu_held_bytes.restype = C.c_size_t
+        self.lib.aec_gpu_held_bytes.argtypes = [C.c_void_p]
+        return int(self.lib.aec_gpu_held_bytes(self.ctx))
+
+    def trim(self, keep_bytes=0):
+        self.lib.aec_gpu_trim.restype = None
+        self.lib.aec_gpu_trim.argtypes = [C.c_void_p, C.c_size_t]
+        self.lib.aec_gpu_trim(self.ctx, keep_bytes)
+
+    def compress_chunks(self, d_src, src_offsets, sizes, want_table=False):
+        """chunks of sizes[i] bytes at d_src[src_offsets[i]:] -> (d_out, records, d_table, d_work): stream i is
+        d_out[records[i]["base_bits"] // 8 :][: (records[i]["bits"] + 7) // 8], what SZ_BufftoBuffCompress gives for
+        chunk i; d_table the int64 RSI table for decompress_chunks (None unless want_table); buffers come from the plan"""
+        torch = self.torch
+        plan = self.chunks_plan(sizes)
+        if plan is None:
+            raise ValueError("not a batch for one call (aec_gpu_sz_chunks_plan)")
+        n = len(sizes)
+        dev = d_src.device
+        d_out = torch.empty(plan["out_bound"], dtype=torch.uint8, device=dev)
+        d_work = torch.empty(plan["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_rec = torch.zeros(max(1, n) * 2, dtype=torch.int64, device=dev)
+        d_res = torch.zeros(gpu.ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_table = torch.zeros(max(1, plan["rsi_entries"]), dtype=torch.int64, device=dev) if want_table else None
+        rc = self.compress_chunks_async(d_src, src_offsets, sizes, d_work, d_out, d_out.numel(), d_rec, d_table, d_res)
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_sz_compress_chunks_async failed ({rc})")
+        if n and d_res.cpu().numpy().view(gpu.ENC_RESULT_DTYPE)[0]["overflow"]:
+            raise RuntimeError("encode overflow")
+        return d_out, d_rec.cpu().numpy().view(np.uint64).view(BATCH_CHUNK_DTYPE)[:n], d_table, d_work
+
+    def decompress_chunks(self, d_in, in_bytes, sizes, d_table=None, in_offsets=None, in_sizes=None):
+        """streams -> (d_dst with the chunks back to back, per-chunk records, overall record).  With d_table (of
+        compress_chunks(..., want_table=True), positions relative to d_in) no index pass runs; without it the streams are
+        in_sizes[i] bytes at d_in[in_offsets[i]:]."""
+        torch = self.torch
+        plan = self.chunks_plan(sizes)
+        if plan is None:
+            raise ValueError("not a batch for one call (aec_gpu_sz_chunks_plan)")
+        n = len(sizes)
+        dev = d_in.device
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.uint64))]).astype(np.uint64)
+        d_dst = torch.empty(int(dst_offsets[-1]), dtype=torch.uint8, device=dev)
+        d_work = torch.empty(plan["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        have = d_table is not None
+        if not have:
+            d_table = torch.zeros(max(1, plan["rsi_entries"]), dtype=torch.int64, device=dev)
+        d_results = torch.zeros(max(1, n) * gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_result = torch.zeros(gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        rc = self.decompress_chunks_async(d_in, in_bytes, in_offsets, in_sizes, dst_offsets[:n], sizes, d_table, have, d_work,
+                                          d_dst, d_results, d_result)
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_sz_decompress_chunks_async failed ({rc})")
+        return (d_dst, d_results.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[:n],
+                d_result.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[0])
 
     # ---- convenience (synchronising) -------------------------------------------------------------
     def compress_batch(self, d_src, chunk_bytes, n_chunks):
