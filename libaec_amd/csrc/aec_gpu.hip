@@ -43,7 +43,6 @@ struct aec_gpu_ctx {
 
     // Device memory, grown on demand (aec_devbuf.h: replace) and kept between calls:
     DevBuf ws;             // workspace of the two-pass encoder (plan / emit: per-block summaries, segment scan)
-    DevBuf fused;          // control block of the single-pass encoder (ticket, fail flag, look-back granules)
     DevBuf idx_ws;         // speculative index tables (aec_idx.hip)
     DevBuf dec_ws;         // workspace of the segment-wise decode of bare streams (aec_dec.hip: launch_decode_bare)
     DevBuf range_ws;       // whole blocks of a range decode whose window does not start on an RSI / end on a block
@@ -52,7 +51,7 @@ struct aec_gpu_ctx {
                            // the coder call in between (that call re-sends into chunks_d and may free it to grow it)
     // ... of which aec_gpu_held_bytes counts, aec_gpu_trim frees and aec_gpu_destroy releases these: a new one goes here
     // (pointers into the context itself, which is never copied)
-    DevBuf *const held[7] = {&ws, &fused, &idx_ws, &dec_ws, &range_ws, &chunks_d, &sz_d};
+    DevBuf *const held[6] = {&ws, &idx_ws, &dec_ws, &range_ws, &chunks_d, &sz_d};
     DevBuf carry;          // device record: what precedes this context's shard (emit_planned); a ShardCarry, never trimmed
     // the pinned buffers the chunk calls write their descriptors to -- kChunkStages, taken in turn, each guarded by the
     // event of its last transfer (stage_descriptors / send_descriptors); never trimmed
@@ -152,16 +151,6 @@ static int reserve_two_pass(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws, bo
     return RC_OK;
 }
 
-// ... and the control block of the single-pass encoder (16 bytes per 4..16 segments)
-static int reserve_fused(aec_gpu_ctx *ctx, const Cfg &c, EncWorkspace *ws)
-{
-    const size_t need = fused_ctl_bytes(c);
-    if (!ctx->fused.replace(need, need + need / 16)) return RC_MEM_ERROR;
-    *ws = EncWorkspace{};
-    ws->fused_ctl = ctx->fused.p;
-    return RC_OK;
-}
-
 // the one condition every enqueueing call closes on: no launch of this call has failed
 static int launched() { return hipGetLastError() == hipSuccess ? RC_OK : RC_MEM_ERROR; }
 
@@ -181,7 +170,7 @@ int aec_gpu_reserve(aec_gpu_ctx *ctx, const aec_gpu_params *p, size_t in_bytes)
     // what aec_gpu_encode_async needs; the (much larger) workspace of the plan / emit pair is
     // allocated by the first plan call
     EncWorkspace ws;
-    return fused_supported(c) ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws, true);
+    return reserve_two_pass(ctx, c, &ws, true);
 }
 
 static int encode_phases(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
@@ -195,9 +184,8 @@ static int encode_phases(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *
     if (start_bit > 7 || k_in > 31) return RC_CONF_ERROR;
     if ((phases & ENC_EMIT) && ((reinterpret_cast<uintptr_t>(d_out) & 15u) || (out_cap & 15u) || out_cap < 16))
         return RC_CONF_ERROR;
-    const bool fused = phases == ENC_ALL && !d_carry && fused_supported(c);
     EncWorkspace ws;
-    rc = fused ? reserve_fused(ctx, c, &ws) : reserve_two_pass(ctx, c, &ws, phases == ENC_ALL && !d_carry);
+    rc = reserve_two_pass(ctx, c, &ws, phases == ENC_ALL && !d_carry);
     if (rc != RC_OK) return rc;
     (void)hipGetLastError();   // only launch errors of THIS call are reported below
     launch_encode(c, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), out_cap, start_bit,

@@ -59,6 +59,16 @@ def values(kind, n, prm, rng, spw=1):
         for at in rng.integers(0, n, max(1, n // 600)):
             step[at:at + int(rng.integers(1, 3 * bs * 8))] = 0               # constant stretches: zero blocks and runs
         return np.clip(mid + np.cumsum(step), lo, hi)
+    if kind == "islands":
+        # zeros with short busy stretches between stretches of zero blocks of every length up to 40 segments: wavefronts
+        # of a few bits each, several of them in one word of the stream (reaches_edge)
+        v, seg, pos = np.zeros(n, dtype=np.int64), 64 * bs, 0
+        while pos < n:
+            pos += int(rng.integers(1, 40 * seg))
+            b = int(rng.integers(1, 3 * bs))
+            v[pos:pos + b] = rng.integers(0, 1 << min(bps - 1, 9), size=len(v[pos:pos + b]))
+            pos += b
+        return v
     assert kind in ("plateau", "late")
     # mid + {0, 1} everywhere; the first block of every wavefront is a ramp of +1 per sample (every mapped residual 2: the
     # plateau [0, 2]); the block in front of it mid + {0, 1} (carries k = 0) for odd wavefronts and
@@ -80,12 +90,17 @@ def values(kind, n, prm, rng, spw=1):
     return v
 
 
+def segment_blocks(prm, nblk):
+    """the first block of every segment"""
+    rsi = prm[2]
+    return [r + s for r in range(0, nblk, rsi) for s in range(0, min(rsi, nblk - r), 64)]
+
+
 def segment_table(data, prm, trace):
     """start bit and the raw sample in front of every segment, from the oracle's per-block trace"""
     bps, bs, rsi, flags = prm
     nb = bytes_per_sample(bps, flags)
-    nblk = len(trace)
-    first = [r + s for r in range(0, nblk, rsi) for s in range(0, min(rsi, nblk - r), 64)]
+    first = segment_blocks(prm, len(trace))
     start = np.concatenate([[0], np.cumsum(trace["bits"].astype(np.uint64))])[first]
     prev = []
     nsamp = data.size // nb
@@ -97,6 +112,20 @@ def segment_table(data, prm, trace):
         raw = data[i * nb:(i + 1) * nb]
         prev.append(int.from_bytes(raw.tobytes(), "big" if flags & MSB else "little"))
     return start, np.array(prev, dtype=np.uint64)
+
+
+def reaches_edge(prm, spw, trace, bits):
+    """What "islands" is for, read off the oracle's per-block trace.  Wavefronts of one segment: a 32-bit word of the
+    stream holds bits of three or more of them.  Longer ones: a word is shared by two wavefronts of zero blocks only."""
+    first = segment_blocks(prm, len(trace))[::spw]               # the first block of every wavefront
+    ends = np.concatenate([[0], np.cumsum(trace["bits"].astype(np.int64))])
+    ws = np.append(ends[first], np.int64(bits))                  # its first bit, and the end of the stream
+    if spw == 1:
+        # wavefronts w, w + 1, w + 2: the last bit of w and the first of w + 2 lie in one word
+        return bool(np.any((ws[1:-2] - 1) >> 5 == ws[2:-1] >> 5))
+    zero = np.isin(trace["option"], (OPT_ZERO, OPT_ZERO_CONT))
+    only = np.array([zero[a:b].all() for a, b in zip(first, first[1:] + [len(trace)])])
+    return bool(np.any(only[:-1] & only[1:] & (ws[1:-1] & 31 != 0)))
 
 
 class Device:
@@ -125,11 +154,13 @@ class Device:
         return d_out.cpu().numpy(), d_off.cpu().numpy().astype(np.uint64), res, d_tab.cpu().numpy().view(gpu.SEG_ENTRY_DTYPE)
 
 
-def check(dev, data, prm, what, fill=None):
-    """one input through the device encoder with the route on, against the oracle and the three-kernel route"""
+def check(dev, data, prm, what, fill=None, edge_spw=None):
+    """one input through the device encoder with the route on, against the oracle and the three-kernel route
+    (edge_spw: the input must reach the edge of wavefronts of that many segments, reaches_edge)"""
     data = np.ascontiguousarray(data, dtype=np.uint8)
     rc, want, trace, offs, bits = oracle_encode(data, *prm, want_trace=True)
     assert rc == 0, what
+    assert edge_spw is None or reaches_edge(prm, edge_spw, trace, bits), (what, "does not reach its edge")
     out, off, res, tab = dev.encode(data, prm, fill=fill)
     nbytes = (bits + 7) // 8
     assert not int(res["overflow"]) and int(res["total_bits"]) == bits, (what, int(res["total_bits"]), bits)
@@ -160,16 +191,25 @@ def inputs(prm, spw, kinds, rng):
         for kind in kinds:
             v = values(kind, blocks * bs + (extra + nb - 1) // nb, prm, rng, spw)
             data = pack_samples(v, bps, flags)[:blocks * bs * nb + extra]
-            yield f"{prm} spw {spw} {name} {kind}", data
+            yield f"{prm} spw {spw} {name} {kind}", data, (name, kind)
+
+
+def sweep_inputs(spw):
+    """(shape, segments per wavefront, name, input, its size and kind) of sweep()"""
+    rng = np.random.default_rng(1210 + spw)
+    for prm in DIRECT + [ONE_BLOCK_RSI, NOT_DIRECT]:
+        # (the shape that keeps the analyze / scan / pack kernels: wavefronts of one segment, which keeps it small)
+        w = 1 if prm == NOT_DIRECT else spw
+        for what, data, tag in inputs(prm, w, ("walk", "zero", "constant", "noise", "islands"), rng):
+            yield prm, w, what, data, tag
 
 
 def sweep(spw):
-    dev, rng, n = Device(), np.random.default_rng(1210 + spw), 0
-    for prm in DIRECT + [ONE_BLOCK_RSI, NOT_DIRECT]:
-        # (the shape that keeps the analyze / scan / pack kernels: wavefronts of one segment, which keeps it small)
-        for what, data in inputs(prm, 1 if prm == NOT_DIRECT else spw, ("walk", "zero", "constant", "noise"), rng):
-            check(dev, data, prm, what)
-            n += 1
+    dev, n = Device(), 0
+    for prm, w, what, data, tag in sweep_inputs(spw):
+        # the largest input of "islands" is the one that has to reach the edge of its wavefronts, for every shape
+        check(dev, data, prm, what, edge_spw=w if tag == ("33 wavefronts", "islands") else None)
+        n += 1
     return n
 
 

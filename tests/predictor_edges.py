@@ -14,9 +14,9 @@ off-by-one in one of the comparisons shows only on data that sits on the edge.  
     vector sits on each of them, and required(): which counts a family must reach (tests/test_predictor_edges.py);
   * gpu_check(): every encoder and decoder path of the library on one vector, against the oracle's bytes and the
     reference's hash (tests/golden/predictor_edges.json); main() runs it over every case with the library AEC_AMD_LIB
-    names (tests/test_gpu_predictor_edges.py runs it on the tuning build with AEC_ENC_FUSED=1):
+    names (tests/test_gpu_encode_local.py runs it on the tuning build with AEC_ENC_LOCAL=1):
 
-    AEC_AMD_LIB=libaec_amd/lib/tuning/libaec.so.0 AEC_ENC_FUSED=1 python tests/predictor_edges.py
+    AEC_AMD_LIB=libaec_amd/lib/tuning/libaec.so.0 AEC_ENC_LOCAL=1 python tests/predictor_edges.py
 """
 import hashlib
 import json
@@ -784,8 +784,7 @@ def main():
             paths[p] = paths.get(p, 0) + 1
         n += 1
     print("paths:", paths)
-    print("predictor edges ok:", n, "cases; AEC_AMD_LIB=%s AEC_ENC_FUSED=%s" % (
-        os.environ.get("AEC_AMD_LIB"), os.environ.get("AEC_ENC_FUSED")))
+    print("predictor edges ok:", n, "cases; AEC_AMD_LIB=%s" % os.environ.get("AEC_AMD_LIB"))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Registers, LDS, scratch and occupancy of the decode kernels and of k_index in two source trees, instantiation by
-instantiation: the compiler remarks libaec_amd/csrc/resusage.sh prints (-Rpass-analysis=kernel-resource-usage), with the
+"""Registers, LDS, scratch and occupancy of the decode kernels, of k_index and of the encoder's kernels in two source
+trees, instantiation by instantiation: the compiler remarks libaec_amd/csrc/resusage.sh prints (-Rpass-analysis=kernel-resource-usage), with the
 template arguments kept -- resusage.sh folds them -- so that every existing instantiation can be found again in a tree
 that adds a template flag.
     python tests/resusage_compare.py <parent tree>/libaec_amd/csrc <this tree>/libaec_amd/csrc
@@ -15,7 +15,9 @@ from concurrent.futures import ThreadPoolExecutor
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 UNITS = [("aec_dec.hip (no part)", "aec_dec.hip", [])] + \
         [(f"aec_dec.hip -DAEC_DEC_PART={p}", "aec_dec.hip", [f"-DAEC_DEC_PART={p}"]) for p in (0, 8, 16, 32, 64)] + \
-        [("aec_idx.hip (k_index)", "aec_idx.hip", [])]
+        [("aec_idx.hip (k_index)", "aec_idx.hip", [])] + \
+        [("aec_enc.hip (no part)", "aec_enc.hip", [])] + \
+        [(f"aec_enc.hip -DAEC_ENC_PART={p}", "aec_enc.hip", [f"-DAEC_ENC_PART={p}"]) for p in (0, 8, 16, 32, 64)]
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
 FLAG_AT = {"k_decode": 7, "k_decode_wave": 4, "k_decode_redo": 3}
 

@@ -20,7 +20,7 @@ from test_gpu_decode_chunks import NONE, expected, make_chunk  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 WIDE = (16, 16, 64, PP)
-TINY = (8, 8, 1, PP)              # a few bytes per chunk: the single-pass encoder's control block is what encode() grows
+TINY = (8, 8, 1, PP)              # a few bytes per chunk
 
 
 def bind(lib):

@@ -17,7 +17,7 @@ TUNING = os.path.join(ROOT, "libaec_amd", "lib", "tuning", "libaec.so.0")
 
 def child(args, env=None, tuning=True):
     e = dict(os.environ)
-    for name in ("AEC_ENC_LOCAL", "AEC_ENC_LOCAL_SPW", "AEC_ENC_LOCAL_GUESS", "AEC_ENC_FUSED", "AEC_AMD_LIB"):
+    for name in ("AEC_ENC_LOCAL", "AEC_ENC_LOCAL_SPW", "AEC_ENC_LOCAL_GUESS", "AEC_AMD_LIB"):
         e.pop(name, None)
     if tuning:
         assert os.path.exists(TUNING)
@@ -31,8 +31,9 @@ def child(args, env=None, tuning=True):
 
 @pytest.mark.parametrize("spw", [1, 8])
 def test_sizes_and_data(spw):
-    """one block to 33 wavefronts of random walk, zeros, a constant and noise, for the three shapes that take the route,
-    RSIs of one block, and a shape that keeps the old kernels"""
+    """one block to 33 wavefronts of random walk, zeros, a constant, noise and islands in zeros (several wavefronts in
+    one word of the stream), for the three shapes that take the route, RSIs of one block, and a shape that keeps the
+    old kernels"""
     assert "encode local ok: sweep" in child(["enc_local_cases.py", "sweep", str(spw)])
 
 

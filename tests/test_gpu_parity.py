@@ -653,23 +653,14 @@ def test_truncated_streams_release_what_arrived(api):
             assert bytes(got) == dec_o, (it, bps, bs, rsi, flags, n, cut, first, len(got), len(dec_o))
 
 
-@pytest.mark.parametrize("env", [{"AEC_ENC_FUSED": "1"}, {"AEC_ENC_FUSED": "1", "AEC_FUSED_SEGS": "1"},
-                                 {"AEC_ENC_FUSED": "1", "AEC_FUSED_SEGS": "2", "AEC_FUSED_PARTS": "3"},
-                                 {"AEC_ENC_FUSED": "1", "AEC_FUSED_SEGS": "4", "AEC_FUSED_PARTS": "1"}, {}])
-def test_fused_encoder_edges(env):
-    """tests/fused_edges.py (streams of zero-block runs whose waves / partitions begin and end inside
-    one word, every partition fill, ragged ends) under several geometries of the single-pass encoder
-    (opt-in: AEC_ENC_FUSED=1) and once through the default two-pass kernels."""
+def test_encoder_edges():
+    """tests/encoder_edges.py (streams of zero-block runs whose waves begin and end inside one word, ragged ends,
+    every container size) through the shipped library."""
     import subprocess
     import sys
-    e = dict(os.environ)
-    e.update(env)
-    if env:     # the variant knobs exist in the tuning build only (libaec_amd/csrc/aec_tune.h)
-        e["AEC_AMD_LIB"] = os.path.join(ROOT, "libaec_amd", "lib", "tuning", "libaec.so.0")
-        assert os.path.exists(e["AEC_AMD_LIB"])
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fused_edges.py")], env=e, capture_output=True,
-                         text=True, timeout=900)
-    assert out.returncode == 0 and "fused edges ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "encoder_edges.py")], env=dict(os.environ),
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and "encoder edges ok: 360 cases" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
 
 
 def test_every_index_scheme_on_the_same_streams():

@@ -4,14 +4,9 @@ the wave kernel and on the generic kernel, the segment decode, the bare decode b
 cut inside the clipping blocks).  Expected bytes are the oracle's, pinned to the reference by the hashes in
 tests/golden/predictor_edges.json; tests/test_predictor_edges.py checks on the CPU that every vector reaches the
 conditions it is meant for."""
-import os
-import subprocess
-import sys
-
 import pytest
 
 import predictor_edges as E
-from helpers import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -69,15 +64,3 @@ def test_every_pair(cfg):
 def test_every_block_clips(cfg):
     """260 and more consecutive blocks with a clipping step each: the wave kernel corrects lane after lane"""
     assert "encode" in E.gpu_check("every_block_clips", cfg)
-
-
-def test_predictor_edges_fused_encoder():
-    """tests/predictor_edges.py once more with the single-pass encoder (AEC_ENC_FUSED=1, tuning build): it shares the
-    segment feeder, and with it the shortcuts, with the two-pass kernels"""
-    e = dict(os.environ)
-    e["AEC_ENC_FUSED"] = "1"
-    e["AEC_AMD_LIB"] = os.path.join(ROOT, "libaec_amd", "lib", "tuning", "libaec.so.0")
-    assert os.path.exists(e["AEC_AMD_LIB"])
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "predictor_edges.py")], env=e, capture_output=True,
-                         text=True, timeout=900)
-    assert out.returncode == 0 and "predictor edges ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
