@@ -107,10 +107,19 @@ __device__ __forceinline__ uint32_t wave_incl_sum_dpp(uint32_t v)
 // The predictor (reference decode.c:91-135): x += d / 2 or x -= (d + 1) / 2 as long as the step's size fits the room on
 // both sides of x, something else where it does not.  Every sample of a block takes the first branch if the SUM of the
 // block's mapped residuals fits the room on both sides of the sample in front of the block (a step is at most its
-// residual, and x moves by at most the steps taken so far): one test per block, wave-wide, and then a sample is a
-// shift, a sign, an exclusive or and an add (4.5 vector instructions with the sum, against 13 for the exact step; the
-// predictor was a third of the kernel's 39 instructions per sample, profiles/r06/k_decode_isa.txt).  A wavefront with
-// a lane whose block does not pass -- samples near the ends of the range -- takes the exact steps for that block.
+// residual, and x moves by at most the steps taken so far) -- GIVEN that this sample lies inside [xmin, xmax]: one test
+// per block, wave-wide, and then a sample is a shift, a sign, an exclusive or and an add (4.5 vector instructions with
+// the sum, against 13 for the exact step; the predictor was a third of the kernel's 39 instructions per sample,
+// profiles/r06/k_decode_isa.txt).  A wavefront with a lane whose block does not pass -- samples near the ends of the
+// range -- takes the exact steps for that block.
+// The state x is the reference's last_out, 32 bits wide: a residual above xmax (no encoder of the reference writes one,
+// a foreign or damaged stream may) takes it outside the range, and there one of the two rooms, x0 - xmin or xmax - x0,
+// wraps to almost 2^32 and says nothing.  The two add up to xmax - xmin modulo 2^32, and x0 lies inside exactly when
+// x0 - xmin <= xmax - xmin: so the room above is taken as (xmax - xmin) - (x0 - xmin) with a subtraction that saturates
+// at 0 -- the instruction count of the plain one -- and a block behind a state outside takes the exact steps, which are
+// the reference's whatever the state (tests/foreign_predictor.py).  This also makes a lane's samples the same on both
+// paths, which the lane-by-lane correction of k_decode_wave needs in order to end: a block whose result depended on
+// what the OTHER lanes' tests said sent it round for ever.
 template <int BS, int BYTES>
 __device__ __forceinline__ void store_block(uint8_t *dst, const uint32_t *d, const Cfg &c, bool ref,
                                             uint32_t &x)
@@ -128,12 +137,15 @@ __device__ __forceinline__ void store_block(uint8_t *dst, const uint32_t *d, con
 #pragma unroll
         for (int i = 1; i + 1 < BS; i += 2) sum += d[i] + d[i + 1];
         if (BS % 2 == 0) sum += d[BS - 1];
-        if (BYTES == 4) {                          // (the sum of 64 residuals of up to 32 bits: none above 26 bits)
+        if (BYTES >= 3) {                          // (the sum of 64 residuals of up to 32 bits: none above 26 bits; split
+                                                   // options of these widths name a k of up to 29, also for 24-bit samples)
 #pragma unroll
             for (int i = 0; i < BS; i++) any |= i == 0 ? d0 : d[i];
         }
-        const uint32_t below = sgn ? x0 + c.xmax + 1u : x0, above = c.xmax - x0;      // x0 - xmin, xmax - x0
-        const bool fits = sum <= below && sum <= above && (BYTES != 4 || (any >> 26) == 0u);
+        // x0 - xmin, and xmax - x0 as (xmax - xmin) - (x0 - xmin), saturating: 0 for a state outside the range, behind
+        // which only a block of zeros -- sum 0, no step at all -- is taken for a running sum
+        const uint32_t below = sgn ? x0 + c.xmax + 1u : x0, above = __builtin_elementwise_sub_sat(c.xmax - c.xmin, below);
+        const bool fits = sum <= below && sum <= above && (BYTES < 3 || (any >> 26) == 0u);
         if (!__any(!fits)) {
             uint32_t xx = x0;
 #pragma unroll

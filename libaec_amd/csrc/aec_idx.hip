@@ -2123,6 +2123,13 @@ __global__ void k_spec_verify(const Cfg c, const TrStream s, const SparseTables 
 // true RSI start among them; empty on well-behaved streams).  Without it every such RSI costs the walker a serial
 // walk AND the chunk-level lookup of its 256 windows: 1 in 1000 RSIs of this kind doubled the index time.
 // (16 bytes per memory round trip instead of 4: the parse below waits for nothing else)
+// (the plain form: a word per round trip, nothing held)
+struct WordFetch {
+    const uint32_t *words;
+    uint64_t nwords;
+    __device__ uint32_t operator()(uint64_t idx) const { return idx < nwords ? bswap32(words[idx]) : 0u; }
+};
+
 struct QuadFetch {
     const uint32_t *words;
     uint64_t nwords;
@@ -2848,6 +2855,24 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
                 if (coop) load_regs(good >> 5);
                 br.init(LdsWindowFetch{win, base}, end_bit, good);
                 st = skip_cds(br, c, ref, b, nblk);
+            }
+            // (longer than a whole window, which still ends in front of the end of the stream -- the format knows no
+            // bound: two residuals of 2^31 at k = 13 are 524 000 bits: read from the stream where it lies, a word per
+            // round trip -- no buffer of its own, the kernel keeps its registers -- and the window filled again behind it.
+            // Worst case: a damaged stream with a zeroed stretch is one fundamental sequence to the end of the stretch, as
+            // it is for the reference, and costs one dependent global load per 32 bits of it, serial; an input that ends
+            // inside is "input ended" at the start of the coded data set)
+            if (st == DEC_NEED_INPUT && (base + kIdxWindowWords) * 32u < end_bit) {
+                BitReaderT<WordFetch> far;
+                far.init(WordFetch{words, nwords}, end_bit, good);
+                st = skip_cds(far, c, ref, b, nblk);
+                if (st == DEC_OK) {
+                    good = far.pos;
+                    __syncthreads();
+                    refill(good >> 5);
+                    if (coop) load_regs(good >> 5);
+                    br.init(LdsWindowFetch{win, base}, end_bit, good);
+                }
             }
             if (st != DEC_OK) {
                 status = st;

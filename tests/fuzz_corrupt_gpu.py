@@ -4,7 +4,11 @@ streams.  Nothing may hang or fault; where the oracle (= the reference's behavio
 without an error, the product must give the same bytes, and where it reports AEC_DATA_ERROR the product may not
 report success with different bytes.
 
-    python tests/fuzz_corrupt_gpu.py [--cases 150] [--seed 1]
+    python tests/fuzz_corrupt_gpu.py [--cases 150] [--seed 1] [--containers]
+
+--containers draws the sample widths the plain sweep never meets -- 5, 12, 20, 24 in 3-byte containers, 31 -- with
+AEC_DATA_MSB and AEC_DATA_SIGNED at random and at most 40 000 samples.  Without it every draw of every seed is what it
+was before the switch existed (tests/test_foreign_predictor.py holds the first ten cases of seed 13).
 """
 import argparse
 import os
@@ -15,29 +19,43 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from helpers import (AEC_DATA_ERROR, AEC_DATA_PREPROCESS, AEC_OK, bytes_per_sample, have_ref, oracle_decode,  # noqa: E402
-                     oracle_encode, pack_samples, random_walk_samples, ref_decode)
+from helpers import (AEC_DATA_3BYTE, AEC_DATA_ERROR, AEC_DATA_MSB, AEC_DATA_PREPROCESS, AEC_DATA_SIGNED, AEC_OK,  # noqa: E402
+                     bytes_per_sample, have_ref, oracle_decode, oracle_encode, pack_samples, random_walk_samples, ref_decode)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=150)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--containers", action="store_true", help="bps 5, 12, 20, 24 (3 bytes), 31; MSB and signed at random")
     return run(ap.parse_args())
 
 
-def run(args):
-    import torch  # noqa: F401
-    from libaec_amd import api
+def run(args, decode=None):
+    """decode: what stands in for the library's aec_buffer_decode (the CPU test of the draws); None: the library's"""
+    if decode is None:
+        import torch  # noqa: F401
+        from libaec_amd import api
+        decode = api.aec_buffer_decode
+    containers = getattr(args, "containers", False)
     rng = np.random.default_rng(args.seed)
     bad = 0
     for case in range(args.cases):
-        bps = int(rng.choice([8, 16, 16, 32]))
-        bs = int(rng.choice([8, 16, 32, 64]))
-        rsi = int(rng.choice([1, 16, 128, 1024]))
-        flags = AEC_DATA_PREPROCESS
+        if containers:
+            bps = int(rng.choice([5, 12, 20, 24, 31]))
+            bs = int(rng.choice([8, 16, 32, 64]))
+            rsi = int(rng.choice([1, 16, 128, 1024]))
+            flags = AEC_DATA_PREPROCESS | (AEC_DATA_3BYTE if bps == 24 else 0)
+            flags |= AEC_DATA_MSB if rng.random() < 0.5 else 0
+            flags |= AEC_DATA_SIGNED if rng.random() < 0.5 else 0
+            n = int(rng.choice([2000, 40000]))
+        else:
+            bps = int(rng.choice([8, 16, 16, 32]))
+            bs = int(rng.choice([8, 16, 32, 64]))
+            rsi = int(rng.choice([1, 16, 128, 1024]))
+            flags = AEC_DATA_PREPROCESS
+            n = int(rng.choice([2000, 40000, 300000, 2000000]))
         nb = bytes_per_sample(bps, flags)
-        n = int(rng.choice([2000, 40000, 300000, 2000000]))
         vals = random_walk_samples(rng, n, bps, flags, scale=float(rng.choice([0.5, 3.0, 50.0])), zero_frac=0.2, jump_frac=0.002)
         data = pack_samples(vals, bps, flags)
         rc, enc, *_ = oracle_encode(data, bps, bs, rsi, flags)
@@ -51,10 +69,10 @@ def run(args):
             enc = bytes(enc) + bytes(rng.integers(0, 256, int(rng.integers(1, 300)), dtype=np.uint8).tolist())
             rc_o, dec_o = ref_decode(enc, bps, bs, rsi, flags, out_size) if have_ref() else \
                 oracle_decode(enc, bps, bs, rsi, flags, out_size)[:2]
-            rc_p, dec_p = api.aec_buffer_decode(enc, bps, bs, rsi, flags, out_size)
+            rc_p, dec_p = decode(enc, bps, bs, rsi, flags, out_size)
             if (rc_p, dec_p) != (rc_o, dec_o):
                 bad += 1
-                print(f"case {case}: bps {bps} bs {bs} rsi {rsi} n {n} kind 3 (tail of {len(enc)} bytes): reference rc {rc_o} "
+                print(f"case {case}: bps {bps} bs {bs} rsi {rsi} flags {flags} n {n} kind 3 (tail of {len(enc)} bytes): reference rc {rc_o} "
                       f"{len(dec_o)} bytes, product rc {rc_p} {len(dec_p)} bytes, equal {dec_p == dec_o}", flush=True)
             continue
         if kind == 0:                                   # bit flips
@@ -69,7 +87,7 @@ def run(args):
             enc[o:o + ln] = bytes(rng.integers(0, 256, min(ln, len(enc) - o), dtype=np.uint8).tolist())
         enc = bytes(enc)
         rc_o, dec_o, _ = oracle_decode(enc, bps, bs, rsi, flags, out_size)
-        rc_p, dec_p = api.aec_buffer_decode(enc, bps, bs, rsi, flags, out_size)
+        rc_p, dec_p = decode(enc, bps, bs, rsi, flags, out_size)
         ok = rc_p in (AEC_OK, AEC_DATA_ERROR)
         if ok and rc_o == AEC_OK:
             ok = rc_p == AEC_OK and dec_p == dec_o
@@ -86,7 +104,7 @@ def run(args):
                     print(f"case {case}: oracle rc {rc_o}, reference with this room rc {rc_r} {len(dec_r)} bytes = product", flush=True)
         if not ok:
             bad += 1
-            print(f"case {case}: bps {bps} bs {bs} rsi {rsi} n {n} kind {kind}: oracle rc {rc_o} {len(dec_o)} bytes, "
+            print(f"case {case}: bps {bps} bs {bs} rsi {rsi} flags {flags} n {n} kind {kind}: oracle rc {rc_o} {len(dec_o)} bytes, "
                   f"product rc {rc_p} {len(dec_p)} bytes, equal {dec_p == dec_o}", flush=True)
     print("mismatches:", bad)
     return 1 if bad else 0

@@ -814,6 +814,15 @@ def test_random_sweep_of_corrupted_streams(api):
     assert fuzz_corrupt_gpu.run(argparse.Namespace(cases=60, seed=13)) == 0
 
 
+def test_random_sweep_of_corrupted_streams_in_other_containers(api):
+    """the same sweep with its `containers` switch, 40 cases: 5, 12, 20 and 31 bits and 24 bits in 3-byte containers,
+    AEC_DATA_MSB and AEC_DATA_SIGNED at random, at most 40 000 samples -- the widths at which a damaged stream's
+    predictor state has room to leave the sample range inside its container"""
+    import argparse
+    import fuzz_corrupt_gpu
+    assert fuzz_corrupt_gpu.run(argparse.Namespace(cases=40, seed=14, containers=True)) == 0
+
+
 def test_random_sweep_of_the_streaming_calls(api):
     """tests/fuzz_stream_gpu.py, 40 cases: aec_encode / aec_decode in random pieces (7 bytes .. 1 MiB of input and of
     room per call), the same calls against the compiled reference: same coded stream; same decoded bytes and return
