@@ -111,6 +111,13 @@ __device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill)
     return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false);               // wave_shr:1
 }
 __device__ __forceinline__ uint32_t wave_last(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
+// lane l's 64-bit value, wave-uniform
+__device__ __forceinline__ uint64_t wave_get64(uint64_t v, uint32_t l)
+{
+    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), (int)l);     // (the builtin returns an int)
+    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, (int)l);
+    return (uint64_t)hi << 32 | lo;
+}
 
 __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, uint32_t)
 {
@@ -1261,67 +1268,129 @@ k_seg_table(const Cfg c, const uint8_t *__restrict__ in, const uint64_t *__restr
 // the last by atomic OR where the run does not own them alone -- k_scan_apply zeroed those, and the words behind cap_words
 // are nobody's, as in k_pack.
 // A lane takes four slot words at a time (the slots are 128-byte aligned) and the word in front of them from the lane
-// below.  A run is a few hundred words: the first loads of all the wavefront's slots are issued before anything waits, and
-// a round's successor is in flight while its words are shifted and stored -- one wavefront per slot that waits for every
-// 64 words in turn spends its life on HBM round trips (0.84 ms at C2 against 0.62 with the second and 0.58 - 0.62 with both).
-constexpr uint32_t kPlaceSlots = 4;
+// below: a ROUND is the wavefront's 256 words.  The order is: the run edges (one load), then the loads of kPlaceRounds
+// rounds of every one of the wavefront's runs, and only then the shifts and stores, run by run and round by round from
+// the registers; a round needs nothing of the one in front but its last word (`carry`, a register).  At C2 a run is
+// three rounds, 11.6 KB a wavefront, 7 wavefronts a SIMD.  A longer run goes on in groups of kPlaceRounds rounds, each
+// group's loads in front of its first store.  What this bought is small (profiles/r15/README.md: 0.56 ms at C2 against
+// 0.58 - 0.59 with one round in flight per run): the copy is not bound by what it has in flight, nor by the
+// instructions of a round; 4 x 4 and 2 x 4 measured no better.
+constexpr uint32_t kPlaceSlots = 4, kPlaceRounds = 3;
+constexpr uint32_t kPlaceRound = 4u * kWave;      // slot words of a round
+
+// Quad `q` of a slot of which `have` words count.  The words behind them are stale and would cost HBM traffic: a lane
+// whose quad lies there reads the last quad that counts once more, a line its wavefront fetches anyway.  So every load
+// is issued whatever the run's length, with no branch around it (loads under a branch measured 0.01 ms slower at C2).
+__device__ __forceinline__ uint4 place_load(const uint4 *__restrict__ slot, uint32_t q, uint32_t have)
+{
+    const uint32_t last = have ? (have - 1u) >> 2 : 0u;
+    return slot[q < last ? q : last];
+}
+
+// What the rounds of a run need besides its span, wave-uniform and relative to the run's first word, so that a lane
+// decides with 32-bit compares: the words [plain_lo, plain_hi) are the run's alone and inside the buffer (a plain store),
+// the words up to `end` are written at all (those that are not plain: by atomic OR, local_word_shared).
+struct PlaceRun {
+    LocalSpan sp;
+    uint32_t plain_lo, plain_hi, end;
+};
+__device__ __forceinline__ PlaceRun place_run(const LocalSpan &sp, uint64_t cap_words)
+{
+    PlaceRun r;
+    r.sp = sp;
+    const uint64_t room = cap_words > sp.word0 ? cap_words - sp.word0 : 0u;
+    const uint32_t cap = room < sp.nwords ? (uint32_t)room : sp.nwords;
+    const uint32_t own = sp.nwords - (sp.tail_shared && sp.nwords ? 1u : 0u);
+    r.plain_lo = sp.head_shared ? 1u : 0u;
+    r.plain_hi = own < cap ? own : cap;
+    r.end = cap;
+    return r;
+}
+
+// the round of a run that starts at slot word `base`, from the lane's quad `cur` of it
+__device__ __forceinline__ void place_round(const PlaceRun &run, uint32_t base, uint32_t lane, const uint4 &cur,
+                                            uint32_t &carry, uint32_t *__restrict__ out_words)
+{
+    typedef uint32_t words4 __attribute__((ext_vector_type(4), aligned(4)));
+    const LocalSpan &sp = run.sp;
+    const uint32_t j0 = base + 4u * lane;
+    uint32_t a0 = cur.x, a1 = cur.y, a2 = cur.z, a3 = cur.w;
+    if (base + kPlaceRound > sp.nslot) {            // (what lies behind the run's last slot word is stale)
+        a0 = j0 < sp.nslot ? a0 : 0u; a1 = j0 + 1 < sp.nslot ? a1 : 0u;
+        a2 = j0 + 2 < sp.nslot ? a2 : 0u; a3 = j0 + 3 < sp.nslot ? a3 : 0u;
+    }
+    const uint32_t before = wave_shr1(a3, carry);       // carry: the slot word in front of this round's first
+    carry = wave_last(a3);
+    const uint32_t v0 = local_word(sp, before, a0), v1 = local_word(sp, a0, a1), v2 = local_word(sp, a1, a2),
+                   v3 = local_word(sp, a2, a3);
+    uint32_t *__restrict__ dst = out_words + sp.word0 + base + 4u * lane;
+    const words4 quad = words4{bswap32(v0), bswap32(v1), bswap32(v2), bswap32(v3)};
+    if (base >= run.plain_lo && base + kPlaceRound <= run.plain_hi) {      // a round in the run's middle: no lane asks
+        *reinterpret_cast<words4 *>(dst) = quad;
+        return;
+    }
+    auto one = [&](uint32_t q, uint32_t v) {        // a word at an end of the run, or of the buffer
+        if (j0 + q < run.end) {
+            if (!local_word_shared(sp, j0 + q))
+                dst[q] = bswap32(v);
+            else if (v != 0)
+                __hip_atomic_fetch_or(&dst[q], bswap32(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    if (j0 >= run.plain_lo && j0 + 4u <= run.plain_hi) {
+        *reinterpret_cast<words4 *>(dst) = quad;
+    } else {
+        one(0, v0); one(1, v1); one(2, v2); one(3, v3);
+    }
+}
 
 __global__ void __launch_bounds__(256)
 k_place(const uint32_t *__restrict__ image, uint32_t slot_words, const uint64_t *__restrict__ seg_start, uint64_t nseg,
         uint32_t segs_per_wave, uint64_t nslots, uint32_t start_bit, const EncResult *__restrict__ res,
         uint32_t *__restrict__ out_words, uint64_t cap_words)
 {
-    typedef uint32_t words4 __attribute__((ext_vector_type(4), aligned(4)));
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t first = ((uint64_t)blockIdx.x * (blockDim.x >> 6) + wave) * kPlaceSlots;
     if (first >= nslots) return;
-    const uint32_t quads = slot_words / 4u;
-    uint64_t edge[kPlaceSlots + 1];           // where the runs start; the last entry: where the last one ends
-    uint4 head[kPlaceSlots];
-#pragma unroll
-    for (uint32_t g = 0; g <= kPlaceSlots; g++) {
-        const uint64_t s = (first + g) * segs_per_wave;
-        edge[g] = first + g > nslots ? 0u : (s < nseg ? seg_start[s] : (uint64_t)start_bit + res->total_bits);
+    // where the runs start, and where the last one ends: lane g reads the edge in front of run g, one load for all
+    uint64_t mine = 0u;
+    if (lane <= kPlaceSlots && first + lane <= nslots) {
+        const uint64_t s = (first + lane) * segs_per_wave;
+        mine = s < nseg ? seg_start[s] : (uint64_t)start_bit + res->total_bits;
     }
-#pragma unroll
-    for (uint32_t g = 0; g < kPlaceSlots; g++)
-        head[g] = first + g < nslots && lane < quads ? reinterpret_cast<const uint4 *>(image + (first + g) * slot_words)[lane]
-                                                     : make_uint4(0u, 0u, 0u, 0u);
+    PlaceRun run[kPlaceSlots];
+    const uint4 *__restrict__ slot[kPlaceSlots];
+    uint32_t have[kPlaceSlots];
 #pragma unroll
     for (uint32_t g = 0; g < kPlaceSlots; g++) {
-        if (first + g >= nslots || edge[g + 1] <= edge[g]) continue;
-        const LocalSpan sp = local_span(edge[g], edge[g + 1] - edge[g]);
-        const uint4 *__restrict__ slot = reinterpret_cast<const uint4 *>(image + (first + g) * slot_words);
-        uint32_t carry = 0u;                                       // the slot word in front of this round's first
-        uint4 cur = head[g];
-        for (uint32_t base = 0; base < sp.nwords; base += 4u * kWave) {
-            const uint32_t j0 = base + 4u * lane, qn = (base >> 2) + kWave + lane;
-            uint4 nxt = make_uint4(0u, 0u, 0u, 0u);       // (a value, not a reference to an object in memory)
-            if (base + 4u * kWave < sp.nwords && qn < quads) nxt = slot[qn];
-            // (what lies behind the run's last slot word is stale)
-            const uint32_t a0 = j0 < sp.nslot ? cur.x : 0u, a1 = j0 + 1 < sp.nslot ? cur.y : 0u,
-                           a2 = j0 + 2 < sp.nslot ? cur.z : 0u, a3 = j0 + 3 < sp.nslot ? cur.w : 0u;
-            const uint32_t before = wave_shr1(a3, carry);
-            carry = wave_last(a3);
-            const uint32_t v0 = local_word(sp, before, a0), v1 = local_word(sp, a0, a1), v2 = local_word(sp, a1, a2),
-                           v3 = local_word(sp, a2, a3);
-            const uint64_t idx = sp.word0 + j0;
-            const bool inner = (j0 != 0 || !sp.head_shared) &&
-                               (j0 + 4 < sp.nwords || (j0 + 4 == sp.nwords && !sp.tail_shared)) && idx + 4 <= cap_words;
-            auto one = [&](uint32_t q, uint32_t v) {        // a word at an end of the run, or of the buffer
-                if (j0 + q < sp.nwords && idx + q < cap_words) {
-                    if (!local_word_shared(sp, j0 + q))
-                        out_words[idx + q] = bswap32(v);
-                    else if (v != 0)
-                        __hip_atomic_fetch_or(&out_words[idx + q], bswap32(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            };
-            if (inner) {
-                *reinterpret_cast<words4 *>(out_words + idx) = words4{bswap32(v0), bswap32(v1), bswap32(v2), bswap32(v3)};
-            } else {
-                one(0, v0); one(1, v1); one(2, v2); one(3, v3);
-            }
-            cur = nxt;
+        const uint64_t from = wave_get64(mine, g), to = wave_get64(mine, g + 1);
+        const bool live = first + g < nslots && to > from;
+        LocalSpan sp = local_span(from, live ? to - from : 0u);
+        if (!live) sp.nwords = 0u;
+        run[g] = place_run(sp, cap_words);
+        have[g] = sp.nslot < slot_words ? sp.nslot : slot_words;
+        slot[g] = reinterpret_cast<const uint4 *>(image + (first + g < nslots ? first + g : first) * slot_words);
+    }
+    uint4 w[kPlaceSlots][kPlaceRounds];
+#pragma unroll
+    for (uint32_t g = 0; g < kPlaceSlots; g++)
+#pragma unroll
+        for (uint32_t r = 0; r < kPlaceRounds; r++) w[g][r] = place_load(slot[g], r * kWave + lane, have[g]);
+#pragma unroll
+    for (uint32_t g = 0; g < kPlaceSlots; g++) {
+        uint32_t carry = 0u;
+#pragma unroll
+        for (uint32_t r = 0; r < kPlaceRounds; r++)
+            if (r * kPlaceRound < run[g].sp.nwords) place_round(run[g], r * kPlaceRound, lane, w[g][r], carry, out_words);
+        // the groups behind the first (C2 has none; data that does not compress fills the slot: about 18 rounds)
+        for (uint32_t base = kPlaceRounds * kPlaceRound; base < run[g].sp.nwords; base += kPlaceRounds * kPlaceRound) {
+            uint4 t[kPlaceRounds];
+#pragma unroll
+            for (uint32_t r = 0; r < kPlaceRounds; r++) t[r] = place_load(slot[g], (base >> 2) + r * kWave + lane, have[g]);
+#pragma unroll
+            for (uint32_t r = 0; r < kPlaceRounds; r++)
+                if (base + r * kPlaceRound < run[g].sp.nwords)
+                    place_round(run[g], base + r * kPlaceRound, lane, t[r], carry, out_words);
         }
     }
 }
@@ -1759,7 +1828,14 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // the stream cost more than the second feed of the input.  8-bit samples in blocks of 8 lose at every size (their runs
 // are a quarter as long, and the placement pays per run); RSIs of part segments have shorter runs still and were not
 // measured.  The tuning build takes it for every open shape with AEC_ENC_LOCAL=1.
+// A wavefront's run is the 8 segments of the other kernels, and kLocalLongRun segments from kLocalLongSegs segments
+// (2 GiB) on: a quarter as many run starts -- guesses, candidates for the redo, shared words and part lines for the
+// placement -- take 0.08 ms off 2.72 at 2 GiB and 0.22 off 5.35 at 4 GiB (placement 0.39 - 0.42 against 0.53 - 0.56 ms),
+// while at 1 GiB and below the fewer, longer wavefronts of k_encode_local cost what the placement saves, or more
+// (profiles/r15/README.md).
 static const uint64_t kLocalMinSegs = 131072;
+static const uint64_t kLocalLongSegs = 1u << 20;
+static const uint32_t kLocalLongRun = 32;
 
 struct LocalPlan {
     bool on;
@@ -1776,9 +1852,9 @@ static LocalPlan local_plan(const Cfg &c)
     const bool wins = c.bs == 16 && c.bytes == 2 && c.rsi % 64 == 0 && c.total_segs >= kLocalMinSegs;
     p.on = direct && (c.flags & F_PREPROCESS) && c.total_segs != 0 && force != 0 && (force == 1 || wins);
     if (!p.on) return p;
-    p.segs_per_wave = make_geom(c, true).segs_per_wave;
+    p.segs_per_wave = wins && c.total_segs >= kLocalLongSegs ? kLocalLongRun : make_geom(c, true).segs_per_wave;
     const uint32_t spw = tune("AEC_ENC_LOCAL_SPW", 0);
-    if (spw == 1 || spw == 2 || spw == 4 || spw == 8) p.segs_per_wave = spw;
+    if (spw == 1 || spw == 2 || spw == 4 || spw == 8 || spw == 16 || spw == 32) p.segs_per_wave = spw;
     p.guess = tune_set("AEC_ENC_LOCAL_GUESS") ? tune("AEC_ENC_LOCAL_GUESS", 0) & 0xFFu : kLocalGuessRule;
     p.slot_words = local_slot_words(c.id_len, c.bs, c.bps, c.rsi, p.segs_per_wave);
     p.waves = (c.total_segs + p.segs_per_wave - 1) / p.segs_per_wave;
