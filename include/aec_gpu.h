@@ -443,6 +443,42 @@ AEC_GPU_API int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_para
                                             aec_gpu_dec_result *d_results, aec_gpu_dec_result *d_result, void *stream);
 
 /*
+ * Which block size?  The exact length of the stream that in_bytes at d_in (16-byte aligned, as for aec_gpu_encode_async)
+ * make under block sizes 8, 16, 32 and 64 -- from ONE read of the input and one pass through the predictor, where a caller
+ * otherwise runs aec_gpu_encode_plan_async once per candidate.  No reference counterpart.
+ *   p      gives bits_per_sample and flags; p->block_size is ignored.
+ *   rsi    rsi[i] = the RSI, in blocks, for block size 8 << i; 0 = this size is not evaluated.  NULL = p->rsi for all four.
+ *   Candidate i is the parameter set {bits_per_sample, 8 << i, rsi[i], flags}.  Every candidate asked for must pass
+ *   aec_gpu_check_params(.., 1), else AEC_CONF_ERROR (the plan: 0); no size asked for is AEC_CONF_ERROR too.
+ *   d_estimate->total_bits[i] is exactly aec_gpu_enc_result.total_bits of aec_gpu_encode_plan_async on the same input
+ *   with candidate i -- max(1, ceil(total_bits / 8)) is the length of aec_buffer_encode's stream -- the padding of a final
+ *   partial block and the short last RSI included; ~0 for a size that was not asked for.  An input without a whole sample
+ *   gives 0 for every size asked for.  best = the index of the smallest total_bits among those asked; ties: the lowest.
+ * Everything is enqueued on `stream`, nothing returns to the host; the call synchronises only when the context's buffer
+ * has to grow.  Its workspace (a 16-bit record per block and size: 0.47 bytes per sample for all four) is the encoder's
+ * -- counted by aec_gpu_held_bytes, released by aec_gpu_trim -- so, as for any other encode, an estimate between a PLAN
+ * and its EMIT on the same context is not allowed.
+ * aec_gpu_estimate_plan is host arithmetic only (1 = the call is taken, 0 = it would be refused): the sizes evaluated and
+ * the device memory the context holds for such a call.  (The plan record goes by its struct tag: the function has its name.)
+ */
+#define AEC_GPU_ESTIMATE_SIZES 4                 /* block sizes 8, 16, 32, 64 in this order */
+typedef struct aec_gpu_estimate {
+    uint64_t total_bits[AEC_GPU_ESTIMATE_SIZES]; /* ~0 for a size that was not asked for */
+    uint32_t best;                               /* index of the smallest total_bits among those asked; ties: the lowest index */
+    uint32_t pad;
+} aec_gpu_estimate;
+struct aec_gpu_estimate_plan {
+    uint32_t evaluated;                          /* bit i set: size i is evaluated */
+    uint32_t pad;
+    size_t   workspace_bytes;                    /* device memory the context holds for such a call */
+};
+AEC_GPU_API int aec_gpu_estimate_plan(const aec_gpu_params *p, const unsigned int rsi[AEC_GPU_ESTIMATE_SIZES],
+                                      size_t in_bytes, struct aec_gpu_estimate_plan *plan);
+AEC_GPU_API int aec_gpu_estimate_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                                       const unsigned int rsi[AEC_GPU_ESTIMATE_SIZES], aec_gpu_estimate *d_estimate,
+                                       void *stream);
+
+/*
  * Measurement hooks (bench.py): with profiling enabled the context records HIP events on the
  * caller's stream around its kernels, one event set per call (a ring of 32), so a timed loop
  * needs no synchronisation inside it; aec_gpu_phase_ms waits for them and returns the device

@@ -13,6 +13,7 @@
 #include "aec_chunks.h"
 #include "aec_dchunks.h"
 #include "aec_devbuf.h"
+#include "aec_est.h"
 #include "aec_kernels.h"
 
 using namespace aec;
@@ -66,6 +67,7 @@ static_assert(sizeof(aec_gpu_seg_entry) == sizeof(SegEntry), "segment table layo
 
 static_assert(sizeof(aec_gpu_enc_result) == sizeof(EncResult), "result layout");
 static_assert(sizeof(aec_gpu_dec_result) == sizeof(DecResult), "result layout");
+static_assert(sizeof(aec_gpu_estimate) == sizeof(EstResult) && AEC_GPU_ESTIMATE_SIZES == kEstSizes, "result layout");
 
 static int cfg_from(const aec_gpu_params *p, size_t in_bytes, bool enc, Cfg *c)
 {
@@ -490,6 +492,37 @@ size_t aec_gpu_held_bytes(const aec_gpu_ctx *ctx)
     if (ctx)
         for (const DevBuf *b : ctx->held) sum += b->cap;
     return sum;
+}
+
+// ---- the coded size under block sizes 8, 16, 32 and 64 in one pass (aec_est.h, aec_est.hip) -----------------------------
+int aec_gpu_estimate_plan(const aec_gpu_params *p, const unsigned int *rsi, size_t in_bytes,
+                          struct aec_gpu_estimate_plan *plan)
+{
+    if (!p || !plan) return 0;
+    EstCfg e;
+    size_t need = 0;
+    if (make_est_cfg(p->bits_per_sample, p->flags, rsi, p->rsi, in_bytes, &e, &need) != RC_OK) return 0;
+    plan->evaluated = e.mask;
+    plan->pad = 0;
+    plan->workspace_bytes = need;
+    return 1;
+}
+
+int aec_gpu_estimate_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                           const unsigned int *rsi, aec_gpu_estimate *d_estimate, void *stream)
+{
+    if (!ctx || !p || !d_estimate) return RC_CONF_ERROR;
+    EstCfg e;
+    size_t need = 0;
+    const int rc = make_est_cfg(p->bits_per_sample, p->flags, rsi, p->rsi, in_bytes, &e, &need);
+    if (rc != RC_OK) return rc;
+    if (e.pieces && (!d_in || (reinterpret_cast<uintptr_t>(d_in) & 15u))) return RC_CONF_ERROR;
+    // the records of all four sizes come out of the encoder's workspace: no encode of this context is under way
+    if (!ctx->ws.replace(need, need)) return RC_MEM_ERROR;
+    (void)hipGetLastError();
+    launch_estimate(e, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(ctx->ws.p),
+                    reinterpret_cast<EstResult *>(d_estimate), static_cast<hipStream_t>(stream));
+    return launched();
 }
 
 int aec_gpu_index_batch_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,

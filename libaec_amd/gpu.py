@@ -25,6 +25,16 @@ class DChunksPlan(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+class Estimate(C.Structure):
+    """aec_gpu_estimate: total_bits per block size 8, 16, 32, 64 (~0: not asked for) and the index of the smallest"""
+    _fields_ = [("total_bits", C.c_uint64 * 4), ("best", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class EstimatePlan(C.Structure):
+    _fields_ = [("evaluated", C.c_uint32), ("pad", C.c_uint32), ("workspace_bytes", C.c_size_t)]
+
+
+ESTIMATE_DTYPE = np.dtype([("total_bits", "<u8", (4,)), ("best", "<u4"), ("pad", "<u4")])
 SEG_ENTRY_DTYPE = np.dtype([("bit", "<u8"), ("prev", "<u4"), ("pad", "<u4")])
 ENC_RESULT_DTYPE = np.dtype([("total_bits", "<u8"), ("k_out", "<u4"), ("overflow", "<u4"),
                              ("k_lo", "<u4"), ("k_hi", "<u4")])
@@ -91,6 +101,11 @@ def _lib():
             lib.aec_gpu_decode_chunks_plan.argtypes = [pp, vp, u64, C.POINTER(DChunksPlan)]
             lib.aec_gpu_decode_chunks_async.restype = C.c_int
             lib.aec_gpu_decode_chunks_async.argtypes = [vp, pp, vp, sz, vp, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp]
+        if hasattr(lib, "aec_gpu_estimate_async"):          # (AEC_AMD_LIB: a build from before the call)
+            lib.aec_gpu_estimate_plan.restype = C.c_int
+            lib.aec_gpu_estimate_plan.argtypes = [pp, C.POINTER(C.c_uint), sz, C.POINTER(EstimatePlan)]
+            lib.aec_gpu_estimate_async.restype = C.c_int
+            lib.aec_gpu_estimate_async.argtypes = [vp, pp, vp, sz, C.POINTER(C.c_uint), vp, vp]
         lib.aec_gpu_index_async.restype = C.c_int
         lib.aec_gpu_index_async.argtypes = [vp, pp, vp, sz, u64, vp, u64, vp, vp]
         lib.aec_gpu_segments_per_rsi.restype = C.c_uint
@@ -185,6 +200,26 @@ def decode_chunks_plan(bits_per_sample, block_size, rsi, flags, out_sizes):
             "workspace_bytes": int(plan.workspace_bytes)}
 
 
+def _rsi4(rsi):
+    """the four RSIs of an estimate as the C array; None stays NULL (the parameter set's rsi for all four sizes)"""
+    if rsi is None:
+        return None
+    if len(rsi) != 4:
+        raise ValueError("rsi: one value per block size 8, 16, 32, 64 (0 = not evaluated), or None")
+    return (C.c_uint * 4)(*[int(r) for r in rsi])
+
+
+def estimate_plan(bits_per_sample, flags, rsi, in_bytes, rsi_all=0):
+    """aec_gpu_estimate_plan: host arithmetic of an estimate of in_bytes.  rsi: four RSIs in blocks for block sizes 8, 16,
+    32, 64 (0 = not evaluated) or None (rsi_all, the parameter set's rsi, for all).  Returns the dict {evaluated, workspace_bytes}, or None where
+    the call would be refused."""
+    p = Params(bits_per_sample, 0, rsi_all, flags)
+    plan = EstimatePlan()
+    if not _lib().aec_gpu_estimate_plan(C.byref(p), _rsi4(rsi), in_bytes, C.byref(plan)):
+        return None
+    return {"evaluated": int(plan.evaluated), "workspace_bytes": int(plan.workspace_bytes)}
+
+
 class Codec:
     """One aec_gpu context (workspace) on the current torch device."""
 
@@ -258,6 +293,24 @@ class Codec:
     def encode_plan_async(self, d_in, in_bytes, d_result, stream=None):
         """first half of an encode: leaves total_bits and (k_lo, k_hi) in d_result"""
         self._enqueue(self.lib.aec_gpu_encode_plan_async, stream, _ptr(d_in), in_bytes, _ptr(d_result))
+
+    def estimate_async(self, d_in, in_bytes, rsi, d_estimate, stream=None):
+        """aec_gpu_estimate_async: the exact total_bits of d_in under block sizes 8, 16, 32 and 64 from one pass, into
+        d_estimate (uint8 tensor of 40 bytes: ESTIMATE_DTYPE).  rsi: four RSIs in blocks (0 = not evaluated) or None (this
+        codec's rsi for all); the codec's block size plays no part.  Returns the call's return code."""
+        return self.lib.aec_gpu_estimate_async(self.ctx, C.byref(self.p), _ptr(d_in), in_bytes, _rsi4(rsi),
+                                               _ptr(d_estimate), self._stream(stream))
+
+    def estimate(self, d_in, rsi=None):
+        """estimate_async on the whole tensor, synchronising: returns (total_bits[4], best); a size not asked for has
+        total_bits None"""
+        d_est = self.torch.zeros(ESTIMATE_DTYPE.itemsize, dtype=self.torch.uint8, device=d_in.device)
+        rc = self.estimate_async(d_in, d_in.numel(), rsi, d_est)
+        if rc != 0:
+            raise ValueError(f"aec_gpu_estimate_async failed ({rc})")
+        rec = d_est.cpu().numpy().view(ESTIMATE_DTYPE)[0]
+        none = (1 << 64) - 1
+        return [None if int(t) == none else int(t) for t in rec["total_bits"]], int(rec["best"])
 
     def encode_emit_async(self, d_in, in_bytes, d_out, d_offsets, d_result, start_bit, k_in, stream=None):
         """second half: writes the stream at bit `start_bit` of d_out[0] with carried k `k_in`"""
