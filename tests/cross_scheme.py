@@ -10,7 +10,11 @@ away one after the other, aec_gpu_index_scheme says which one is left, and for e
 encoder's table, the record the end of the stream, the decoded bytes the oracle's -- for the whole stream, a stream cut
 short, a stream with bytes behind the caller's bound, and a walk that resumes inside an RSI.
 
-    AEC_AMD_LIB=libaec_amd/lib/tuning/libaec.so.0 python tests/cross_scheme.py [--quick]
+    AEC_AMD_LIB=libaec_amd/lib/tuning/libaec.so.0 python tests/cross_scheme.py [--quick] [--narrow]
+
+--narrow swaps the shape list for tests/narrow_cases.py: FORCED -- generic block sizes, samples below 8 bits, restricted code
+sets, odd containers -- and the last assertion for the schemes tests/golden/narrow_chain.json names per shape and per class
+(the region index does not admit block headers of one and two bits).
 """
 import argparse
 import os
@@ -51,10 +55,14 @@ def smooth(rng, n, bps, signed, scale, zero_frac=0.05, jump_frac=0.0005):
 PAD = H.AEC_PAD_RSI
 
 
-def make_stream(rng, bps, bs, rsi, flags, nbytes, scale):
+def make_stream(rng, bps, bs, rsi, flags, nbytes, scale, case=None):
     nb = H.bytes_per_sample(bps, flags)
     n = nbytes // nb // bs * bs                          # whole blocks
-    data = H.pack_samples(smooth(rng, n, bps, bool(flags & SGN), scale), bps, flags)
+    if case is not None:                                 # (--narrow: the case's own data)
+        import narrow_cases
+        data = narrow_cases.case_data(case, n)
+    else:
+        data = H.pack_samples(smooth(rng, n, bps, bool(flags & SGN), scale), bps, flags)
     if flags & PAD:
         # AEC_PAD_RSI is the DECODER's flag (reference decode.c:407-408; the encoder's padding is dead code, encode.c:499-505):
         # a stream whose RSIs begin on bytes is the RSIs coded one by one, each padded to a byte
@@ -82,6 +90,7 @@ def make_stream(rng, bps, bs, rsi, flags, nbytes, scale):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--narrow", action="store_true", help="the shapes of tests/narrow_cases.py in place of the list below")
     args = ap.parse_args()
     import torch
     from libaec_amd import gpu
@@ -108,9 +117,16 @@ def main():
                (8, 8, 128, PP, 20 * MiB, 1.2), (16, 64, 256, PP | MSB, 20 * MiB, 40.0)]
     # AEC_PAD_RSI: every RSI begins on a byte (the every-bit scheme from round 6 on, the trunk, the serial walker)
     shapes += [(16, 16, 8, PP | PAD, 100 * KiB, 2.0), (8, 8, 64, PP | PAD | MSB, 600 * KiB, 1.2), (16, 16, 128, PAD, 600 * KiB, 30.0)]
+    want = None
+    if args.narrow:
+        import narrow_cases
+        shapes = [(*narrow_cases.prm(c), narrow_cases.forced_samples(c, size) * H.bytes_per_sample(c.bps, c.flags), 0.0, c)
+                  for c, size in narrow_cases.FORCED]         # (whole RSIs: the streams of the table)
+        want = narrow_cases.golden_chains()["forced"]
+        ran_in = {cls: {s: 0 for s in range(6)} for cls in narrow_cases.CLASSES}
     ran = {s: 0 for s in range(6)}
-    for (bps, bs, rsi, flags, size, scale) in shapes:
-        data, enc, tr, offs, bits = make_stream(rng, bps, bs, rsi, flags, size, scale)
+    for (bps, bs, rsi, flags, size, scale, *case) in shapes:
+        data, enc, tr, offs, bits = make_stream(rng, bps, bs, rsi, flags, size, scale, *case)
         n_rsi = len(offs)
         hint = bits // max(1, n_rsi)
         codec = gpu.Codec(bps, bs, rsi, flags)
@@ -189,11 +205,25 @@ def main():
                     assert np.array_equal(got, offs[r0:]), (tag, "resumed walk", j)
                     assert int(res["end_bit"]) == bits, (tag, "resumed walk: end")
         assert taken, (bps, bs, rsi, flags, size)
+        if want is not None:
+            row = want[narrow_cases.case_id(case[0])]
+            assert (len(enc), hint) == (row["in_bytes"], row["rsi_bits"]), (narrow_cases.case_id(case[0]), len(enc), hint)
+            assert taken == row["schemes"], (narrow_cases.case_id(case[0]), taken)
+            for s in taken:
+                ran_in[case[0].cls][s] += 1
         codec.close()
         print(f"{bps}-bit block {bs} rsi {rsi} flags {flags} {size >> 10} KiB ({n_rsi} RSIs of {hint} bits): "
               + ", ".join(SCHEMES[s] for s in taken), flush=True)
     print("schemes exercised:", {SCHEMES[s]: n for s, n in ran.items() if n})
-    assert all(ran[s] for s in (1, 2, 3, 4, 5)), ran
+    if want is not None:
+        # per class, every scheme aec_gpu_index_scheme names for one of its shapes (the CPU table) has run
+        for cls in narrow_cases.CLASSES:
+            legal = sorted({s for c, _ in narrow_cases.FORCED if c.cls == cls for s in want[narrow_cases.case_id(c)]["schemes"]})
+            assert legal and all(ran_in[cls][s] for s in legal), (cls, legal, ran_in[cls])
+            print(f"{cls}:", ", ".join(SCHEMES[s] for s in legal))
+        assert all(ran[s] for s in (1, 2, 3, 4)), ran
+    else:
+        assert all(ran[s] for s in (1, 2, 3, 4, 5)), ran
     print("cross scheme ok")
 
 
