@@ -158,6 +158,56 @@ AEC_GPU_API int aec_gpu_sz_decompress_chunks_async(aec_gpu_ctx *ctx, const SZ_co
                                                    aec_gpu_dec_result *d_results, aec_gpu_dec_result *d_result,
                                                    void *stream);
 
+/*
+ * Which pixels_per_block?  The length of SZ_BufftoBuffCompress's stream of every chunk of a batch under pixels per block
+ * 8, 16, 32 and 64, from ONE read of the chunks: nothing is marshalled to memory, no stream is written and no d_work is
+ * needed.  (aec_gpu_estimate_async answers for ONE coder input; SZIP pads every scan line to whole blocks of the candidate
+ * size, so the coder's input differs per candidate.)
+ *
+ * sz gives options_mask and bits_per_pixel; sz->pixels_per_block is ignored.  Candidate i is {options_mask,
+ * bits_per_pixel, 8 << i, pixels_per_scanline[i]}; pixels_per_scanline[i] == 0 leaves size i out, pixels_per_scanline ==
+ * NULL takes sz->pixels_per_scanline for all four.  (HDF5 derives the scan line from pixels_per_block when a chunk's row
+ * is shorter than a block or longer than 128 blocks, hence a scan line per candidate.)  Sizes that share a scan line are
+ * evaluated in one pass over the chunks; each further distinct scan line costs one more pass, one behind the other on the
+ * stream: plan.passes.
+ *
+ * src_offsets and chunk_bytes are HOST arrays with the contract of aec_gpu_sz_compress_chunks_async (any byte offset,
+ * any order, no overlap, nothing between the chunks is read, free again on return).  d_chunk_bits (optional, n_chunks * 4
+ * entries): entry [c * 4 + i] is exactly the `bits` that aec_gpu_sz_compress_chunks_async writes into d_chunks[c] for
+ * candidate i, ~0 for a size not asked.  d_estimate->total_bytes[i] is the sum over c of max(1, ceil(bits / 8)), the
+ * length of SZ_BufftoBuffCompress's stream of chunk c.
+ *
+ * AEC_CONF_ERROR with nothing enqueued (the plan returns 0): no size asked; an asked candidate that aec_gpu_sz_layout
+ * rejects for any chunk (more than 4096 blocks per line, a chunk without a whole pixel, ...); totals a launch cannot
+ * count, by the bounds of aec_gpu_sz_chunks_plan applied to every asked candidate.  n_chunks == 0: AEC_OK, the record
+ * holds 0 for every size asked and best is the lowest index asked.
+ *
+ * The call only enqueues and synchronises only where a buffer of the context grows.  Its workspace -- the 16-bit block
+ * records of the sizes of one pass, the per-chunk sums, the chunk descriptors and wavefront tables -- is the context's:
+ * aec_gpu_held_bytes counts it, aec_gpu_trim releases it, plan.workspace_bytes is what the context holds after such a
+ * call at most.  It shares that buffer with the SZIP chunk calls above, and as any estimate or encode it may not run
+ * between a PLAN and its EMIT on the same context.
+ */
+#define AEC_GPU_SZ_ESTIMATE_SIZES 4           /* pixels_per_block 8, 16, 32, 64 in this order */
+typedef struct aec_gpu_sz_estimate_s {
+    uint64_t total_bytes[AEC_GPU_SZ_ESTIMATE_SIZES]; /* sum over the chunks of the length of SZ_BufftoBuffCompress's stream; ~0: not asked */
+    uint32_t best;                                   /* index of the smallest total_bytes among those asked; ties: the lowest */
+    uint32_t pad;                                    /* 0 */
+} aec_gpu_sz_estimate_t;
+struct aec_gpu_sz_estimate_plan {
+    uint32_t evaluated;       /* bit i set: size i is evaluated */
+    uint32_t passes;          /* distinct scan lines among the sizes asked */
+    uint64_t pieces;          /* pieces of 64 coder samples over all passes: the lanes that code */
+    size_t   workspace_bytes; /* device memory the context holds for such a call */
+};
+AEC_GPU_API int aec_gpu_sz_estimate_plan(const SZ_com_t *sz, const unsigned int pixels_per_scanline[AEC_GPU_SZ_ESTIMATE_SIZES],
+                                         const uint64_t *chunk_bytes, uint64_t n_chunks,
+                                         struct aec_gpu_sz_estimate_plan *plan);
+AEC_GPU_API int aec_gpu_sz_estimate_async(aec_gpu_ctx *ctx, const SZ_com_t *sz,
+                                          const unsigned int pixels_per_scanline[AEC_GPU_SZ_ESTIMATE_SIZES], const void *d_src,
+                                          const uint64_t *src_offsets, const uint64_t *chunk_bytes, uint64_t n_chunks,
+                                          uint64_t *d_chunk_bits, aec_gpu_sz_estimate_t *d_estimate, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -653,7 +653,7 @@ static aec_gpu_ctx::ChunkStage *stage_descriptors(aec_gpu_ctx *ctx, size_t h_nee
 // copy failed.
 static uint8_t *send_descriptors(DevBuf &d, aec_gpu_ctx::ChunkStage *s, size_t h_need, size_t d_need, hipStream_t st)
 {
-    if (!d.replace(d_need, (d_need + d_need / 4 + 255) & ~(size_t)255)) return nullptr;
+    if (!d.replace(d_need, ctx_desc_room(d_need))) return nullptr;
     (void)hipGetLastError();   // only errors of THIS call are reported by it
     if (hipMemcpyAsync(d.p, s->h.p, h_need, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipEventRecord(s->ev, st) != hipSuccess)

@@ -262,6 +262,8 @@ size_t index_batch_workspace_bytes(const Cfg &c, size_t in_bytes, uint64_t n_chu
 // room for h_need bytes and free to write: *h.  Returns the stage for step 2, null where there is no memory.
 // Step 2: h_need bytes of it, in stream order, to the context's device buffer of the SZIP layer, which gets room for
 // d_need bytes (it grows like chunks_d, is counted by aec_gpu_held_bytes and released by aec_gpu_trim).  null = failed.
+// what a descriptor buffer of the context allocates when it has to grow to d_need bytes (a plan's workspace_bytes)
+inline size_t ctx_desc_room(size_t d_need) { return (d_need + d_need / 4 + 255) & ~(size_t)255; }
 void *ctx_sz_stage(::aec_gpu_ctx *ctx, size_t h_need, void **h);
 uint8_t *ctx_sz_send(::aec_gpu_ctx *ctx, void *stage, size_t h_need, size_t d_need, hipStream_t st);
 

@@ -26,7 +26,20 @@ class ChunksPlan(C.Structure):
                 ("workspace_bytes", C.c_size_t), ("direct", C.c_uint)]
 
 
+class SzEstimate(C.Structure):
+    """aec_gpu_sz_estimate_t"""
+    _fields_ = [("total_bytes", C.c_uint64 * 4), ("best", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SzEstimatePlan(C.Structure):
+    """struct aec_gpu_sz_estimate_plan"""
+    _fields_ = [("evaluated", C.c_uint32), ("passes", C.c_uint32), ("pieces", C.c_uint64), ("workspace_bytes", C.c_size_t)]
+
+
 BATCH_CHUNK_DTYPE = np.dtype([("base_bits", "<u8"), ("bits", "<u8")])
+SZ_ESTIMATE_DTYPE = np.dtype([("total_bytes", "<u8", 4), ("best", "<u4"), ("pad", "<u4")])
+SZ_ESTIMATE_SIZES = 4               # pixels per block 8, 16, 32, 64 in this order
+NOT_ASKED = (1 << 64) - 1
 
 _bound = False
 
@@ -59,6 +72,11 @@ def _lib():
             lib.aec_gpu_sz_decompress_chunks_async.restype = C.c_int
             lib.aec_gpu_sz_decompress_chunks_async.argtypes = [vp, ps, vp, sz, vp, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp,
                                                                vp, vp]
+        if hasattr(lib, "aec_gpu_sz_estimate_plan"):        # (AEC_AMD_LIB: a build from before the call)
+            lib.aec_gpu_sz_estimate_plan.restype = C.c_int
+            lib.aec_gpu_sz_estimate_plan.argtypes = [ps, vp, vp, u64, C.POINTER(SzEstimatePlan)]
+            lib.aec_gpu_sz_estimate_async.restype = C.c_int
+            lib.aec_gpu_sz_estimate_async.argtypes = [vp, ps, vp, vp, vp, vp, u64, vp, vp, vp]
         _bound = True
     return lib
 
@@ -86,6 +104,28 @@ def chunks_plan(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanl
     return dict(coder=(plan.coder.bits_per_sample, plan.coder.block_size, plan.coder.rsi, plan.coder.flags),
                 work_bytes=int(plan.work_bytes), out_bound=int(plan.out_bound), rsi_entries=int(plan.rsi_entries),
                 workspace_bytes=int(plan.workspace_bytes), direct=int(plan.direct), work_offsets=offs[:sizes.size])
+
+
+def _pps(pps):
+    """the four candidates' pixels per scan line for a call (None stays None: the SZ_com_t's for all four)"""
+    if pps is None:
+        return None
+    if len(pps) != SZ_ESTIMATE_SIZES:
+        raise ValueError("pixels per scan line: one value per pixels-per-block 8, 16, 32, 64 (0: not asked)")
+    return (C.c_uint * SZ_ESTIMATE_SIZES)(*[int(v) for v in pps])
+
+
+def estimate_plan(options_mask, bits_per_pixel, pixels_per_scanline, sizes, pps=None):
+    """aec_gpu_sz_estimate_plan (host arithmetic, no device needed) for chunks of `sizes` bytes: the dict {evaluated, passes,
+    pieces, workspace_bytes}, or None where the call would be refused.  pps: per pixels-per-block 8, 16, 32, 64 the pixels
+    per scan line (0: not asked); None: pixels_per_scanline for all four."""
+    p = SZ_com_t(options_mask, bits_per_pixel, 0, pixels_per_scanline)
+    sizes = _u64(sizes)
+    plan = SzEstimatePlan()
+    if not _lib().aec_gpu_sz_estimate_plan(C.byref(p), _pps(pps), _host(sizes), sizes.size, C.byref(plan)):
+        return None
+    return dict(evaluated=int(plan.evaluated), passes=int(plan.passes), pieces=int(plan.pieces),
+                workspace_bytes=int(plan.workspace_bytes))
 
 
 def layout(options_mask, bits_per_pixel, pixels_per_block, pixels_per_scanline, chunk_bytes):
@@ -217,6 +257,34 @@ class SzCodec:
                                                            _host(ins), _host(dso), _host(sizes), sizes.size, _ptr(d_table),
                                                            int(bool(have_table)), _ptr(d_work), _ptr(d_dst), _ptr(d_results),
                                                            _ptr(d_result), self._stream(stream))
+
+    # ---- which pixels_per_block? (aec_gpu_sz_estimate_async) -------------------------------------
+    def estimate_plan(self, sizes, pps=None):
+        s = self.sz
+        return estimate_plan(s.options_mask, s.bits_per_pixel, s.pixels_per_scanline, sizes, pps)
+
+    def estimate_async(self, d_src, src_offsets, sizes, d_chunk_bits, d_estimate, pps=None, stream=None):
+        """src_offsets / sizes: uint64 arrays on the host; d_chunk_bits: int64 tensor of n * 4 entries, or None;
+        d_estimate: 40 bytes (SZ_ESTIMATE_DTYPE).  Returns the call's return code."""
+        offs, sizes = _u64(src_offsets), _u64(sizes)
+        return self.lib.aec_gpu_sz_estimate_async(self.ctx, C.byref(self.sz), _pps(pps), _ptr(d_src), _host(offs), _host(sizes),
+                                                  sizes.size, _ptr(d_chunk_bits), _ptr(d_estimate), self._stream(stream))
+
+    def estimate(self, d_src, src_offsets, sizes, pps=None):
+        """the length of SZ_BufftoBuffCompress's streams of the chunks under pixels per block 8, 16, 32, 64 ->
+        (total_bytes, best, chunk_bits): total_bytes[i] over all chunks (None: not asked), best the index of the smallest,
+        chunk_bits an (n, 4) uint64 array of the streams' bits (NOT_ASKED where not asked).  Synchronises."""
+        torch = self.torch
+        n = len(sizes)
+        d_bits = torch.zeros(max(1, n) * SZ_ESTIMATE_SIZES, dtype=torch.int64, device=d_src.device)
+        d_est = torch.zeros(SZ_ESTIMATE_DTYPE.itemsize, dtype=torch.uint8, device=d_src.device)
+        rc = self.estimate_async(d_src, src_offsets, sizes, d_bits, d_est, pps)
+        if rc != 0:
+            raise ValueError("not an estimate for one call (aec_gpu_sz_estimate_plan)") if rc == AEC_CONF_ERROR else \
+                RuntimeError(f"aec_gpu_sz_estimate_async failed ({rc})")
+        est = d_est.cpu().numpy().view(SZ_ESTIMATE_DTYPE)[0]
+        total = [None if int(v) == NOT_ASKED else int(v) for v in est["total_bytes"]]
+        return total, int(est["best"]), d_bits.cpu().numpy().view(np.uint64)[:n * SZ_ESTIMATE_SIZES].reshape(n, SZ_ESTIMATE_SIZES)
 
     def held_bytes(self):
         self.lib.aec_gpu_held_bytes.restype = C.c_size_t
