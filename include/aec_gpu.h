@@ -405,13 +405,13 @@ AEC_GPU_API int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_para
  *            aec_gpu_encode_chunks_async writes.  No index pass; in_offsets and in_bytes_each may be NULL.  The call is
  *            the upload of the descriptors, one set-up kernel, ONE decode launch and the (idle) sequential decoder
  *            behind it.
- *   have_table == 0   bare streams: the same table (plan.rsi_entries entries) is filled first -- one wavefront per
- *            stream walks from bit 8 * in_offsets[i] to at most bit 8 * (in_offsets[i] + in_bytes_each[i]), so streams
- *            may lie back to back without padding, and writes up to rsi_count_i starts at the chunk's place -- then the
- *            same decode launch runs with every chunk's counts from its record on the device.  Only the serial walk is
- *            used here: there are no window tables for unequal batches, so large low-entropy chunks (tens of KiB and
- *            more per stream) are better served chunk by chunk (aec_gpu_index_async + aec_gpu_decode_indexed_async) or
- *            as an equal batch (aec_gpu_decode_batch_async), as the libaec ABI's batch decode decides.
+ *   have_table == 0   bare streams: the same table (plan.rsi_entries entries) is filled first, by the index pass of
+ *            aec_gpu_index_chunks_async below, run as the context's aec_gpu_set_chunks_index says -- stream i is read
+ *            from bit 8 * in_offsets[i] to at most bit 8 * (in_offsets[i] + in_bytes_each[i]), so streams may lie
+ *            back to back without padding, and up to rsi_count_i starts are written at the chunk's place -- then the
+ *            same decode launch runs with every chunk's counts from its record on the device.  Streams of tens of
+ *            KiB go through the every-bit scheme, many in one set of launches; short ones, and streams beyond 2^24
+ *            bits (there are no window tables for unequal batches), are walked by one wavefront each.
  *   d_results[i]   bare streams: the index record of stream i as aec_gpu_index_batch_async writes it (n_rsi / tail_blocks
  *            below what the chunk announces: the stream was shorter; status 2: corrupt); with a table: n_rsi /
  *            tail_blocks from the arguments, status 0.  Either way raised to status 2 when one of the chunk's items
@@ -426,7 +426,8 @@ AEC_GPU_API int aec_gpu_encode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_para
  *
  * aec_gpu_decode_chunks_plan is host arithmetic only (1 = the batch is taken, 0 = it would be refused: more than
  * 2^31 - 1 chunks or items -- a launch addresses at most that many workgroups, and a wavefront per item is one of the
- * ways an item is decoded -- or invalid parameters).
+ * ways an item is decoded -- or invalid parameters).  Its workspace_bytes does not count the index pass of a bare
+ * batch: that is aec_gpu_index_chunks_plan's, below.
  */
 typedef struct aec_gpu_dchunks_plan {
     uint64_t items;          /* sum of rsi_count_i: the decode launch's items */
@@ -441,6 +442,69 @@ AEC_GPU_API int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_para
                                             const uint64_t *out_offsets, const uint64_t *out_bytes, uint64_t n_chunks,
                                             uint64_t *d_rsi_bit_offsets, int have_table, void *d_out,
                                             aec_gpu_dec_result *d_results, aec_gpu_dec_result *d_result, void *stream);
+
+/*
+ * The index pass of such a batch of BARE streams, as a call of its own and as the first step of
+ * aec_gpu_decode_chunks_async(have_table == 0) -- for streams of a foreign producer (every HDF5 / netCDF file written
+ * through the CPU library): index once, keep the table where the streams are kept, read with have_table != 0 ever after.
+ * No reference counterpart.
+ *
+ * Two schemes share the pass.  The EVERY-BIT scheme parses the coded data set that would begin at every bit of a stream,
+ * walks one RSI from every bit and ranks the RSI starts by pointer doubling -- no guesses, any parameter set -- for many
+ * streams in one set of launches: every stream has a slot of 8 * in_bytes_each[i] + 1 entries in per-bit tables (8 bytes
+ * per entry, 12 where rsi > 16), its own end bound and its own chain.  The batch is cut into rounds of whole streams whose
+ * slots (rounded up to 1024 entries) fit round_bits entries; the rounds use the same tables one after the other, all
+ * launches are enqueued at once.  The SERIAL WALK, one wavefront per stream, is enqueued once behind all rounds and walks
+ * exactly the streams the every-bit scheme has not delivered: those it does not take, and those it gives up -- a coded
+ * data set that does not parse, a chain that ends anywhere but at the end of the input, a run of zero blocks that does
+ * not fit.  The walk is the only verdict on damaged streams.  Whichever scheme delivers a stream, its record and the
+ * entries 0 .. n_rsi - 1 (and entry n_rsi where tail_blocks != 0) of its part of the table are byte for byte the same.
+ *
+ * The every-bit scheme's LIMITS: a stream of 64 to 2^24 bits whose slot fits a round, rsi <= 256.
+ * aec_gpu_set_chunks_index says how the bare chunk index passes of a context run (a plain setter):
+ *   AEC_GPU_CHUNKS_INDEX_PLANNED    (default) the walk costs what the LONGEST stream it is left with costs (0.4 to 0.6 us
+ *                                   per block, a wavefront per stream), the every-bit scheme what ALL the bits it takes
+ *                                   cost (0.1 ns per bit, 0.1 ms per round).  The plan takes the streams within the limits
+ *                                   that announce at least T blocks, for the T among 128, 512, 2048, ... whose pass it
+ *                                   expects to be the shortest, in at most 16 rounds -- and none where the walk alone is
+ *                                   expected to be as fast: few long streams are taken (16 chunks of 4 to 128 KiB: 0.5
+ *                                   against 6.2 ms; 64 x 1 MiB: 16 against 49 ms), a thousand streams about as long as
+ *                                   the longest are not (17.6 against 6.5 ms).  Measured on an MI355X:
+ *                                   profiles/r18/bench_index_chunks.txt.
+ *   AEC_GPU_CHUNKS_INDEX_SERIAL     the serial walk alone.
+ *   AEC_GPU_CHUNKS_INDEX_EVERY_BIT  every stream within the limits, in as many rounds as they take.
+ *   round_bits   the budget of a round in table entries, for callers short of memory: 0 = the default (2^24), at least
+ *                4096, values above the default are clamped.
+ *
+ * aec_gpu_index_chunks_plan is host arithmetic only (1 = the batch is taken, 0 = refused, as aec_gpu_decode_chunks_plan
+ * refuses): what a pass of such a batch under `how` and round_bits does.  O(n_chunks) per pass over the chunks.
+ *
+ * aec_gpu_index_chunks_async: the pass alone.  Arrays as for aec_gpu_decode_chunks_async (host arrays of n_chunks
+ * entries); it writes the table in the layout aec_gpu_encode_chunks_async writes (plan.rsi_entries entries, chunk i from
+ * entry sum over j < i of (rsi_count_j + 1) on, nothing outside a chunk's rsi_count_i + 1 entries) and d_results[i], the
+ * index record of stream i.  d_how (optional, n_chunks entries): 1 = the every-bit scheme delivered stream i, 0 = the
+ * walker did.  Argument checks as for aec_gpu_decode_chunks_async(have_table == 0); n_chunks == 0: AEC_OK, nothing is
+ * enqueued.  The call only enqueues; it synchronises only where one of the context's buffers grows: the descriptors'
+ * and the index-table buffer, which holds plan.workspace_bytes (counted by aec_gpu_held_bytes, released by aec_gpu_trim).
+ * Without memory for the tables the serial walk runs alone.
+ */
+#define AEC_GPU_CHUNKS_INDEX_PLANNED 0
+#define AEC_GPU_CHUNKS_INDEX_SERIAL 1
+#define AEC_GPU_CHUNKS_INDEX_EVERY_BIT 2
+typedef struct aec_gpu_ichunks_plan {
+    uint64_t taken;          /* streams the every-bit scheme takes */
+    uint64_t rounds;         /* rounds they make */
+    uint64_t table_bits;     /* table entries of the largest round */
+    uint64_t rsi_entries;    /* the table's entries (= aec_gpu_dchunks_plan.rsi_entries) */
+    size_t   workspace_bytes;/* what the index-table buffer of the context holds for the pass (0: the walk alone) */
+} aec_gpu_ichunks_plan;
+AEC_GPU_API void aec_gpu_set_chunks_index(aec_gpu_ctx *ctx, int how, uint64_t round_bits);
+AEC_GPU_API int aec_gpu_index_chunks_plan(const aec_gpu_params *p, int how, uint64_t round_bits, const uint64_t *in_bytes_each,
+                                          const uint64_t *out_bytes, uint64_t n_chunks, aec_gpu_ichunks_plan *plan);
+AEC_GPU_API int aec_gpu_index_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                                           const uint64_t *in_offsets, const uint64_t *in_bytes_each, const uint64_t *out_bytes,
+                                           uint64_t n_chunks, uint64_t *d_rsi_bit_offsets, aec_gpu_dec_result *d_results,
+                                           uint32_t *d_how, void *stream);
 
 /*
  * Which block size?  The exact length of the stream that in_bytes at d_in (16-byte aligned, as for aec_gpu_encode_async)

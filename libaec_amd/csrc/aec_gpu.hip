@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <new>
+#include <vector>
 
 #include "../../include/aec_gpu.h"
 #include "aec_cfg.h"
@@ -12,6 +13,7 @@
 
 #include "aec_chunks.h"
 #include "aec_dchunks.h"
+#include "aec_bsmall.h"
 #include "aec_devbuf.h"
 #include "aec_est.h"
 #include "aec_kernels.h"
@@ -41,6 +43,8 @@ struct aec_gpu_ctx {
     uint64_t idx_used_hint = 0;  // ... and what the last index pass worked with (sizes the rings of the decode behind it)
     bool seg_filled = false;   // the last index pass with a segment-start table filled it (it ran over the trunk tables)
     uint64_t idx_stop_near = 0;  // the next index pass is a piece of a longer stream (aec_gpu_set_index_piece)
+    int chunks_index = BS_PLANNED;   // how the bare chunk index passes run (aec_gpu_set_chunks_index) ...
+    uint64_t chunks_round_bits = 0;  // ... and the budget of a round of the every-bit scheme (0: the default)
 
     // Device memory, grown on demand (aec_devbuf.h: replace) and kept between calls:
     DevBuf ws;             // workspace of the two-pass encoder (plan / emit: per-block summaries, segment scan)
@@ -454,6 +458,11 @@ int aec_gpu_decode_bare_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const v
 
 void aec_gpu_set_index_hint(aec_gpu_ctx *ctx, uint64_t rsi_bits) { ctx->idx_hint = rsi_bits; }
 void aec_gpu_set_index_piece(aec_gpu_ctx *ctx, uint64_t stop_near_bits) { ctx->idx_stop_near = stop_near_bits; }
+void aec_gpu_set_chunks_index(aec_gpu_ctx *ctx, int how, uint64_t round_bits)
+{
+    ctx->chunks_index = (how == AEC_GPU_CHUNKS_INDEX_SERIAL || how == AEC_GPU_CHUNKS_INDEX_EVERY_BIT) ? how : AEC_GPU_CHUNKS_INDEX_PLANNED;
+    ctx->chunks_round_bits = round_bits;
+}
 
 int aec_gpu_index_is_windowed(const aec_gpu_params *p, size_t in_bytes, uint64_t rsi_bits)
 {
@@ -828,6 +837,104 @@ int aec_gpu_decode_chunks_plan(const aec_gpu_params *p, const uint64_t *out_byte
     return 1;
 }
 
+// ---- the index pass of a batch of bare chunks (aec_bsmall.h; aec_idx.hip: launch_index_chunks) ----------------------------
+namespace {
+// What the pass of a batch needs beyond the chunk descriptors: the plan, its rounds, and -- behind the descriptors in the
+// pinned buffer -- the slots and the unit table as they lie in the workspace from plan.o_slots on.
+struct BareIndex {
+    BsPlan plan{};
+    std::vector<BsRound> rounds;
+    size_t h_bytes = 0;
+};
+bool bare_index_plan(const Cfg &c, int how, uint64_t round_bits, const uint64_t *in_bytes_each, const uint64_t *out_bytes, uint64_t n,
+                     BareIndex *b)
+{
+    // (the plan of a batch whose longest chunk the walker is through in the time of one round of the every-bit scheme takes
+    // none -- bs_plan says so after a pass over the chunks that divides; here from the largest out_bytes alone: thousands
+    // of small chunks are a call of a third of a millisecond, and the host's passes come in front of it)
+    if (how == BS_PLANNED) {
+        uint64_t most = 0;
+        for (uint64_t i = 0; i < n; i++) most = out_bytes[i] > most ? out_bytes[i] : most;
+        if ((most / c.bytes + c.bs - 1) / c.bs * kBsWalkNsPerBlock <= kBsFixedNs + kBsRoundNs) how = BS_SERIAL;
+    }
+    bs_plan(c, how, round_bits, in_bytes_each, out_bytes, n, &b->plan);
+    b->h_bytes = b->plan.taken ? b->plan.o_e - b->plan.o_slots : 0;
+    try {
+        b->rounds.resize(b->plan.rounds);
+    } catch (...) {
+        return false;
+    }
+    return true;
+}
+// Writes slots and unit table to h (h_bytes of the pinned buffer), makes room in the context's index-table buffer and
+// enqueues their copy.  The workspace, or null: no memory, or a plan that takes none -- the serial walk alone then.
+uint8_t *bare_index_send(aec_gpu_ctx *ctx, const Cfg &c, const uint64_t *in_offsets, const uint64_t *in_bytes_each, const uint64_t *out_bytes,
+                         uint64_t n, BareIndex *b, uint8_t *h, hipStream_t st)
+{
+    const BsPlan &pl = b->plan;
+    if (!pl.taken) return nullptr;
+    BsPlan again{};
+    bs_pack(c, bs_round_bits(ctx->chunks_round_bits), in_offsets, in_bytes_each, out_bytes, n, pl.min_blocks, &again,
+            reinterpret_cast<BsSlot *>(h), b->rounds.data(), reinterpret_cast<uint32_t *>(h + (pl.o_units - pl.o_slots)));
+    if (!ctx->idx_ws.replace(pl.bytes, pl.bytes)) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    uint8_t *ws = static_cast<uint8_t *>(ctx->idx_ws.p);
+    if (hipMemcpyAsync(ws + pl.o_slots, h, b->h_bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return ws;
+}
+}  // namespace
+
+int aec_gpu_index_chunks_plan(const aec_gpu_params *p, int how, uint64_t round_bits, const uint64_t *in_bytes_each,
+                              const uint64_t *out_bytes, uint64_t n_chunks, aec_gpu_ichunks_plan *plan)
+{
+    DChunksShape sh;
+    if (!p || !plan || (n_chunks && !in_bytes_each) || !dchunks_shape(p, nullptr, nullptr, nullptr, out_bytes, n_chunks, &sh, nullptr))
+        return 0;
+    BsPlan b;
+    bs_plan(sh.c, how, round_bits, in_bytes_each, out_bytes, n_chunks, &b);
+    plan->taken = b.taken;
+    plan->rounds = b.rounds;
+    plan->table_bits = b.table_bits;
+    plan->rsi_entries = sh.entries;
+    plan->workspace_bytes = b.taken ? b.bytes : 0;
+    return 1;
+}
+
+int aec_gpu_index_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
+                               const uint64_t *in_offsets, const uint64_t *in_bytes_each, const uint64_t *out_bytes,
+                               uint64_t n_chunks, uint64_t *d_rsi_bit_offsets, aec_gpu_dec_result *d_results,
+                               uint32_t *d_how, void *stream)
+{
+    if (aec_gpu_check_params(p, 0) != RC_OK) return RC_CONF_ERROR;
+    if (n_chunks == 0) return RC_OK;
+    if (!out_bytes || !d_rsi_bit_offsets || !d_results || (reinterpret_cast<uintptr_t>(d_in) & 3u) || !in_offsets || !in_bytes_each)
+        return RC_CONF_ERROR;
+    for (uint64_t i = 0; i < n_chunks; i++)
+        if (in_offsets[i] > in_bytes || in_bytes_each[i] > in_bytes - in_offsets[i]) return RC_CONF_ERROR;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    Cfg c;
+    if (cfg_from(p, 0, false, &c) != RC_OK) return RC_CONF_ERROR;
+    BareIndex bi;
+    if (!bare_index_plan(c, ctx->chunks_index, ctx->chunks_round_bits, in_bytes_each, out_bytes, n_chunks, &bi)) return RC_MEM_ERROR;
+    const size_t h_desc = ((size_t)(n_chunks + 1) * sizeof(DChunkDesc) + 15) & ~(size_t)15;
+    aec_gpu_ctx::ChunkStage *stage = stage_descriptors(ctx, h_desc + bi.h_bytes);
+    if (!stage) return RC_MEM_ERROR;
+    DChunksShape sh;
+    if (!dchunks_shape(p, in_offsets, in_bytes_each, nullptr, out_bytes, n_chunks, &sh, static_cast<DChunkDesc *>(stage->h.p)))
+        return RC_CONF_ERROR;
+    uint8_t *ws = bare_index_send(ctx, sh.c, in_offsets, in_bytes_each, out_bytes, n_chunks, &bi, static_cast<uint8_t *>(stage->h.p) + h_desc, st);
+    uint8_t *cd = send_descriptors(ctx->chunks_d, stage, h_desc, sh.desc_bytes, st);
+    if (!cd) return RC_MEM_ERROR;
+    launch_index_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, reinterpret_cast<const DChunkDesc *>(cd), n_chunks,
+                        d_rsi_bit_offsets, rec(d_results), st, &bi.plan, bi.rounds.data(), ws, d_how);
+    return launched();
+}
+
 int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const void *d_in, size_t in_bytes,
                                 const uint64_t *in_offsets, const uint64_t *in_bytes_each, const uint64_t *out_offsets,
                                 const uint64_t *out_bytes, uint64_t n_chunks, uint64_t *d_rsi_bit_offsets, int have_table,
@@ -844,12 +951,21 @@ int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
     }
     const hipStream_t st = static_cast<hipStream_t>(stream);
 
-    const size_t h_need = (size_t)(n_chunks + 1) * sizeof(DChunkDesc);
-    aec_gpu_ctx::ChunkStage *stage = stage_descriptors(ctx, h_need);
+    BareIndex bi;
+    if (!have_table) {
+        Cfg c;
+        if (cfg_from(p, 0, false, &c) != RC_OK) return RC_CONF_ERROR;
+        if (!bare_index_plan(c, ctx->chunks_index, ctx->chunks_round_bits, in_bytes_each, out_bytes, n_chunks, &bi)) return RC_MEM_ERROR;
+    }
+    const size_t h_need = (size_t)(n_chunks + 1) * sizeof(DChunkDesc), h_desc = (h_need + 15) & ~(size_t)15;
+    aec_gpu_ctx::ChunkStage *stage = stage_descriptors(ctx, h_desc + bi.h_bytes);
     if (!stage) return RC_MEM_ERROR;
     DChunksShape sh;
     if (!dchunks_shape(p, in_offsets, in_bytes_each, out_offsets, out_bytes, n_chunks, &sh, static_cast<DChunkDesc *>(stage->h.p)))
         return RC_CONF_ERROR;
+    uint8_t *iws = have_table ? nullptr
+                              : bare_index_send(ctx, sh.c, in_offsets, in_bytes_each, out_bytes, n_chunks, &bi,
+                                                static_cast<uint8_t *>(stage->h.p) + h_desc, st);
     uint8_t *cd = send_descriptors(ctx->chunks_d, stage, h_need, sh.desc_bytes + sh.table_bytes, st);
     if (!cd) return RC_MEM_ERROR;
     const DChunkDesc *d_desc = reinterpret_cast<const DChunkDesc *>(cd);
@@ -857,7 +973,8 @@ int aec_gpu_decode_chunks_async(aec_gpu_ctx *ctx, const aec_gpu_params *p, const
     DecResult *records = rec(d_results);
     launch_dchunks_setup(sh.c, d_desc, n_chunks, sh.items, d_item_chunk, have_table ? records : nullptr, st);
     if (!have_table)
-        launch_index_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_desc, n_chunks, d_rsi_bit_offsets, records, st);
+        launch_index_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_desc, n_chunks, d_rsi_bit_offsets, records, st,
+                            &bi.plan, bi.rounds.data(), iws, nullptr);
     // (bits per coded data set, from what the chunks announce: sizes the rings of the lane kernel)
     const uint64_t avg = sh.blocks ? (uint64_t)in_bytes * 8 / sh.blocks : 0;
     if (!launch_decode_chunks(sh.c, static_cast<const uint8_t *>(d_in), in_bytes, d_rsi_bit_offsets, d_desc, d_item_chunk,

@@ -38,6 +38,7 @@
 #include "aec_coop.h"
 #include "aec_stretch.h"
 #include "aec_small.h"
+#include "aec_bsmall.h"
 #include "aec_tune.h"
 
 namespace aec {
@@ -2389,7 +2390,9 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
         uint32_t serial_cap = 0, uint32_t *__restrict__ delivered = nullptr,
         const DChunkDesc *__restrict__ streams = nullptr)
 {
-    if (skip_if && *skip_if) return;                 // (the phase-locked chains have delivered everything: launch_index_locked)
+    // (a batch of unequal chunks: skip_if has a flag per STREAM -- the every-bit scheme over the batch in front has delivered
+    // that stream: launch_index_chunks)
+    if (skip_if && skip_if[streams ? blockIdx.x : 0u]) return;                 // (the phase-locked chains have delivered everything: launch_index_locked)
     // serial_cap / delivered (launch_index_sparse, a small stream in one span): the tables resolve most RSIs of the streams
     // they are made for and next to none of others -- very compressible data, runs of zero blocks -- and this walk is
     // then 50 ns per block on ONE wavefront (16 MiB of 12-bit data in blocks of 8: 54 ms).  After serial_cap blocks
@@ -3188,7 +3191,7 @@ void side_give(const SideStream &s)
 
 // What a launch of the walker has beyond the walk itself (IdxWalk), filled by name; as it stands: the plain serial walk.
 struct IdxVary {
-    const uint32_t *skip_if = nullptr;
+    const uint32_t *skip_if = nullptr;     // (with streams: a flag per stream)
     const uint64_t *chunk_off = nullptr;   // a batch: n_chunks + 1 byte offsets, a workgroup per stream
     const DChunkDesc *streams = nullptr;   // a batch of unequal chunks: n_chunks descriptors, a workgroup per stream
     uint64_t n_chunks = 1, stop_near = 0;
@@ -5489,6 +5492,103 @@ static void launch_index_small(const IdxWalk &w, const SmallPlan &p, uint8_t *ba
     go_index(w, {.skip_if = flags});
 }
 
+// ---- the same scheme over a BATCH of bare streams (aec_bsmall.h: slots, rounds, the verdict) ------------------------
+// One set of launches per round serves all its streams: a workgroup reads its stream's slot through the unit table, the
+// entry it computes is aec_bsmall.h's.  No cursor and no pieces: a stream is one slot.
+static_assert(kBsUnit == kSmRsiWg && kBsMaxBits == kSmMaxBits, "a workgroup of the widest kernel lies inside one slot");
+struct BsTables {
+    const BsSlot *slots;
+    const uint32_t *units;       // the round's part of the unit table
+    uint16_t *e0, *e1;
+    uint32_t *ja, *jb, *hop, *sidx;
+};
+
+__global__ void __launch_bounds__(256)
+k_bsmall_parse(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, const BsTables t)
+{
+    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
+    const BsSlot sl = t.slots[t.units[at / kBsUnit]];
+    const uint32_t q = at - sl.t0;
+    if (q <= sl.nbits) bs_parse_entry(c, words, nwords, sl, q, t.e0, t.e1);
+}
+
+__global__ void __launch_bounds__(256)
+k_bsmall_hop(const Cfg c, const BsTables t)
+{
+    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
+    const BsSlot sl = t.slots[t.units[at / kBsUnit]];
+    const uint32_t q = at - sl.t0;
+    const uint16_t *e0 = t.e0 + sl.t0;
+    if (q <= sl.nbits) t.hop[at] = sm_hop(c, [&](uint32_t p) { return (uint32_t)e0[p]; }, q, sl.nbits);
+}
+
+// (staged in LDS as k_small_rsi stages it: the stretch is one stream's, since the workgroup is)
+__global__ void __launch_bounds__(kSmRsiWg)
+k_bsmall_rsi(const Cfg c, const BsTables t, uint32_t hops)
+{
+    __shared__ uint32_t lds[kSmRsiWg + kSmRsiSpan];
+    const BsSlot sl = t.slots[t.units[blockIdx.x]];
+    const uint32_t w0 = blockIdx.x * kSmRsiWg - sl.t0, q = w0 + threadIdx.x, nbits = sl.nbits;
+    const uint16_t *e0 = t.e0 + sl.t0, *e1 = t.e1 + sl.t0;
+    const uint32_t *hop = hops ? t.hop + sl.t0 : nullptr;
+    bs_chain_init(sl, q, t.sidx);
+    const uint32_t wn = w0 > nbits ? 0u : (nbits + 1u - w0 < kSmRsiWg + kSmRsiSpan ? nbits + 1u - w0 : kSmRsiWg + kSmRsiSpan);
+    for (uint32_t i = threadIdx.x; i < wn; i += kSmRsiWg)
+        lds[i] = hop ? hop[w0 + i] : ((uint32_t)e0[w0 + i] | ((uint32_t)e1[w0 + i] << 16));
+    __syncthreads();
+    if (q > nbits) return;
+    auto r0 = [&](uint32_t at) { return (!hop && at - w0 < wn) ? (lds[at - w0] & 0xFFFFu) : (uint32_t)e0[at]; };
+    auto r1 = [&](uint32_t at) { return (!hop && at - w0 < wn) ? (lds[at - w0] >> 16) : (uint32_t)e1[at]; };
+    auto rh = [&](uint32_t at) { return at - w0 < wn ? lds[at - w0] : hop[at]; };
+    auto rh2 = [&](uint32_t) { return 0u; };
+    t.ja[sl.t0 + q] = sm_rsi(c, r0, r1, rh, hop != nullptr, rh2, false, q, nbits, 0u, bs_pad(c));
+}
+
+// doubling round k of the streams whose chains need it (a chunk of one RSI beside a chunk of a thousand)
+__global__ void __launch_bounds__(256)
+k_bsmall_double(const BsTables t, uint32_t k)
+{
+    const uint32_t at = blockIdx.x * 256u + threadIdx.x;
+    const BsSlot sl = t.slots[t.units[at / kBsUnit]];
+    bs_double_entry(sl, k, at - sl.t0, (k & 1u) ? t.jb : t.ja, (k & 1u) ? t.ja : t.jb, t.sidx);
+}
+
+// a workgroup per stream: the verdict, then -- for a stream that is delivered -- its RSI starts as absolute bits from
+// table entry item0 + chunk on, its record as the walker writes it, and its flag; every other stream stays untouched
+__global__ void __launch_bounds__(256)
+k_bsmall_finish(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, const DChunkDesc *__restrict__ desc,
+                const BsTables t, uint64_t slot0, uint64_t *__restrict__ rsi_off, DecResult *__restrict__ res,
+                uint32_t *__restrict__ done)
+{
+    __shared__ uint32_t first_none;
+    __shared__ BsVerdict verdict;
+    const BsSlot sl = t.slots[slot0 + blockIdx.x];
+    const uint32_t *s = t.sidx + sl.s0;
+    if (threadIdx.x == 0) first_none = sl.scap;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < sl.scap; i += 256u)
+        if (s[i] == kSmNone) {
+            atomicMin(&first_none, i);
+            break;
+        }
+    __syncthreads();
+    if (threadIdx.x == 0) verdict = bs_finish(c, QuadFetch{words, nwords}, sl, t.sidx, first_none);
+    __syncthreads();
+    const BsVerdict v = verdict;
+    if (!v.delivered) return;
+    uint64_t *out = rsi_off + desc[sl.chunk].item0 + sl.chunk;
+    for (uint64_t i = threadIdx.x; i < v.nout; i += 256u) out[i] = 8u * sl.in_off + s[i];
+    if (threadIdx.x != 0) return;
+    DecResult *r = res + sl.chunk;
+    r->n_rsi = v.n_rsi;
+    r->tail_blocks = v.tail_blocks;
+    r->end_bit = v.end_bit;
+    r->status = DEC_OK;
+    r->pad = 0u;
+    r->bad_rsi = ~0ull;
+    done[sl.chunk] = 1u;
+}
+
 }  // namespace
 
 // (tuning build: the A/B switches that live in device globals)
@@ -5753,17 +5853,46 @@ void launch_index_batch(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
                        (const IdxCarry *)nullptr, hops, nhops, (uint32_t)n_chunks, hop_cap, d_rsi_off, rsi_per_chunk);
 }
 
-// The bare streams of a batch of unequal chunks (aec_dchunks.h): one wavefront per stream, the serial walk alone, from
-// the stream's first byte to its last; chunk s's RSI starts go to the table from entry d_desc[s].item0 + s on, its
-// record to d_res[s].
+// The bare streams of a batch of unequal chunks (aec_dchunks.h).  The streams the plan takes (aec_bsmall.h: bs_plan; slots,
+// unit table and rounds written by the caller, the former two at plan->o_slots / o_units of ws) go through the every-bit
+// scheme, round after round, all launches enqueued at once; the serial walker behind them -- one wavefront per stream,
+// from the stream's first byte to its last -- walks exactly the streams that scheme has not marked delivered: those it
+// does not take and those it gives up.  Chunk s's RSI starts go to the table from entry d_desc[s].item0 + s on, its
+// record to d_res[s]; d_how[s] (optional): 1 = delivered by the every-bit scheme, 0 = by the walker.
+// plan == nullptr, or a plan that takes none: the serial walk alone.
 void launch_index_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DChunkDesc *d_desc, uint64_t n_chunks,
-                         uint64_t *d_rsi_off, DecResult *d_res, hipStream_t st)
+                         uint64_t *d_rsi_off, DecResult *d_res, hipStream_t st, const BsPlan *plan, const BsRound *rounds,
+                         uint8_t *ws, uint32_t *d_how)
 {
     if (n_chunks == 0) return;
     idx_tuning_sync();
     const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, 0, d_rsi_off,
                     0, d_res, st, 0u, 0u, 0, nullptr, 0};
-    go_index(w, {.streams = d_desc, .n_chunks = n_chunks});
+    const bool every_bit = plan && rounds && ws && plan->taken;
+    uint32_t *done = d_how ? d_how : (every_bit ? reinterpret_cast<uint32_t *>(ws + plan->o_flags) : nullptr);
+    if (done) (void)hipMemsetAsync(done, 0, (size_t)n_chunks * 4, st);
+    if (every_bit) {
+        const uint32_t hops = c.rsi > kBsHopRsi ? 1u : 0u;
+        for (uint64_t r = 0; r < plan->rounds; r++) {
+            const BsRound &rd = rounds[r];
+            const BsTables t{reinterpret_cast<const BsSlot *>(ws + plan->o_slots),
+                             reinterpret_cast<const uint32_t *>(ws + plan->o_units) + rd.unit0,
+                             reinterpret_cast<uint16_t *>(ws + plan->o_e),
+                             reinterpret_cast<uint16_t *>(ws + plan->o_e) + plan->table_bits,
+                             reinterpret_cast<uint32_t *>(ws + plan->o_ja),
+                             reinterpret_cast<uint32_t *>(ws + plan->o_e),
+                             reinterpret_cast<uint32_t *>(ws + plan->o_hop),
+                             reinterpret_cast<uint32_t *>(ws + plan->o_sidx)};
+            hipLaunchKernelGGL(k_bsmall_parse, dim3(rd.entries / 256u), dim3(256), 0, st, c, w.words, w.nwords, t);
+            if (hops) hipLaunchKernelGGL(k_bsmall_hop, dim3(rd.entries / 256u), dim3(256), 0, st, c, t);
+            hipLaunchKernelGGL(k_bsmall_rsi, dim3(rd.entries / kSmRsiWg), dim3(kSmRsiWg), 0, st, c, t, hops);
+            for (uint32_t k = 0; k < rd.levels; k++)
+                hipLaunchKernelGGL(k_bsmall_double, dim3(rd.entries / 256u), dim3(256), 0, st, t, k);
+            hipLaunchKernelGGL(k_bsmall_finish, dim3((uint32_t)rd.nslots), dim3(256), 0, st, c, w.words, w.nwords, d_desc, t,
+                               rd.slot0, d_rsi_off, d_res, done);
+        }
+    }
+    go_index(w, {.skip_if = every_bit ? done : nullptr, .streams = d_desc, .n_chunks = n_chunks});
 }
 
 }  // namespace aec

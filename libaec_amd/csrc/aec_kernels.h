@@ -153,8 +153,12 @@ bool launch_decode_range(const Cfg &c, const uint8_t *d_in, size_t in_bytes, con
 struct DChunkDesc;
 void launch_dchunks_setup(const Cfg &c, const DChunkDesc *d_desc, uint64_t n, uint64_t items, uint32_t *d_item_chunk,
                           DecResult *d_records, hipStream_t stream);
+// (plan, rounds, ws: the every-bit scheme over the batch in front of the walker, aec_bsmall.h; d_how: who delivered a stream)
+struct BsPlan;
+struct BsRound;
 void launch_index_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const DChunkDesc *d_desc, uint64_t n_chunks,
-                         uint64_t *d_rsi_off, DecResult *d_res, hipStream_t stream);
+                         uint64_t *d_rsi_off, DecResult *d_res, hipStream_t stream, const BsPlan *plan = nullptr,
+                         const BsRound *rounds = nullptr, uint8_t *ws = nullptr, uint32_t *d_how = nullptr);
 bool launch_decode_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, const uint64_t *d_rsi_off,
                           const DChunkDesc *d_desc, const uint32_t *d_item_chunk, uint64_t items, uint64_t avg_cds_hint,
                           uint8_t *d_out, DecResult *d_records, DecResult *d_res, hipStream_t stream,

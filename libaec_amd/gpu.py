@@ -25,6 +25,14 @@ class DChunksPlan(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+class IChunksPlan(C.Structure):
+    _fields_ = [("taken", C.c_uint64), ("rounds", C.c_uint64), ("table_bits", C.c_uint64), ("rsi_entries", C.c_uint64),
+                ("workspace_bytes", C.c_size_t)]
+
+
+CHUNKS_INDEX_PLANNED, CHUNKS_INDEX_SERIAL, CHUNKS_INDEX_EVERY_BIT = 0, 1, 2
+
+
 class Estimate(C.Structure):
     """aec_gpu_estimate: total_bits per block size 8, 16, 32, 64 (~0: not asked for) and the index of the smallest"""
     _fields_ = [("total_bits", C.c_uint64 * 4), ("best", C.c_uint32), ("pad", C.c_uint32)]
@@ -101,6 +109,13 @@ def _lib():
             lib.aec_gpu_decode_chunks_plan.argtypes = [pp, vp, u64, C.POINTER(DChunksPlan)]
             lib.aec_gpu_decode_chunks_async.restype = C.c_int
             lib.aec_gpu_decode_chunks_async.argtypes = [vp, pp, vp, sz, vp, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp]
+        if hasattr(lib, "aec_gpu_index_chunks_async"):      # (AEC_AMD_LIB: a build from before the call)
+            lib.aec_gpu_set_chunks_index.restype = None
+            lib.aec_gpu_set_chunks_index.argtypes = [vp, C.c_int, u64]
+            lib.aec_gpu_index_chunks_plan.restype = C.c_int
+            lib.aec_gpu_index_chunks_plan.argtypes = [pp, C.c_int, u64, vp, vp, u64, C.POINTER(IChunksPlan)]
+            lib.aec_gpu_index_chunks_async.restype = C.c_int
+            lib.aec_gpu_index_chunks_async.argtypes = [vp, pp, vp, sz, vp, vp, vp, u64, vp, vp, vp, vp]
         if hasattr(lib, "aec_gpu_estimate_async"):          # (AEC_AMD_LIB: a build from before the call)
             lib.aec_gpu_estimate_plan.restype = C.c_int
             lib.aec_gpu_estimate_plan.argtypes = [pp, C.POINTER(C.c_uint), sz, C.POINTER(EstimatePlan)]
@@ -200,6 +215,23 @@ def decode_chunks_plan(bits_per_sample, block_size, rsi, flags, out_sizes):
             "workspace_bytes": int(plan.workspace_bytes)}
 
 
+def index_chunks_plan(bits_per_sample, block_size, rsi, flags, in_sizes, out_sizes, how=CHUNKS_INDEX_PLANNED, round_bits=0):
+    """aec_gpu_index_chunks_plan: host arithmetic of the index pass of a batch of bare streams of `in_sizes` bytes that
+    decode to `out_sizes` bytes, run as `how` (CHUNKS_INDEX_*) with rounds of `round_bits` table entries (0: the default).
+    Returns the dict {taken, rounds, table_bits, rsi_entries, workspace_bytes}, or None where the batch would be refused."""
+    p = Params(bits_per_sample, block_size, rsi, flags)
+    a = np.ascontiguousarray(in_sizes, dtype=np.uint64)
+    b = np.ascontiguousarray(out_sizes, dtype=np.uint64)
+    if a.size != b.size:
+        raise ValueError("in_sizes and out_sizes differ in length")
+    plan = IChunksPlan()
+    if not _lib().aec_gpu_index_chunks_plan(C.byref(p), int(how), int(round_bits), C.c_void_p(a.ctypes.data),
+                                            C.c_void_p(b.ctypes.data), a.size, C.byref(plan)):
+        return None
+    return {"taken": int(plan.taken), "rounds": int(plan.rounds), "table_bits": int(plan.table_bits),
+            "rsi_entries": int(plan.rsi_entries), "workspace_bytes": int(plan.workspace_bytes)}
+
+
 def _rsi4(rsi):
     """the four RSIs of an estimate as the C array; None stays NULL (the parameter set's rsi for all four sizes)"""
     if rsi is None:
@@ -275,6 +307,18 @@ class Codec:
         rc = self.lib.aec_gpu_reserve(self.ctx, C.byref(self.p), in_bytes)
         if rc != 0:
             raise MemoryError(f"aec_gpu_reserve({in_bytes}) failed ({rc})")
+
+    def held_bytes(self):
+        """aec_gpu_held_bytes: device memory the context holds between calls"""
+        self.lib.aec_gpu_held_bytes.restype = C.c_size_t
+        self.lib.aec_gpu_held_bytes.argtypes = [C.c_void_p]
+        return int(self.lib.aec_gpu_held_bytes(self.ctx))
+
+    def trim(self, keep_bytes=0):
+        """aec_gpu_trim: release every buffer of the context above keep_bytes (synchronises the device)"""
+        self.lib.aec_gpu_trim.restype = None
+        self.lib.aec_gpu_trim.argtypes = [C.c_void_p, C.c_size_t]
+        self.lib.aec_gpu_trim(self.ctx, keep_bytes)
 
     def _stream(self, stream):
         return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
@@ -471,6 +515,51 @@ class Codec:
         rec = d_rec.cpu().numpy().view(DEC_RESULT_DTYPE)[:n]
         res = d_res.cpu().numpy().view(DEC_RESULT_DTYPE)[0]
         return d_out[: plan["out_bytes"]], ooff, rec, res
+
+    def set_chunks_index(self, how=CHUNKS_INDEX_PLANNED, round_bits=0):
+        """aec_gpu_set_chunks_index: how the bare chunk index passes of this context run (CHUNKS_INDEX_*), and the budget
+        of a round of the every-bit scheme in table entries (0: the default)"""
+        self._chunks_index = (int(how), int(round_bits))
+        self.lib.aec_gpu_set_chunks_index(self.ctx, int(how), int(round_bits))
+
+    def index_chunks_plan(self, in_sizes, out_sizes, how=None, round_bits=None):
+        """index_chunks_plan for this codec's parameters; how / round_bits default to what set_chunks_index was given"""
+        cur = getattr(self, "_chunks_index", (CHUNKS_INDEX_PLANNED, 0))
+        return index_chunks_plan(self.p.bits_per_sample, self.p.block_size, self.p.rsi, self.p.flags, in_sizes, out_sizes,
+                                 cur[0] if how is None else how, cur[1] if round_bits is None else round_bits)
+
+    def index_chunks_async(self, d_in, in_bytes, in_offsets, in_sizes, out_sizes, d_table, d_records, d_how=None, stream=None):
+        """aec_gpu_index_chunks_async as it is: the three arrays are uint64 numpy arrays on the host, d_table an int64
+        tensor of the plan's rsi_entries, d_records a uint8 tensor of 40 n bytes, d_how an int32 tensor of n entries or
+        None.  Returns the call's return code."""
+        return self.lib.aec_gpu_index_chunks_async(
+            self.ctx, C.byref(self.p), _ptr(d_in), in_bytes, C.c_void_p(in_offsets.ctypes.data),
+            C.c_void_p(in_sizes.ctypes.data), C.c_void_p(out_sizes.ctypes.data), int(out_sizes.size), _ptr(d_table),
+            _ptr(d_records), _ptr(d_how), self._stream(stream))
+
+    def index_chunks(self, d_in, in_bytes, out_sizes, in_offsets, in_sizes):
+        """The index pass of a batch of bare streams (in_sizes[i] bytes at byte in_offsets[i] of d_in, decoding to
+        out_sizes[i] bytes).  Returns (d_table, records, how): the int64 RSI table on the device in the layout
+        decode_chunks takes as d_table, the DEC_RESULT_DTYPE record per stream, and per stream 1 where the every-bit scheme
+        delivered it, 0 where the serial walker did.  Synchronises."""
+        torch = self.torch
+        osz = np.ascontiguousarray(out_sizes, dtype=np.uint64)
+        ioff = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+        isz = np.ascontiguousarray(in_sizes, dtype=np.uint64)
+        n = int(osz.size)
+        if ioff.size != n or isz.size != n:
+            raise ValueError("in_offsets, in_sizes and out_sizes differ in length")
+        plan = self.index_chunks_plan(isz, osz)
+        if plan is None:
+            raise ValueError("aec_gpu_index_chunks_plan refuses this batch")
+        d_table = torch.zeros(max(plan["rsi_entries"], 1), dtype=torch.int64, device=d_in.device)
+        d_rec = torch.zeros(max(n, 1) * DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=d_in.device)
+        d_how = torch.zeros(max(n, 1), dtype=torch.int32, device=d_in.device)
+        rc = self.index_chunks_async(d_in, in_bytes, ioff, isz, osz, d_table, d_rec, d_how)
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_index_chunks_async failed ({rc})")
+        rec = d_rec.cpu().numpy().view(DEC_RESULT_DTYPE)[:n]
+        return d_table, rec, d_how.cpu().numpy()[:n]
 
     # ---- convenience (synchronising) -------------------------------------------------------------
     def encode(self, d_in, start_bit=0, k_in=0):

@@ -296,6 +296,10 @@ class SzCodec:
         self.lib.aec_gpu_trim.argtypes = [C.c_void_p, C.c_size_t]
         self.lib.aec_gpu_trim(self.ctx, keep_bytes)
 
+    def set_chunks_index(self, how=gpu.CHUNKS_INDEX_PLANNED, round_bits=0):
+        """aec_gpu_set_chunks_index on this codec's context: how decompress_chunks without a table finds the RSI starts"""
+        gpu._lib().aec_gpu_set_chunks_index(self.ctx, int(how), int(round_bits))
+
     def compress_chunks(self, d_src, src_offsets, sizes, want_table=False):
         """chunks of sizes[i] bytes at d_src[src_offsets[i]:] -> (d_out, records, d_table, d_work): stream i is
         d_out[records[i]["base_bits"] // 8 :][: (records[i]["bits"] + 7) // 8], what SZ_BufftoBuffCompress gives for
