@@ -118,6 +118,11 @@ __device__ __forceinline__ uint64_t wave_get64(uint64_t v, uint32_t l)
     const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, (int)l);
     return (uint64_t)hi << 32 | lo;
 }
+// `v` with lane l's value replaced by `x`
+__device__ __forceinline__ uint32_t wave_set_lane(uint32_t v, uint32_t lane, uint32_t l, uint32_t x)
+{
+    return lane == l ? x : v;
+}
 
 __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, uint32_t)
 {
@@ -1427,6 +1432,42 @@ __device__ __forceinline__ void emit_segment(const Cfg &c, const Seg &g, const u
         const bool emits = valid && opt != OPT_ZCONT;
         const uint32_t ref = (pp && g.b0 == 0 && lane == 0) ? 1u : 0u;
         const uint32_t karg = opt == OPT_ZERO ? meta_a(m) : k;
+        constexpr bool PAIRS = BS > 0 && BS <= 16 && Rows<BS, BYTES>::HALF;
+        if (PAIRS) {
+            // small blocks of 16-bit residuals: emitted from the sample pairs as they are, one placement a block
+            // (aec_lane.h emit_small_pairs); the few lanes that are not eligible unpack them for emit_block
+            constexpr int NW = PAIRS ? BS / 2 : 1;
+            uint32_t pw[NW];
+            if (direct) {
+#pragma unroll
+                for (int j = 0; j < NW; j++) pw[j] = direct[j];
+            } else {
+                const uint32_t *row = rows + (valid ? lane : 0u) * stride;
+#pragma unroll
+                for (int q = 0; q < NW / 4; q++) {
+                    const uint4 t = *reinterpret_cast<const uint4 *>(row + 4 * q);
+                    pw[4 * q] = t.x; pw[4 * q + 1] = t.y; pw[4 * q + 2] = t.z; pw[4 * q + 3] = t.w;
+                }
+            }
+            LdsSink sink{obuf};
+            uint32_t ubits = 0, fbits = 0;
+            const bool small = emits && pairs_eligible(c, bs, opt, karg, ref, len, ubits, fbits);
+            emit_small_pairs<(PAIRS ? BS : 8)>(sink, lead + excl, pw, c, opt, karg, ref, ref_sample, ubits, fbits, small);
+            if (__any(emits && !small)) {
+                if (emits && !small) {
+                    uint32_t dv[2 * NW];
+#pragma unroll
+                    for (int j = 0; j < NW; j++) {
+                        dv[2 * j] = pw[j] & 0xFFFFu;
+                        dv[2 * j + 1] = pw[j] >> 16;
+                    }
+                    BitWriter<LdsSink> bw(sink, lead + excl);
+                    emit_block<BS>(bw, dv, c, opt, karg, ref, ref_sample);
+                }
+            }
+            wave_lds_fence();
+            return;
+        }
         BlockRegs<BS, Rows<BS, BYTES>::HALF> regs;
         const uint32_t *d;
         uint32_t dv[BS ? BS : 1];
@@ -1509,8 +1550,10 @@ k_pack_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDesc 
 // where the guess made a block take another k than the true one (local_missed) -- the carry then comes from seg_kin,
 // the positions inside the slot from seg_start, and nothing is written but the slot, whose layout the carried k does
 // not move.
+// (The redo of blocks of 16 8-bit samples is told to stay at the seven waves per SIMD it had: left alone the allocator takes
+// 73 registers, one more than seven waves allow; with the hint 71, no scratch.  The other instantiations are not bound.)
 template <int BS, int BYTES, bool REDO>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REDO && BS == 16 && BYTES == 1 ? 7 : 1)))
 k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict__ seg_bits,
                uint16_t *__restrict__ seg_clamp, const uint8_t *__restrict__ seg_kin,
                const uint64_t *__restrict__ seg_start, const LocalLaunch l,
@@ -1533,6 +1576,8 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
     uint32_t pending = 0;        // open tail word of the previous segment
     uint32_t pos = 0;            // bits of the run so far = where the segment starts in the slot
     bool merge_tail = false;     // REDO: the last segment coded again ends in a word that goes on with an untouched one
+    const uint64_t run0 = sg;    // the run's first segment
+    uint32_t keep_bk = 0, keep_cf = 0;      // lane s: bits | k used << 24 and clamp | first clamp << 16 of segment run0 + s
     if (REDO) {
         bool miss = false;
         const uint64_t s = sg + lane;
@@ -1542,7 +1587,6 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
         // only the segments from the first to the last miss (aec_enc_local.h): positions from the scan, the open words
         // at both ends shared with what stays in the slot
         const LocalRedo range = local_redo_range(missed);
-        const uint64_t run0 = sg;
         merge_tail = run0 + range.end < sg_end;
         sg_end = run0 + range.end;
         sg = run0 + range.first;
@@ -1576,12 +1620,11 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
                 have_k = true;
             }
             kin = k;
-            if (lane == 0) {
-                seg_bits[sgi] = tot;
-                seg_clamp[sgi] = (uint16_t)cl;
-                l.seg_first[sgi] = (uint16_t)first;
-                l.seg_kused[sgi] = (uint8_t)kin;
-            }
+            // what the segment leaves for the scan and the redo: lane s keeps segment s of the run (all four are
+            // wave-uniform; a segment is less than 2^24 bits, a k less than 2^8), stored once behind the run
+            const uint32_t at = (uint32_t)(sgi - run0);
+            keep_bk = wave_set_lane(keep_bk, lane, at, tot | (kin << 24));
+            keep_cf = wave_set_lane(keep_cf, lane, at, (cl & 0xFFFFu) | (first << 16));
             k = kclamp_apply(clamp_unpack(cl), k);
         }
         const uint32_t lead = pos & 31u;
@@ -1607,12 +1650,20 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
     for (; sg < sg_end; sg++) {
         const auto cur = feeder.pre_direct;
         const Seg g = gnext;
+        const bool direct = feeder.direct_ok(c, g);
         uint32_t ref_sample = 0;
-        if (pp && g.b0 == 0 && lane == 0)
-            ref_sample = load_sample_bytes(in + g.samp0 * c.bytes, c.bytes, msb) & low_mask32(c.bps);
+        if (pp && g.b0 == 0) {
+            // the reference sample of an RSI is the first sample of lane 0's block: on the direct path from the words
+            // the lane holds (as load_sample_raw has it), else by a load of lane 0's own
+            constexpr uint32_t one = BYTES == 2 ? 0xFFFFu : 0xFFu;
+            if (direct)
+                ref_sample = __builtin_amdgcn_readfirstlane(sample_byte_order<BYTES>(cur.raw[0] & one, msb)) & low_mask32(c.bps);
+            else if (lane == 0)
+                ref_sample = load_sample_bytes(in + g.samp0 * c.bytes, c.bytes, msb) & low_mask32(c.bps);
+        }
         if (sg + 1 < sg_end) gnext = seg_next(c, gnext);
         feeder.prefetch_direct(c, in, gnext, lane);       // the next segment's loads fly during this one
-        if (feeder.direct_ok(c, g)) {
+        if (direct) {
             uint32_t w[BS / 2];
             direct_finish<BS, BYTES>(c, g, cur, lane, w);
             do_segment(g, ref_sample, sg, w);
@@ -1620,6 +1671,12 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
             feeder.feed_now(c, in, g, rows, stride, lane);
             do_segment(g, ref_sample, sg, nullptr);
         }
+    }
+    if (!REDO && run0 + lane < sg_end) {        // (a run is at most 32 segments: local_plan)
+        seg_bits[run0 + lane] = keep_bk & 0xFFFFFFu;
+        seg_clamp[run0 + lane] = (uint16_t)keep_cf;
+        l.seg_first[run0 + lane] = (uint16_t)(keep_cf >> 16);
+        l.seg_kused[run0 + lane] = (uint8_t)(keep_bk >> 24);
     }
 }
 

@@ -587,6 +587,101 @@ AEC_HD void emit_small(BitWriter<Sink> &w, const uint32_t *d, const Cfg &c, uint
     }
 }
 
+// The same for a block held as BS / 2 words of two 16-bit residuals each (sample 2j in the low half of w[j], what the
+// uint16 rows and direct_finish hold), placed as ONE value: header, unary region and field region are at most 128 bits
+// (pairs_eligible: header and unary region share 64 bits, which only a reference block with long codes misses -- it
+// goes through emit_block with the other lanes that are not eligible), shifted to the block's bit position with
+// straight-line code and ORed into three to five words of the image -- no flush test and no branch per put.
+//   * t + 1 of both halves by one packed shift and one packed add; the low half's shift count is that register
+//     itself (a 64-bit shift reads six bits, and an eligible block has no code of 64 bits and more); the low half's
+//     field is w & km, for km < 2^16.  Only the high halves are shifted down.
+//   * `word` + 2 stays inside the image for every eligible block: make_geom sizes it for 64 blocks of
+//     id_len + bs * bps + 2 + bps bits, 2 + bps more than any block takes.
+AEC_HD bool pairs_eligible(const Cfg &c, uint32_t bs, uint32_t opt, uint32_t k, uint32_t ref, uint32_t len,
+                           uint32_t &ubits, uint32_t &fbits)
+{
+    const bool small = small_eligible(c, bs, opt, k, ref, len, ubits, fbits);
+    const uint32_t head = c.id_len + (opt == OPT_SPLIT ? 0u : 1u) + ref * c.bps;
+    return small && head + ubits <= 64u;
+}
+
+// both 16-bit halves of w shifted right by the count in the halves of kk (the same count < 16 in both)
+AEC_HD uint32_t pair_shr(uint32_t w, uint32_t kk)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned short pair16 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(pair16, w) >> __builtin_bit_cast(pair16, kk));
+#else
+    const uint32_t k = kk & 15u;
+    return (((w >> 16) >> k) << 16) | ((w & 0xFFFFu) >> k);
+#endif
+}
+
+template <int BS, class Sink>
+AEC_HD void emit_small_pairs(Sink &sink, uint32_t pos, const uint32_t *w, const Cfg &c, uint32_t opt, uint32_t k_or_fs,
+                             uint32_t ref, uint32_t ref_sample, uint32_t ubits, uint32_t fbits, bool live)
+{
+    const bool is_split = live && opt == OPT_SPLIT, is_se = live && opt == OPT_SE;
+    const bool is_zero = live && opt == OPT_ZERO;
+    const uint32_t k = is_split ? k_or_fs : 0u;
+    const uint32_t km = low_mask32(k), kk = k * 0x00010001u;
+    // unary and field regions, right aligned, as emit_small builds them (lanes that are not split blocks on k = 0)
+    uint64_t ua = 0, fa = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < (uint32_t)BS / 2u; j++) {
+        const uint32_t t1 = pair_shr(w[j], kk) + 0x00010001u;      // t + 1 of both samples
+        const uint32_t hi = w[j] >> 16;
+        if (j == 0) {
+            ua = ref ? 0u : 1u;                          // only sample 0 can be the reference slot (skipped)
+            fa = ref ? 0u : (uint64_t)(w[0] & km);
+        } else {
+            ua = (ua << (t1 & 63u)) | 1u;
+            fa = (fa << k) | (w[j] & km);
+        }
+        ua = (ua << ((t1 >> 16) & 63u)) | 1u;
+        fa = (fa << k) | (hi & km);
+    }
+    if (!is_split) {
+        ua = is_zero ? 1u : 0u;
+        fa = 0;
+    }
+    if (AEC_ANY(is_se)) {
+#pragma unroll
+        for (uint32_t j = 0; j < (uint32_t)BS / 2u; j++) {
+            const uint32_t hi = w[j] >> 16, sum = (w[j] & 0xFFFFu) + hi;      // (< 2^17: a 24-bit multiply is exact)
+#if defined(__HIP_DEVICE_COMPILE__)
+            const uint32_t m = __umul24(sum, sum + 1u) / 2u + hi;
+#else
+            const uint32_t m = sum * (sum + 1u) / 2u + hi;
+#endif
+            ua = (ua << (is_se ? (m + 1u) & 63u : 0u)) | (is_se ? 1u : 0u);
+        }
+    }
+    if (!live) return;
+    // header (option id, low-entropy selector bit, reference sample) in front of the unary region: nb = 1 .. 64 bits
+    const uint32_t idv = is_split ? k + 1u : (is_se ? 1u : 0u);
+    const uint32_t idb = c.id_len + (is_split ? 0u : 1u);
+    const uint32_t hb = idb + (ref ? c.bps : 0u);
+    const uint64_t hdr = ref ? ((uint64_t)idv << c.bps) | ref_sample : (uint64_t)idv;
+    ua |= hdr << (ubits & 63u);                          // (ubits <= 63: hb >= 1 and hb + ubits <= 64)
+    const uint32_t nb = ubits + hb;
+    // the block's nb + fbits <= 128 bits, left aligned in hi : lo (fbits == 0: fa is 0)
+    const uint64_t a = ua << (64u - nb), f = fa << ((64u - fbits) & 63u);
+    const uint64_t hi = a | ((f >> 1) >> (nb - 1u)), lo = f << ((64u - nb) & 63u);
+    // ... and shifted to bit `pos` of the image: five words from word pos / 32 on
+    const uint32_t off = pos & 31u, word = pos >> 5, nw = (off + nb + fbits + 31u) >> 5;
+    const uint32_t w0 = (uint32_t)(hi >> 32), w1 = (uint32_t)hi, w2 = (uint32_t)(lo >> 32), w3 = (uint32_t)lo;
+    sink.or_word(word, w0 >> off);
+    sink.or_word(word + 1u, (uint32_t)((((uint64_t)w0 << 32) | w1) >> off));
+    sink.or_word(word + 2u, (uint32_t)((((uint64_t)w1 << 32) | w2) >> off));
+    if (AEC_ANY(nw > 3u)) {
+        if (nw > 3u) sink.or_word(word + 3u, (uint32_t)((((uint64_t)w2 << 32) | w3) >> off));
+    }
+    if (AEC_ANY(nw > 4u)) {
+        if (nw > 4u) sink.or_word(word + 4u, (uint32_t)(((uint64_t)w3 << 32) >> off));
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // bit reader: stream = big-endian 32-bit words at a 4-byte aligned base
 // ------------------------------------------------------------------------------------
