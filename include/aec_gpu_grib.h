@@ -1,0 +1,166 @@
+/*
+ * aec_gpu_grib.h -- GRIB2 CCSDS packing (data representation template 5.42 / 7.42, ecCodes' grid_ccsds) that stays on
+ * the device: float fields to section-7 streams and back.
+ *
+ * Between a field of floats and the coder (aec_gpu.h) sits GRIB2's simple packing, WMO regulation 92.9.4:
+ *       Y * 10^D = R + X * 2^E
+ * R an IEEE float32, E and D small integers, X an unsigned integer of nbits bits.  A writer finds the field's minimum
+ * and maximum, chooses R and E, quantises every value to X and codes the X; a reader decodes the X and reverses the
+ * formula.  These entry points are that layer for a caller whose fields live in HBM (a model that writes packed
+ * messages, a training pipeline that reads them), as aec_gpu_sz.h is the layer for SZIP chunks.  All pointers marked
+ * d_ are HIP device pointers; every call only ENQUEUES work on `stream` (a hipStream_t passed as void*), allocates
+ * nothing the context does not keep and reads nothing back.  Exported by libaec.so.0.
+ *
+ * THE CONTRACT
+ * A batch is n_fields fields of ONE element type (elem: AEC_GPU_GRIB_F32 or AEC_GPU_GRIB_F64) under ONE template
+ * (nbits 1..32, the compression-options octet, block size, reference sample interval); R, E and D are per field.
+ * Field i is n_values[i] >= 1 values at d_src + src_offsets[i]: n_values and src_offsets are HOST arrays (free again
+ * when the call returns), the offsets are multiples of the element size (so is d_src) and otherwise arbitrary, the
+ * fields lie in any order, do not overlap, and nothing between them is read.
+ *
+ * All quantisation arithmetic is IEEE double, one correctly rounded operation at a time, never contracted into a fused
+ * multiply-add (which rounds once where this contract rounds twice):
+ *   p    = 10^|D|, exact in a double for |D| <= 22 (from a table)
+ *   s(y) = y * p for D > 0, y / p for D < 0, y for D = 0
+ * Pack
+ *   1. lo = s(minimum of the field), hi = s(maximum); -0.0 counts as +0.0
+ *   2. R  = the largest float32 <= lo
+ *   3. range = hi - (double)R;  M = 2^nbits - 1
+ *   4. E  = the smallest integer with range * 2^-E <= M, held to [-127, 127]
+ *   5. X  = trunc((s(y) - R) * 2^-E + 0.5)      (the scaling by a power of two is exact; ties go UP, this is not rint)
+ *   Every step is monotone and M is exact, so 0 <= X <= M without clamping -- except where E had to be held at 127 (a
+ *   range beyond 2^127 * M: nbits 1 or 2 and extremes near +-FLT_MAX): X is then held to M and the field gets status bit 2.
+ *   A constant field (lo == hi) gets E = 0 and X = 0 throughout: a GRIB writer sets nbits 0 for it and drops section 7.
+ *   With have_params the caller supplies R and E per field (re-packing with a source message's parameters, |E| <= 1022);
+ *   X then follows the formula for every field, is held to [0, M], and a field that needed that gets status bit 2.
+ * Unpack
+ *   v = X * 2^E + (double)R (the product is exact, the sum rounded once), Y = v / p (D > 0), v * p (D < 0) or v, then
+ *   one rounding to the element type.
+ * This is the WMO definition.  It is NOT claimed to be bit-identical to ecCodes' floats: ecCodes builds its powers of
+ * ten by repeated multiplication.  The STREAMS are bit-identical to what any libaec gives for the same X.
+ *
+ * X lie little-endian in containers of 1 byte (nbits <= 8), 2 bytes (<= 16) or 4 bytes (<= 32), never 3.
+ *
+ * OUT OF SCOPE: section 6 bitmaps and missing values (the caller compacts the field first); second-order and JPEG
+ * packings; parsing or writing GRIB messages themselves; a quantiser fused into the encoder.
+ */
+#ifndef AEC_GPU_GRIB_H
+#define AEC_GPU_GRIB_H 1
+
+#include "aec_gpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AEC_GPU_GRIB_F32 4      /* elem: the element type by its size */
+#define AEC_GPU_GRIB_F64 8
+
+#define AEC_GPU_GRIB_BAD      1u  /* status bit 0: the field holds a non-finite value, or |lo| or |hi| exceeds FLT_MAX; its
+                                     stream and X are unspecified, every other field of the batch is exact */
+#define AEC_GPU_GRIB_CONSTANT 2u  /* status bit 1: lo == hi */
+#define AEC_GPU_GRIB_CLAMPED  4u  /* status bit 2: an X of a field that is not bad was held to [0, M] -- under have_params,
+                                     or where E was held at 127 */
+
+/* Template 5.42 as far as it is shared by a batch */
+typedef struct aec_gpu_grib_template_s {
+    unsigned int nbits;       /* octet 20: bits per packed value */
+    unsigned int options;     /* octet 22, the CCSDS compression options mask (libaec.h's AEC_* flags) */
+    unsigned int block_size;  /* octet 23 */
+    unsigned int rsi;         /* octets 24-25: reference sample interval */
+} aec_gpu_grib_template;
+
+/* The per-field record, 16 bytes: what the caller writes into section 5 (R octets 12-15, E 16-17, D 18-19), on the
+ * device after a pack (d_fields) and on the host where the caller supplies parameters (params). */
+typedef struct aec_gpu_grib_field_s {
+    float R;
+    int32_t E;
+    int32_t D;
+    uint32_t status;          /* AEC_GPU_GRIB_* bits; ignored in params */
+} aec_gpu_grib_field;
+
+typedef struct aec_gpu_grib_layout_s {
+    aec_gpu_params coder;     /* bits_per_sample = nbits; flags = the mask's AEC_DATA_PREPROCESS | AEC_RESTRICTED | AEC_PAD_RSI
+                                 bits plus AEC_NOT_ENFORCE, which the encoder needs and the decoder ignores.  The mask's
+                                 AEC_DATA_MSB and AEC_DATA_3BYTE bits are ignored: they say how samples lie in memory and
+                                 never change a stream */
+    unsigned int container;   /* bytes of an X in memory: 1 / 2 / 4 */
+} aec_gpu_grib_layout_t;
+
+/* Host arithmetic only.  AEC_CONF_ERROR for AEC_DATA_SIGNED in the mask, nbits 0 (a constant field has no section 7:
+ * there is nothing to code) or above 32, |D| > 22, and whatever aec_gpu_check_params refuses for the coder. */
+AEC_GPU_API int aec_gpu_grib_layout(const aec_gpu_grib_template *t, int D, aec_gpu_grib_layout_t *layout);
+
+/*
+ * aec_gpu_grib_plan is host arithmetic only (1 = the batch is taken, 0 = it would be refused).  Field i has blocks_i =
+ * ceil(n_values[i] / block_size) blocks and a room of its own in d_work at work_offsets[i], the running sum of
+ * up16(blocks_j * block_size * container), j < i (work_offsets is optional).  Refused, and AEC_CONF_ERROR from the calls
+ * below with nothing enqueued: a template aec_gpu_grib_layout rejects; an elem that is neither; a field without a value;
+ * a batch aec_gpu_encode_chunks_plan or aec_gpu_decode_chunks_plan refuses; totals a launch cannot count -- more than
+ * 2^31 - 1 fields, a field of 2^35 bytes or more (values or room), or more than 2^25 wavefronts of 64 lanes, a wavefront
+ * per 4 KiB of a field's values and one per 1 KiB of its room, every field rounded up to whole wavefronts.
+ */
+typedef struct aec_gpu_grib_plan_s {
+    aec_gpu_params coder;     /* as aec_gpu_grib_layout gives it (the encoder's flags) */
+    size_t   work_bytes;      /* d_work: the sum of up16(blocks_i * block_size * container) */
+    size_t   out_bound;       /* = aec_gpu_encode_chunks_plan(coder, rooms).out_bound: an out_cap that never overflows */
+    uint64_t rsi_entries;     /* = that plan's rsi_entries: entries of d_rsi_bit_offsets */
+    size_t   workspace_bytes; /* device memory the context holds for such a batch: the coder's (encode or decode, the
+                                 larger) and this layer's descriptors, wavefront table and extremes (aec_gpu_held_bytes
+                                 counts it, aec_gpu_trim releases it; it is the buffer of the SZIP chunk calls) */
+} aec_gpu_grib_plan_t;
+AEC_GPU_API int aec_gpu_grib_plan(const aec_gpu_grib_template *t, int elem, const uint64_t *n_values, uint64_t n_fields,
+                                  aec_gpu_grib_plan_t *plan, uint64_t *work_offsets);
+
+/*
+ * Pack n_fields fields in one enqueue: minimum and maximum, the parameters, the quantisation into d_work, then
+ * aec_gpu_encode_chunks_async over the rooms.  D (host array, n_fields entries) gives every field's decimal scale
+ * factor; with have_params != 0, params (host array, n_fields entries) gives R and E and its D is ignored.
+ * d_work (plan.work_bytes bytes, 16-byte aligned): after the call d_work + work_offsets[i] holds field i's X, the last
+ * block padded with the last X (nothing behind the field is read); the up to 15 bytes between that and the next room
+ * are not written, nor is anything outside [d_work, d_work + work_bytes).
+ * d_out, out_cap (overflow; nothing is written at or beyond out_cap), d_chunks, d_rsi_bit_offsets (optional) and
+ * d_result: exactly as aec_gpu_encode_chunks_async defines them.  Section 7 of field i is the ceil(bits / 8) bytes at
+ * base_bits / 8 of d_out: byte for byte aec_buffer_encode of its X.
+ * d_fields (n_fields records): R, E, D and status of every field.
+ * Nothing returns to the host; the device is synchronised only where a buffer of the context grows.
+ * n_fields == 0: AEC_OK, nothing is enqueued.
+ */
+AEC_GPU_API int aec_gpu_grib_pack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_src,
+                                        const uint64_t *src_offsets, const uint64_t *n_values, const int32_t *D,
+                                        int have_params, const aec_gpu_grib_field *params, uint64_t n_fields, void *d_work,
+                                        void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
+                                        uint64_t *d_rsi_bit_offsets, aec_gpu_grib_field *d_fields,
+                                        aec_gpu_enc_result *d_result, void *stream);
+
+/*
+ * Unpack n_fields streams in one enqueue: aec_gpu_decode_chunks_async into d_work (out_offsets = work_offsets,
+ * out_bytes = the rooms), then the reverse formula with params[i] (host array: R, E, D as section 5 gives them).
+ * d_in, in_bytes, in_offsets, in_bytes_each, d_rsi_bit_offsets, have_table, d_results and d_result are exactly those of
+ * aec_gpu_decode_chunks_async: with have_table != 0 the table is the one the pack call wrote and no index pass runs;
+ * with have_table == 0 the index pass runs first, for messages of a foreign producer, whose streams may lie at any byte.
+ * Exactly n_values[i] elements are written at d_dst + dst_offsets[i] (multiples of the element size, as d_dst) and
+ * nothing outside them.  The values of a field whose record in d_results is not clean are unspecified, every other
+ * field is exact.
+ */
+AEC_GPU_API int aec_gpu_grib_unpack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_in,
+                                          size_t in_bytes, const uint64_t *in_offsets, const uint64_t *in_bytes_each,
+                                          const uint64_t *n_values, const aec_gpu_grib_field *params,
+                                          const uint64_t *dst_offsets, uint64_t n_fields, uint64_t *d_rsi_bit_offsets,
+                                          int have_table, void *d_work, void *d_dst, aec_gpu_dec_result *d_results,
+                                          aec_gpu_dec_result *d_result, void *stream);
+
+/* The two halves alone, for callers that drive the coder themselves: pack without the encoder (d_work and d_fields as
+ * above), and unpack without the decoder (d_work holds the X in the plan's rooms). */
+AEC_GPU_API int aec_gpu_grib_quantise_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_src,
+                                            const uint64_t *src_offsets, const uint64_t *n_values, const int32_t *D,
+                                            int have_params, const aec_gpu_grib_field *params, uint64_t n_fields,
+                                            void *d_work, aec_gpu_grib_field *d_fields, void *stream);
+AEC_GPU_API int aec_gpu_grib_dequantise_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_work,
+                                              const uint64_t *n_values, const aec_gpu_grib_field *params,
+                                              const uint64_t *dst_offsets, uint64_t n_fields, void *d_dst, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AEC_GPU_GRIB_H */

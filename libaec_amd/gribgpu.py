@@ -1,0 +1,280 @@
+"""GRIB2 CCSDS packing that stays on the device (include/aec_gpu_grib.h) for torch tensors living in HBM: float fields to
+section-7 streams and back.
+
+torch is used for device memory and streams only; the minimum / maximum, the parameters, the quantisation and the coder are
+kernels launched by libaec.so.0 through the C entry points declared in aec_gpu_grib.h.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import gpu
+from .api import AEC_DATA_PREPROCESS
+
+AEC_CONF_ERROR = -1
+F32, F64 = 4, 8                       # elem: the element type by its size
+BAD, CONSTANT, CLAMPED = 1, 2, 4      # status bits of a field record
+
+
+class Template(C.Structure):
+    """aec_gpu_grib_template"""
+    _fields_ = [("nbits", C.c_uint), ("options", C.c_uint), ("block_size", C.c_uint), ("rsi", C.c_uint)]
+
+
+class Layout(C.Structure):
+    """aec_gpu_grib_layout_t"""
+    _fields_ = [("coder", gpu.Params), ("container", C.c_uint)]
+
+
+class Plan(C.Structure):
+    """aec_gpu_grib_plan_t"""
+    _fields_ = [("coder", gpu.Params), ("work_bytes", C.c_size_t), ("out_bound", C.c_size_t), ("rsi_entries", C.c_uint64),
+                ("workspace_bytes", C.c_size_t)]
+
+
+FIELD_DTYPE = np.dtype([("R", "<f4"), ("E", "<i4"), ("D", "<i4"), ("status", "<u4")])      # aec_gpu_grib_field
+BATCH_CHUNK_DTYPE = np.dtype([("base_bits", "<u8"), ("bits", "<u8")])
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    lib = gpu._lib()
+    if not _bound:
+        if not hasattr(lib, "aec_gpu_grib_pack_async"):
+            raise RuntimeError("this libaec.so.0 has no GRIB layer (aec_gpu_grib_*): rebuild it")
+        vp, sz, u64, pt = C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(Template)
+        lib.aec_gpu_grib_layout.restype = C.c_int
+        lib.aec_gpu_grib_layout.argtypes = [pt, C.c_int, C.POINTER(Layout)]
+        lib.aec_gpu_grib_plan.restype = C.c_int
+        lib.aec_gpu_grib_plan.argtypes = [pt, C.c_int, vp, u64, C.POINTER(Plan), vp]
+        lib.aec_gpu_grib_pack_async.restype = C.c_int
+        lib.aec_gpu_grib_pack_async.argtypes = [vp, pt, C.c_int, vp, vp, vp, vp, C.c_int, vp, u64, vp, vp, sz, vp, vp, vp, vp, vp]
+        lib.aec_gpu_grib_unpack_async.restype = C.c_int
+        lib.aec_gpu_grib_unpack_async.argtypes = [vp, pt, C.c_int, vp, sz, vp, vp, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.aec_gpu_grib_quantise_async.restype = C.c_int
+        lib.aec_gpu_grib_quantise_async.argtypes = [vp, pt, C.c_int, vp, vp, vp, vp, C.c_int, vp, u64, vp, vp, vp]
+        lib.aec_gpu_grib_dequantise_async.restype = C.c_int
+        lib.aec_gpu_grib_dequantise_async.argtypes = [vp, pt, C.c_int, vp, vp, vp, vp, u64, vp, vp]
+        _bound = True
+    return lib
+
+
+def _u64(a):
+    """a host array of uint64 for a call (None stays None); the array must outlive the call, so it is returned"""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _host(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def records(R=None, E=None, D=None, n=None):
+    """a host array of aec_gpu_grib_field from per-field R, E, D (scalars or sequences)"""
+    n = n if n is not None else len(D if D is not None else R)
+    rec = np.zeros(n, FIELD_DTYPE)
+    for key, v in (("R", R), ("E", E), ("D", D)):
+        if v is not None:
+            rec[key] = v
+    return rec
+
+
+def layout(nbits, options, block_size, rsi, D=0):
+    """aec_gpu_grib_layout (host arithmetic, no device needed): a Layout, or None where the call says AEC_CONF_ERROR"""
+    t = Template(nbits, options, block_size, rsi)
+    out = Layout()
+    rc = _lib().aec_gpu_grib_layout(C.byref(t), D, C.byref(out))
+    if rc == AEC_CONF_ERROR:
+        return None
+    if rc != 0:
+        raise RuntimeError(f"aec_gpu_grib_layout failed ({rc})")
+    return out
+
+
+def plan(nbits, options, block_size, rsi, elem, n_values):
+    """aec_gpu_grib_plan (host arithmetic, no device needed) for fields of n_values values: the dict {coder, work_bytes,
+    out_bound, rsi_entries, workspace_bytes, work_offsets}, or None where the batch would be refused"""
+    t = Template(nbits, options, block_size, rsi)
+    n_values = _u64(n_values)
+    offs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    p = Plan()
+    if not _lib().aec_gpu_grib_plan(C.byref(t), elem, _host(n_values), n_values.size, C.byref(p), _host(offs)):
+        return None
+    return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
+                out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
+                work_offsets=offs[:n_values.size])
+
+
+def _elem_of(t):
+    import torch
+    if t.dtype == torch.float32:
+        return F32
+    if t.dtype == torch.float64:
+        return F64
+    raise ValueError("fields are float32 or float64 tensors")
+
+
+class GribCodec:
+    """One template 5.42 (nbits, compression options, block size, reference sample interval) and one aec_gpu context
+    (workspace) on the current torch device."""
+
+    def __init__(self, nbits, block_size=32, rsi=128, mask=AEC_DATA_PREPROCESS):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("libaec_amd.gribgpu needs a HIP device (no CPU implementation)")
+        self.torch = torch
+        self.lib = _lib()
+        self.t = Template(nbits, mask, block_size, rsi)
+        if layout(nbits, mask, block_size, rsi) is None:
+            raise ValueError("invalid template (aec_gpu_grib_layout -> AEC_CONF_ERROR)")
+        self.ctx = C.c_void_p()
+        torch.zeros(1, device="cuda")          # make sure the HIP context of this device is current
+        rc = self.lib.aec_gpu_create(C.byref(self.ctx))
+        if rc != 0:
+            raise RuntimeError(f"aec_gpu_create failed ({rc})")
+
+    def close(self):
+        if self.ctx:
+            self.lib.aec_gpu_destroy(self.ctx)
+            self.ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self, stream):
+        return C.c_void_p(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
+
+    def plan(self, n_values, elem=F32):
+        t = self.t
+        return plan(t.nbits, t.options, t.block_size, t.rsi, elem, n_values)
+
+    # ---- enqueue -------------------------------------------------------------------------------
+    def pack_async(self, elem, d_src, src_offsets, n_values, D, params, d_work, d_out, out_cap, d_chunks, d_table, d_fields,
+                   d_result, stream=None):
+        """src_offsets (bytes) / n_values: uint64 arrays on the host, D: int32 array on the host, params: a FIELD_DTYPE
+        array on the host or None; d_work: the plan's work_bytes, 16-byte aligned; d_chunks: n * 16 bytes
+        (BATCH_CHUNK_DTYPE); d_table: int64 tensor of the plan's rsi_entries, or None; d_fields: n * 16 bytes (FIELD_DTYPE);
+        d_result: 24 bytes (gpu.ENC_RESULT_DTYPE).  Returns the call's return code."""
+        offs, nv = _u64(src_offsets), _u64(n_values)
+        Dh = None if D is None else np.ascontiguousarray(D, dtype=np.int32)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_pack_async(self.ctx, C.byref(self.t), elem, _ptr(d_src), _host(offs), _host(nv), _host(Dh),
+                                                int(ph is not None), _host(ph), nv.size, _ptr(d_work), _ptr(d_out), out_cap,
+                                                _ptr(d_chunks), _ptr(d_table), _ptr(d_fields), _ptr(d_result), self._stream(stream))
+
+    def unpack_async(self, elem, d_in, in_bytes, in_offsets, in_sizes, n_values, params, dst_offsets, d_table, have_table, d_work,
+                     d_dst, d_results, d_result, stream=None):
+        """in_offsets / in_sizes (None with a table), n_values, dst_offsets (bytes): uint64 arrays on the host; params: a
+        FIELD_DTYPE array on the host; d_table: int64 tensor of the plan's rsi_entries; d_results: n * 40 bytes, d_result:
+        40 bytes (gpu.DEC_RESULT_DTYPE).  Returns the call's return code."""
+        ino, ins, nv, dso = _u64(in_offsets), _u64(in_sizes), _u64(n_values), _u64(dst_offsets)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_unpack_async(self.ctx, C.byref(self.t), elem, _ptr(d_in), in_bytes, _host(ino), _host(ins),
+                                                  _host(nv), _host(ph), _host(dso), nv.size, _ptr(d_table), int(bool(have_table)),
+                                                  _ptr(d_work), _ptr(d_dst), _ptr(d_results), _ptr(d_result), self._stream(stream))
+
+    def quantise_async(self, elem, d_src, src_offsets, n_values, D, params, d_work, d_fields, stream=None):
+        """pack_async without the encoder"""
+        offs, nv = _u64(src_offsets), _u64(n_values)
+        Dh = None if D is None else np.ascontiguousarray(D, dtype=np.int32)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_quantise_async(self.ctx, C.byref(self.t), elem, _ptr(d_src), _host(offs), _host(nv), _host(Dh),
+                                                    int(ph is not None), _host(ph), nv.size, _ptr(d_work), _ptr(d_fields),
+                                                    self._stream(stream))
+
+    def dequantise_async(self, elem, d_work, n_values, params, dst_offsets, d_dst, stream=None):
+        """unpack_async without the decoder: d_work holds the X in the plan's rooms"""
+        nv, dso = _u64(n_values), _u64(dst_offsets)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_dequantise_async(self.ctx, C.byref(self.t), elem, _ptr(d_work), _host(nv), _host(ph),
+                                                      _host(dso), nv.size, _ptr(d_dst), self._stream(stream))
+
+    # ---- convenience (synchronising) -------------------------------------------------------------
+    def _check(self, rc, what):
+        if rc != 0:
+            raise ValueError(f"not a batch for one call ({what} -> AEC_CONF_ERROR)") if rc == AEC_CONF_ERROR else \
+                RuntimeError(f"{what} failed ({rc})")
+
+    def pack(self, d_values, offsets, n_values, D, params=None, want_offsets=False):
+        """fields of n_values[i] elements at ELEMENT offsets[i] of the float tensor d_values -> (d_out, spans, fields,
+        d_table): section 7 of field i is d_out[spans[i][0]:][:spans[i][1]] (start, bytes), fields the FIELD_DTYPE records
+        (R, E, D, status), d_table the int64 RSI table for unpack (None unless want_offsets)"""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        pl = self.plan(n_values, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_plan)")
+        n, dev = len(n_values), d_values.device
+        d_out = torch.empty(pl["out_bound"], dtype=torch.uint8, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_rec = torch.zeros(max(1, n) * 2, dtype=torch.int64, device=dev)
+        d_fields = torch.zeros(max(1, n) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_res = torch.zeros(gpu.ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev) if want_offsets else None
+        Dh = np.broadcast_to(np.asarray(D, dtype=np.int32), (n,))
+        self._check(self.pack_async(elem, d_values, _u64(offsets) * np.uint64(elem), n_values, Dh, params, d_work, d_out,
+                                    d_out.numel(), d_rec, d_table, d_fields, d_res), "aec_gpu_grib_pack_async")
+        if n and d_res.cpu().numpy().view(gpu.ENC_RESULT_DTYPE)[0]["overflow"]:
+            raise RuntimeError("encode overflow")
+        rec = d_rec.cpu().numpy().view(np.uint64).view(BATCH_CHUNK_DTYPE)[:n]
+        spans = [(int(r["base_bits"]) // 8, (int(r["bits"]) + 7) // 8) for r in rec]
+        return d_out, spans, d_fields.cpu().numpy().view(FIELD_DTYPE)[:n], d_table
+
+    def unpack(self, d_streams, spans, params, n_values, d_table=None, dtype=None):
+        """streams -> (float tensor with the fields back to back, per-field decode records): stream i is spans[i] = (start,
+        bytes) of the uint8 tensor d_streams, params the FIELD_DTYPE records of section 5.  With d_table (of pack(...,
+        want_offsets=True), positions relative to d_streams) no index pass runs."""
+        torch = self.torch
+        dtype = dtype or torch.float32
+        elem = F32 if dtype == torch.float32 else F64
+        pl = self.plan(n_values, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_plan)")
+        n, dev = len(n_values), d_streams.device
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(n_values, dtype=np.uint64))]).astype(np.uint64) * np.uint64(elem)
+        d_dst = torch.empty(int(dst_offsets[-1]) // elem, dtype=dtype, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        have = d_table is not None
+        if not have:
+            d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev)
+        d_results = torch.zeros(max(1, n) * gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_result = torch.zeros(gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        in_offs = None if have else [s for s, _ in spans]
+        in_sizes = None if have else [b for _, b in spans]
+        self._check(self.unpack_async(elem, d_streams, d_streams.numel(), in_offs, in_sizes, n_values, params, dst_offsets[:n], d_table,
+                                      have, d_work, d_dst, d_results, d_result), "aec_gpu_grib_unpack_async")
+        return d_dst, d_results.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[:n]
+
+    def quantise(self, d_values, offsets, n_values, D, params=None):
+        """-> (d_work with the X in the plan's rooms, the plan, the FIELD_DTYPE records)"""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        pl = self.plan(n_values, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_plan)")
+        n = len(n_values)
+        d_work = torch.zeros(pl["work_bytes"] + 16, dtype=torch.uint8, device=d_values.device)
+        d_fields = torch.zeros(max(1, n) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=d_values.device)
+        Dh = np.broadcast_to(np.asarray(D, dtype=np.int32), (n,))
+        self._check(self.quantise_async(elem, d_values, _u64(offsets) * np.uint64(elem), n_values, Dh, params, d_work, d_fields),
+                    "aec_gpu_grib_quantise_async")
+        return d_work, pl, d_fields.cpu().numpy().view(FIELD_DTYPE)[:n]
+
+    def dequantise(self, d_work, n_values, params, dtype=None):
+        """X in the plan's rooms of d_work -> a float tensor with the fields back to back"""
+        torch = self.torch
+        dtype = dtype or torch.float32
+        elem = F32 if dtype == torch.float32 else F64
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(n_values, dtype=np.uint64))]).astype(np.uint64) * np.uint64(elem)
+        d_dst = torch.empty(int(dst_offsets[-1]) // elem, dtype=dtype, device=d_work.device)
+        self._check(self.dequantise_async(elem, d_work, n_values, params, dst_offsets[:len(n_values)], d_dst),
+                    "aec_gpu_grib_dequantise_async")
+        return d_dst
