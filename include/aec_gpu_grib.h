@@ -29,7 +29,9 @@
  *   4. E  = the smallest integer with range * 2^-E <= M, held to [-127, 127]
  *   5. X  = trunc((s(y) - R) * 2^-E + 0.5)      (the scaling by a power of two is exact; ties go UP, this is not rint)
  *   Every step is monotone and M is exact, so 0 <= X <= M without clamping -- except where E had to be held at 127 (a
- *   range beyond 2^127 * M: nbits 1 or 2 and extremes near +-FLT_MAX): X is then held to M and the field gets status bit 2.
+ *   range beyond 2^127 * M: nbits 1 or 2 and extremes near +-FLT_MAX): an X that would exceed M is then held to M, and a
+ *   field in which one was gets status bit 2.  (Holding E does not by itself flag a field: up to a range of
+ *   2^127 * (M + 0.5) every X still rounds to at most M, and nothing is held.)
  *   A constant field (lo == hi) gets E = 0 and X = 0 throughout: a GRIB writer sets nbits 0 for it and drops section 7.
  *   With have_params the caller supplies R and E per field (re-packing with a source message's parameters, |E| <= 1022);
  *   X then follows the formula for every field, is held to [0, M], and a field that needed that gets status bit 2.
@@ -83,7 +85,10 @@ typedef struct aec_gpu_grib_layout_s {
     aec_gpu_params coder;     /* bits_per_sample = nbits; flags = the mask's AEC_DATA_PREPROCESS | AEC_RESTRICTED | AEC_PAD_RSI
                                  bits plus AEC_NOT_ENFORCE, which the encoder needs and the decoder ignores.  The mask's
                                  AEC_DATA_MSB and AEC_DATA_3BYTE bits are ignored: they say how samples lie in memory and
-                                 never change a stream */
+                                 never change a stream.  AEC_PAD_RSI is the coder's (libaec.h): the ENCODER ignores it, as
+                                 the reference's does, so a pack under it writes unpadded streams -- which an unpack reads
+                                 with the pack's table, but not bare: a decoder under it expects every RSI on a byte, as
+                                 a producer that pads writes them */
     unsigned int container;   /* bytes of an X in memory: 1 / 2 / 4 */
 } aec_gpu_grib_layout_t;
 

@@ -3,7 +3,11 @@ tests/grib_cases.py: the records, the X in the work buffer, the streams, the chu
 what an unpack writes with the pack's table and from foreign streams; the two halves alone; the refusals; an output that
 is too small; a NaN and an Inf in a batch.  References: the NumPy model bit for bit, the streams the reference made of the
 model's X (tests/golden/grib_vectors.npz), the library's own aec_buffer_encode, and the reference itself when oracle/_ref
-travelled.  Every buffer a call writes lies between guard bytes and is compared whole."""
+travelled.  Every buffer a call writes lies between guard bytes and is compared whole.
+
+The same checks run over grib_cases.edge_batches() (R, E, D and X at their thresholds, the positions of the extremes in
+k_grib_minmax on either alignment, the coder flags) and dequantise_cases() (Y under parameters no pack produced); there
+the streams are aec_buffer_encode's of the model's X, and the model is pinned to exact rationals by tests/test_grib_emul.py."""
 import numpy as np
 import pytest
 
@@ -15,6 +19,8 @@ pytestmark = pytest.mark.gpu
 
 AEC_OK, AEC_CONF_ERROR = 0, -1
 BATCHES = [b["name"] for b in gc.batches()]
+EDGES = [b["name"] for b in gc.edge_batches()]
+DEQS = [c["name"] for c in gc.dequantise_cases()]
 
 
 @pytest.fixture(scope="module")
@@ -91,8 +97,10 @@ def pack(mods, codec, b, out_cap=None, encode=True):
     n_values = [f.size for f in b["fields"]]
     plan = codec.plan(n_values, b["elem"])
     assert plan is not None
-    offs, extent = gc.placement(b)
+    offs, extent = gc.edge_placement(b)
     src_whole, d_src = guarded(torch, extent)
+    if b.get("bases") is not None:             # fields that say where they lie: on a multiple of 16 bytes, or one element behind one
+        assert [(d_src.data_ptr() + o) % 16 for o in offs] == [0 if how == "aligned" else b["elem"] for how in b["bases"]]
     put(torch, d_src, [(o, f.view(np.uint8)) for o, f in zip(offs, b["fields"])])
     src_want = src_whole.clone()
     work_whole, d_work = guarded(torch, plan["work_bytes"])
@@ -135,10 +143,12 @@ def streams_of(got):
     return [out[int(base) // 8:int(base) // 8 + (int(bits) + 7) // 8].tobytes() for base, bits in got["rec"]]
 
 
-@pytest.mark.parametrize("name", BATCHES)
-def test_pack(mods, golden, name):
+def check_pack(mods, b):
+    """a pack of the batch: records and work buffer are the model's, every stream is b["streams"][i] (where the batch
+    brings streams), aec_buffer_encode of the model's X and the reference's; the chunk records and the RSI table are those
+    of the chunk coder on the work buffer"""
     torch, api, gpu, gribgpu = mods
-    b = golden[name]
+    name = b["name"]
     nbits, options, bs, rsi = b["tmpl"]
     codec = gribgpu.GribCodec(nbits, bs, rsi, options)
     got = pack(mods, codec, b)
@@ -147,18 +157,19 @@ def test_pack(mods, golden, name):
     streams = streams_of(got)
     at = 0
     flags = gc.coder_flags(options, False)
-    for i, (s, x, want) in enumerate(zip(streams, b["X"], b["streams"])):
+    for i, (s, x) in enumerate(zip(streams, b["X"])):
         assert int(got["rec"][i][0]) == at * 8, f"stream {i} does not lie behind stream {i - 1}"
         at += len(s)
         if x is None:
             continue
-        assert s == want, f"{name}: stream {i} is not the fixture's ({len(s)} vs {len(want)} bytes)"
+        if b.get("streams") is not None:
+            want = b["streams"][i]
+            assert s == want, f"{name}: stream {i} is not the fixture's ({len(s)} vs {len(want)} bytes)"
         data = gc.x_bytes(x, nbits, x.size)
         assert api.aec_buffer_encode(data, nbits, bs, rsi, flags) == (0, s), f"{name}: stream {i} is not aec_buffer_encode's"
         if have_ref():
             assert ref_encode(data, nbits, bs, rsi, flags) == (0, s), f"{name}: stream {i} is not the reference's"
     assert (int(got["res"]["total_bits"]) + 7) // 8 == at
-    # the chunk records and the RSI table are those of the chunk coder on the work buffer
     coder = gpu.Codec(*got["plan"]["coder"])
     d_out, rec, d_tab, res = coder.encode_chunks(got["d_work"].clone(), got["plan"]["work_offsets"], rooms_of(b, got["plan"]),
                                                  want_offsets=True)
@@ -166,6 +177,11 @@ def test_pack(mods, golden, name):
     assert torch.equal(d_tab, got["d_table"])
     assert torch.equal(d_out[:at], got["d_out"][:at])
     codec.close()
+
+
+@pytest.mark.parametrize("name", BATCHES)
+def test_pack(mods, golden, name):
+    check_pack(mods, golden[name])
 
 
 def unpack(mods, codec, b, d_in, in_offs, in_sizes, d_table, fields_idx, seed):
@@ -200,47 +216,67 @@ def unpack(mods, codec, b, d_in, in_offs, in_sizes, d_table, fields_idx, seed):
     whole_is(dst_whole, 0, regions, unspecified, "d_dst")
 
 
-@pytest.mark.parametrize("name", BATCHES)
-def test_unpack(mods, golden, name):
-    """the round trip with the pack's table, and foreign streams (the reference's, back to back from an odd byte) bare"""
+def check_unpack(mods, b, streams):
+    """the round trip with the pack's table, and `streams` (one per field, None for a bad one) back to back from an odd
+    byte, bare"""
     torch, api, gpu, gribgpu = mods
-    b = golden[name]
     nbits, options, bs, rsi = b["tmpl"]
     codec = gribgpu.GribCodec(nbits, bs, rsi, options)
     got = pack(mods, codec, b)
     assert got["rc"] == AEC_OK
     unpack(mods, codec, b, got["d_out"], None, None, got["d_table"].clone(), list(range(len(b["fields"]))), 1)
-    clean = [i for i, x in enumerate(b["X"]) if x is not None]
+    unpack_bare(mods, codec, b, streams)
+    codec.close()
+
+
+def unpack_bare(mods, codec, b, streams):
+    torch = mods[0]
+    clean = [i for i, m in enumerate(b["model"]) if m[3] is not None]
     in_offs, at = [], 1
     for i in clean:
         in_offs.append(at)
-        at += len(b["streams"][i])
+        at += len(streams[i])
     in_whole, d_in = guarded(torch, at + 3)
-    put(torch, d_in, [(o, np.frombuffer(b["streams"][i], np.uint8)) for o, i in zip(in_offs, clean)])
-    unpack(mods, codec, b, d_in, in_offs, [len(b["streams"][i]) for i in clean], None, clean, 2)
+    put(torch, d_in, [(o, np.frombuffer(streams[i], np.uint8)) for o, i in zip(in_offs, clean)])
+    unpack(mods, codec, b, d_in, in_offs, [len(streams[i]) for i in clean], None, clean, 2)
+
+
+@pytest.mark.parametrize("name", BATCHES)
+def test_unpack(mods, golden, name):
+    """the round trip with the pack's table, and foreign streams (the reference's, back to back from an odd byte) bare"""
+    check_unpack(mods, golden[name], golden[name]["streams"])
+
+
+def dequantise_alone(mods, codec, b, d_work, work_whole):
+    """dequantise_async of the X in d_work under the parameters of b["model"]: the work buffer stays, the whole
+    destination is the model's"""
+    torch = mods[0]
+    n_values = [f.size for f in b["fields"]]
+    offs, extent = gc.placement(b, 3)
+    dst_whole, d_dst = guarded(torch, extent)
+    work_before = work_whole.clone()
+    rc = codec.dequantise_async(b["elem"], d_work, n_values, host_params(b), offs, d_dst)
+    torch.cuda.synchronize()
+    assert rc == AEC_OK and torch.equal(work_before, work_whole)
+    regions = [(o, gc.dequantise(x, R, E, D, b["dtype"]).view(np.uint8)) for o, (R, E, st, x), D in zip(offs, b["model"], b["D"])
+               if x is not None]
+    unspecified = [(o, f.nbytes) for o, f, (R, E, st, x) in zip(offs, b["fields"], b["model"]) if x is None]
+    whole_is(dst_whole, 0, regions, unspecified, "d_dst")
+
+
+def check_halves(mods, b):
+    torch, api, gpu, gribgpu = mods
+    nbits, options, bs, rsi = b["tmpl"]
+    codec = gribgpu.GribCodec(nbits, bs, rsi, options)
+    got = pack(mods, codec, b, encode=False)
+    check_records_and_work(b, got)
+    dequantise_alone(mods, codec, b, got["d_work"], got["work_whole"])
     codec.close()
 
 
 @pytest.mark.parametrize("name", ["mix12_f4", "mix16_f8", "n32_f8", "shapes_f4", "witness_f8", "given_f4", "nonfinite_f8"])
 def test_quantise_and_dequantise_alone(mods, golden, name):
-    torch, api, gpu, gribgpu = mods
-    b = golden[name]
-    nbits, options, bs, rsi = b["tmpl"]
-    codec = gribgpu.GribCodec(nbits, bs, rsi, options)
-    got = pack(mods, codec, b, encode=False)
-    check_records_and_work(b, got)
-    n_values = got["n_values"]
-    offs, extent = gc.placement(b, 3)
-    dst_whole, d_dst = guarded(torch, extent)
-    work_before = got["work_whole"].clone()
-    rc = codec.dequantise_async(b["elem"], got["d_work"], n_values, host_params(b), offs, d_dst)
-    torch.cuda.synchronize()
-    assert rc == AEC_OK and torch.equal(work_before, got["work_whole"])
-    regions = [(o, gc.dequantise(x, R, E, D, b["dtype"]).view(np.uint8)) for o, (R, E, st, x), D in zip(offs, b["model"], b["D"])
-               if x is not None]
-    unspecified = [(o, f.nbytes) for o, f, (R, E, st, x) in zip(offs, b["fields"], b["model"]) if x is None]
-    whole_is(dst_whole, 0, regions, unspecified, "d_dst")
-    codec.close()
+    check_halves(mods, golden[name])
 
 
 @pytest.mark.parametrize("name", [b["name"] for b in gc.extra_batches()])
@@ -254,6 +290,76 @@ def test_status_of_the_extra_batches(mods, name):
     codec = gribgpu.GribCodec(nbits, bs, rsi, options)
     for encode in (True, False):
         check_records_and_work(b, pack(mods, codec, b, encode=encode))
+    codec.close()
+
+
+def edge_of(name):
+    """a batch of grib_cases.edge_batches() with what the checks above look at: the model and its X"""
+    b = next(g for g in gc.edge_batches() if g["name"] == name)
+    model = gc.model_of(b)
+    return dict(b, model=model, X=[m[3] for m in model])
+
+
+def own_streams(mods, tmpl, X):
+    """the streams of a foreign producer: aec_buffer_encode of every X (None stays None), and the reference's the same
+    where it was built.  Under AEC_PAD_RSI the encoder pads nothing (include/libaec.h: ignored, as by the reference) while
+    a decoder under it expects every RSI on a byte, so such a stream is made RSI by RSI and laid back to back, as
+    tests/bsmall_cases.py makes them"""
+    api = mods[1]
+    nbits, options, bs, rsi = tmpl
+    flags = gc.coder_flags(options, False) & ~gc.PAD_RSI
+    piece = bs * rsi * gc.container(nbits) if options & gc.PAD_RSI else 1 << 62
+    out = []
+    for x in X:
+        if x is None:
+            out.append(None)
+            continue
+        data = gc.x_bytes(x, nbits, x.size)
+        s = b""
+        for at in range(0, data.size, piece):
+            rc, part = api.aec_buffer_encode(data[at:at + piece], nbits, bs, rsi, flags)
+            assert rc == 0
+            if have_ref():
+                assert ref_encode(data[at:at + piece], nbits, bs, rsi, flags) == (0, part)
+            s += part
+        out.append(s)
+    return out
+
+
+@pytest.mark.parametrize("name", EDGES)
+def test_pack_of_the_edge_batches(mods, name):
+    """records, X and streams at the thresholds of R, E, D and X (the given records where the batch brings them)"""
+    check_pack(mods, edge_of(name))
+
+
+@pytest.mark.parametrize("name", EDGES)
+def test_quantise_and_dequantise_alone_on_the_edge_batches(mods, name):
+    check_halves(mods, edge_of(name))
+
+
+@pytest.mark.parametrize("name", EDGES)
+def test_unpack_of_the_edge_batches(mods, name):
+    b = edge_of(name)
+    check_unpack(mods, b, own_streams(mods, b["tmpl"], b["X"]))
+
+
+@pytest.mark.parametrize("name", DEQS)
+def test_dequantise_cases(mods, name):
+    """Y under parameters no pack produced (ties to even, Inf, subnormal results, an exact +0.0, E and D at the limits of
+    what the calls accept): dequantise_async on a work buffer that holds the X, and unpack_async, bare, on the streams
+    aec_buffer_encode makes of them"""
+    torch, api, gpu, gribgpu = mods
+    c = next(g for g in gc.dequantise_cases() if g["name"] == name)
+    b = gc.deq_as_batch(c)
+    nbits, options, bs, rsi = b["tmpl"]
+    codec = gribgpu.GribCodec(nbits, bs, rsi, options)
+    plan = codec.plan([x.size for x in c["X"]], b["elem"])
+    assert plan is not None
+    work_whole, d_work = guarded(torch, plan["work_bytes"])
+    regions, _ = work_regions(b, plan)
+    put(torch, d_work, regions)
+    dequantise_alone(mods, codec, b, d_work, work_whole)
+    unpack_bare(mods, codec, b, own_streams(mods, b["tmpl"], c["X"]))
     codec.close()
 
 
@@ -302,6 +408,9 @@ def test_refusals_enqueue_nothing(mods, golden):
     assert packs(nv=none) == [AEC_CONF_ERROR] * 2 and unpacks(nv=none) == [AEC_CONF_ERROR] * 2
     assert packs(work=d_work[8:]) == [AEC_CONF_ERROR] * 2 and unpacks(work=d_work[8:]) == [AEC_CONF_ERROR] * 2
     assert packs(prm=far) == [AEC_CONF_ERROR] * 2 and unpacks(prm=far) == [AEC_CONF_ERROR] * 2
+    low = params.copy()
+    low["E"][1] = -1023
+    assert packs(prm=low) == [AEC_CONF_ERROR] * 2 and unpacks(prm=low) == [AEC_CONF_ERROR] * 2
     for out, oc in ((d_out[8:], cap - 16), (d_out, cap - 8), (d_out, 0)):         # (the encoder's own conditions on its output)
         assert codec.pack_async(b["elem"], d_src, offs, n_values, D, None, d_work, out, oc, d_rec, d_table, d_fields, d_res) == AEC_CONF_ERROR
     signed = gribgpu.GribCodec(nbits, bs, rsi, options)
@@ -314,6 +423,16 @@ def test_refusals_enqueue_nothing(mods, golden):
     torch.cuda.synchronize()
     assert all(torch.equal(x, y) for x, y in zip(before, after)), "a call without fields wrote"
     signed.close()
+    # the limits themselves are taken: a given E of exactly +-1022 and a D of exactly +-22, and what comes out is the model's
+    ends = dict(b, D=[22, -22, 22, -22] + D[4:], given=[(float(R), [1022, -1022, -1022, 1022][i] if i < 4 else E)
+                                                         for i, (R, E, st, x) in enumerate(b["model"])])
+    ends["model"] = gc.model_of(ends)
+    assert [m[1] for m in ends["model"][:4]] == [1022, -1022, -1022, 1022] and not any(m[2] & gc.BAD for m in ends["model"])
+    for encode in (True, False):
+        got = pack(mods, codec, ends, encode=encode)
+        check_records_and_work(ends, got)
+    dequantise_alone(mods, codec, ends, got["d_work"], got["work_whole"])
+    unpack_bare(mods, codec, ends, own_streams(mods, ends["tmpl"], [m[3] for m in ends["model"]]))
     codec.close()
 
 

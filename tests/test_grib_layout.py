@@ -83,6 +83,21 @@ def test_layout_takes_the_edges():
     assert gribgpu.layout(32, 0, 64, 4096) is not None and gribgpu.layout(1, 0, 2, 1) is not None
 
 
+def test_the_templates_of_the_edge_cases_are_taken():
+    """every template of grib_cases.edge_batches() and dequantise_cases(), RSI padding and the restricted code set among
+    them: the layout passes the flags through and the plan takes the batch"""
+    cases = [(b["name"], b["tmpl"], b["elem"], [f.size for f in b["fields"]]) for b in gc.edge_batches()]
+    cases += [(c["name"], c["tmpl"], c["elem"], [x.size for x in c["X"]]) for c in gc.dequantise_cases()]
+    seen = set()
+    for name, tmpl, elem, n_values in cases:
+        L = gribgpu.layout(*tmpl)
+        assert L is not None, name
+        assert L.coder.flags == gc.coder_flags(tmpl[1]), name
+        assert gribgpu.plan(*tmpl, elem, n_values) is not None, name
+        seen.add(tmpl[1] & (gc.PP | gc.RESTRICTED | gc.PAD_RSI))
+    assert {gc.PP | gc.PAD_RSI, gc.PP | gc.RESTRICTED, gc.RESTRICTED | gc.PAD_RSI} <= seen
+
+
 def test_plan_refuses():
     t = (16, gc.PP, 32, 128)
     assert gribgpu.plan(*t, 2, [100]) is None and gribgpu.plan(*t, 16, [100]) is None         # an elem that is neither
