@@ -1283,10 +1283,8 @@ int decode_range_call(struct aec_stream *strm, const size_t *offs, size_t n, siz
     // (at least kRangeRsis RSIs per batch: long RSIs -- 512 KiB of 32-bit output each -- are a wavefront each, and a
     // batch of fewer than the chip holds at once leaves it part idle: k_decode_wave<32, 4> takes 244 VGPRs, 8 waves per
     // CU, 2048 on 256 CUs, and one launch of them takes ~3.1 ms whether it has 512 RSIs or 2048 (profiles/r07: config 3,
-    // 1 GiB: 29.7 GB/s with batches of 512 RSIs, 34.6 with 1024, 39.2 with 2048).  AEC_RANGE_RSIS: the tuning build's
-    // knob for measuring it)
-    const size_t least = tune("AEC_RANGE_RSIS", (uint32_t)kRangeRsis);
-    const size_t per = kPipeOut / rsi_bytes > least ? kPipeOut / rsi_bytes : least;
+    // 1 GiB: 29.7 GB/s with batches of 512 RSIs, 34.6 with 1024, 39.2 with 2048))
+    const size_t per = kPipeOut / rsi_bytes > kRangeRsis ? kPipeOut / rsi_bytes : kRangeRsis;
     aec_gpu_dec_result *d_dec = static_cast<aec_gpu_dec_result *>(s->d_res.p);
     uint8_t *bounce = s->h_res + 256;
     int rc = AEC_OK;

@@ -1598,18 +1598,14 @@ DecGeom dec_geom(const Cfg &c, uint64_t n_rsi, uint64_t avg_cds_bits, uint32_t s
     // half ring: after a full refill at least rw/2 - 3 words lie ahead of any position
     // (how many average coded data sets half of the half ring -- its steady-state look-ahead -- must hold: 2.  With
     // 4, typical.dat's 720-bit blocks of 64 samples kept the full ring, 33 KB per wave and 4 waves per CU: 5.8 ms;
-    // on the half ring 3.3 ms, the second attempts included.  AEC_DEC_HALF_FACTOR overrides, for measurements.)
-    const uint64_t hf = tune("AEC_DEC_HALF_FACTOR", 2);
-    if (rw >= 32 && g.maxw <= rw / 2 - 3 && avg_cds_bits && avg_cds_bits * hf <= (uint64_t)rw / 2 * 32) {
+    // on the half ring 3.3 ms, the second attempts included.)
+    if (rw >= 32 && g.maxw <= rw / 2 - 3 && avg_cds_bits && avg_cds_bits * 2 <= (uint64_t)rw / 2 * 32) {
         rw /= 2;
         g.needw = rw / 2;
     }
     g.ring_words = rw;
     // (+ the output staging rows of k_decode for small blocks: 64 x (row + 16) bytes)
-    // (AEC_DEC_LDS_PAD: extra LDS bytes per wave, a diagnostic knob for occupancy experiments; the kernel
-    // never touches them)
-    const size_t pad = tune("AEC_DEC_LDS_PAD", 0);
-    const size_t per_wave = (size_t)(rw + 2) * 64 * 4 + (stg_row_bytes ? 64 * (stg_row_bytes + 16) : 0) + pad;
+    const size_t per_wave = (size_t)(rw + 2) * 64 * 4 + (stg_row_bytes ? 64 * (stg_row_bytes + 16) : 0);
     // waves per workgroup: whatever packs most waves into the 160 KiB of a CU
     uint32_t waves = 1, best = 0;
     for (uint32_t w = 1; w <= 4; w *= 2) {
@@ -1692,11 +1688,9 @@ void launch_lanes(const DecLaunch &a)
         const DecGeom g = dec_geom(c, a.n_items, avg, (!SUMS && stg_on((int)blk)) ? stg_row((int)blk) : 0u);
         // loads in flight per block iteration (see kPend): sized for the average coded data set where the caller
         // knows it, for the worst case of large blocks where it does not
-        const uint32_t e_kp = tune("AEC_DEC_KP", 0);               // (diagnostic: force 2, 4 or 8)
         // (measured: 2 up to the 256 bits per block they feed -- C3 at 247: 2.70 ms against 2.74 with 4 --, 8 for the
         // 720 bits of typical.dat's blocks: 5.8 ms against 7.1 with 4 and 7.8 with 2)
-        int kp = BS >= 32 ? (avg == 0 || avg > 512 ? 8 : (avg > 256 ? 4 : 2)) : (avg > 256 ? 4 : 2);
-        if (e_kp) kp = e_kp >= 8 ? (BS >= 32 ? 8 : 4) : (e_kp >= 4 ? 4 : 2);
+        const int kp = BS >= 32 ? (avg == 0 || avg > 512 ? 8 : (avg > 256 ? 4 : 2)) : (avg > 256 ? 4 : 2);
         with_container_bytes(c, [&](auto by) {
             constexpr int B = decltype(by)::value;
             if constexpr (kCanWin) {
@@ -1787,9 +1781,9 @@ static bool dec_wave_wanted(const Cfg &c, uint64_t n_items)
     // for room / RSI size + 2 of at least 4 MiB of room, 4098 for the 8-bit shape whatever the call holds)
     // (RSIs of 64 .. 127 blocks: as many more as they are shorter -- the bound of a small call is 8194 for RSIs of 64
     // blocks of 8 samples, which left a 64 KiB chunk of 128 RSIs to a lane per RSI: 102 us of the call's 260)
-    const uint32_t most = tune("AEC_DEC_WAVE_MAX", 8192u), least = tune("AEC_DEC_WAVE_RSI", 16u);
+    const uint32_t most = tune("AEC_DEC_WAVE_MAX", 8192u);
     const uint64_t scaled = c.rsi >= 64u && c.rsi < 128u ? (uint64_t)most * 128u / c.rsi : most;
-    return c.rsi >= least && n_items <= scaled;
+    return c.rsi >= 16u && n_items <= scaled;
 }
 
 // The lane kernel (wave = false) or the wave kernel of block size bs for one launch (0: the generic lane kernel)

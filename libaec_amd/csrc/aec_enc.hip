@@ -2048,8 +2048,6 @@ void launch_encode_uniform_batch(const Cfg &c, const uint8_t *d_in, uint64_t seg
 // c describes the sum of the chunks (total_blocks, total_segs, rsi_count summed over them)
 uint32_t chunks_segs_per_wave(const Cfg &c)
 {
-    const uint32_t force = tune("AEC_CHUNKS_SPW", 0);          // (tuning build: every value at a small total)
-    if (force == 1 || force == 2 || force == 4 || force == 8) return force;
     return make_geom(c, true).segs_per_wave;
 }
 

@@ -370,7 +370,7 @@ k_trunk_scan(const TrGeom g, const TrTables t)
 
 // Hypothesis walks.  Every node of the core windows is tried as an RSI start.  One workgroup per group of
 // `wpg` windows (persistent: the groups in turn); the group's stretch of the stream plus a margin behind it is
-// staged in LDS with the trunk marks and, for short coded data sets (NX), the byte table of ordinary coded
+// staged in LDS with the trunk marks and the byte table of ordinary coded
 // data sets (aec_trunk.h: TrStaged), so that a step of a walk touches no device memory.  The walks differ
 // wildly in length (a node in the middle of an RSI is back on the trunk after a few coded data sets, one behind
 // a true RSI start after the trunk's resynchronisation distance), so the loop is flat -- one coded data set per
@@ -379,8 +379,7 @@ k_trunk_scan(const TrGeom g, const TrTables t)
 //   TABLE   the byte table has the length (an ordinary coded data set inside an RSI)
 //   PARSE   the parse on the staged words (reference sample, zero-block runs, long coded data sets)
 //   REMOTE  device memory: the lane's next node, or a walk that has left the stretch
-// LDS: sw[bits / 32 + 8] u32 | bm[bits / 32] u32 | wnb[wpg + 1] u32 | wnp[wpg + 1] u32 | nx[bits] u8 (NX)
-template <bool NX>
+// LDS: sw[bits / 32 + 8] u32 | bm[bits / 32] u32 | wnb[wpg + 1] u32 | wnp[wpg + 1] u32 | nx[bits] u8
 __global__ void __launch_bounds__(1024)
 k_hyp_walk(const Cfg c, const TrStream s, const TrGeom g, const TrTables t, uint32_t wpg, uint32_t margin,
            uint32_t ngroups)
@@ -409,13 +408,11 @@ k_hyp_walk(const Cfg c, const TrStream s, const TrGeom g, const TrTables t, uint
         }
         __syncthreads();
         if (tid <= w1 - w0) wnp[tid] = wnb[tid] - wnb[0];    // (nbase[w + 1] - nbase[w] = ccnt[w] after the scan)
-        TrStaged st{mem, sw, bm, NX ? nx : nullptr, base, bits};
-        if (NX) {
-            for (uint32_t q = tid; q < bits; q += nt) {
-                TrWin W;
-                st.win(base + q, W);
-                nx[q] = tr_fast_entry(s, c, base + q, W);
-            }
+        TrStaged st{mem, sw, bm, nx, base, bits};
+        for (uint32_t q = tid; q < bits; q += nt) {
+            TrWin W;
+            st.win(base + q, W);
+            nx[q] = tr_fast_entry(s, c, base + q, W);
         }
         __syncthreads();
         const uint32_t nnodes = wnp[w1 - w0];
@@ -453,7 +450,7 @@ k_hyp_walk(const Cfg c, const TrStream s, const TrGeom g, const TrTables t, uint
                 } else if (h.steps >= g.budget) {
                     finish(TR_FAIL);
                 } else {
-                    e8 = NX ? nx[r] : 0u;
+                    e8 = nx[r];
                     cls = e8 ? TABLE : PARSE;
                 }
             }
@@ -628,7 +625,6 @@ struct CoLists {
     uint2 *plain;              // {window, index inside the window}
     uint32_t *counts;          // [0] queue entries, [1] plain entries (both may run beyond their capacity)
     uint32_t qcap, pcap;
-    uint32_t over_plain;       // CO_OVER nodes go to the plain walk too (RSIs not much longer than the way to the trunk)
 };
 
 __device__ __forceinline__ void co_push(uint2 *list, uint32_t *count, uint32_t cap, uint2 v)
@@ -662,7 +658,6 @@ k_hyp_walk_co(const Cfg c, const TrStream s, const TrGeom g, const TrTables t, u
               uint32_t ngroups, uint32_t shift, uint32_t tmax, uint32_t cap, const CoLists ls, uint32_t park_at)
 {
     if (t.skip_if && *t.skip_if) return;
-    // ls.over_plain: walks that run over the end of their RSI before they land go to the plain walk as well
     extern __shared__ __attribute__((aligned(16))) uint32_t co_lds[];
     __shared__ CoParked pk[kCoPark];
     __shared__ uint32_t sh_npark;
@@ -802,8 +797,7 @@ k_hyp_walk_co(const Cfg c, const TrStream s, const TrGeom g, const TrTables t, u
             if (kind != CO_LAND && kind != CO_QUEUE && kind != CO_DEFER) {
                 out = TrRec{0u, 0u};
                 park = 0;
-                if (kind == CO_PLAIN || (kind == CO_OVER && ls.over_plain))
-                    co_push(ls.plain, ls.counts + 1, ls.pcap, make_uint2(w0 + wi, idx));
+                if (kind == CO_PLAIN) co_push(ls.plain, ls.counts + 1, ls.pcap, make_uint2(w0 + wi, idx));
             } else if (kind == CO_LAND && !park) {
                 co_push(ls.plain, ls.counts + 1, ls.pcap, make_uint2(w0 + wi, idx));
             }
@@ -834,7 +828,7 @@ k_hyp_walk_rest(const Cfg c, const TrStream s, const TrGeom g, const TrTables t,
         t.rec[at] = TrRec{dist, bh};                           // (y: the count it was handed on with -- k_hyp_defer)
         t.park[at] = res;
         const uint32_t rk = co_kind(res);
-        if (rk == CO_PLAIN || (rk == CO_OVER && (ls.over_plain || co_bend(res))))
+        if (rk == CO_PLAIN || (rk == CO_OVER && co_bend(res)))
             co_push(ls.plain, ls.counts + 1, ls.pcap, make_uint2(e.y, (uint32_t)(at - t.nbase[e.y])));
     }
 }
@@ -863,7 +857,7 @@ k_hyp_defer(const Cfg c, const TrGeom g, const TrTables t, const CoLists ls)
             t.rec[at] = TrRec{0u, 0u};
             t.park[at] = 0;
             if (kind == CO_LAND) kind = CO_PLAIN;
-            if (kind == CO_PLAIN || (kind == CO_OVER && ls.over_plain)) co_push(ls.plain, ls.counts + 1, ls.pcap, make_uint2(w, i));
+            if (kind == CO_PLAIN) co_push(ls.plain, ls.counts + 1, ls.pcap, make_uint2(w, i));
         }
     }
 }
@@ -1146,7 +1140,7 @@ constexpr uint32_t kS2FlatWindows = 48;     // spans of at most this many window
 constexpr uint32_t kS2BridgeAfter = 16;      // RSIs the walker had to walk itself before k_bridge steps in
 
 struct Spec2Geom {
-    uint32_t lead, core, look, stride, burn, cap_lds, cap_core, fast, refill, uncrun;
+    uint32_t lead, core, look, stride, burn, cap_lds, cap_core, refill, uncrun;
     uint32_t v4;          // k_spec4 (a table of every position's coded data set) instead of k_spec2
     const uint32_t *skip_if = nullptr;   // != 0 there: a scheme in front has delivered the stream; the kernel returns at once
 };
@@ -1244,17 +1238,14 @@ k_spec2(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
     stamp(1);
     // a coded data set without / with (`ref`) a reference sample: the straight-line parse, the full one where a
     // unary part does not end inside its 64-bit peek (rare at the coded rates this kernel is chosen for)
-    const bool use_fast = g.fast != 0;
     // (a walk that fails this close to the end of the window may have run out of it -- see kS2Limited)
     auto near_end = [&](uint32_t pos) { return pos + 4096u > s.limit; };
     auto cds1 = [&](uint32_t q, uint32_t &run) -> uint32_t {
-        if (!use_fast) return spec_cds(s, c, q, 1u, run);
         uint32_t len = spec_cds_fast<1>(win, s.limit, c, q, run);
         if (len == kSpecUnresolved) len = spec_cds(s, c, q, 1u, run);
         return len;
     };
     auto cds0 = [&](uint32_t q, uint32_t &run) -> uint32_t {
-        if (!use_fast) return spec_cds(s, c, q, 0u, run);
         uint32_t len = spec_cds_fast<0>(win, s.limit, c, q, run);
         if (len == kSpecUnresolved) len = spec_cds(s, c, q, 0u, run);
         return len;
@@ -1567,7 +1558,7 @@ k_spec2(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
 // the candidate arrays take later; rank is a prefix count per word + one popcount.)  Every step of a chain or of a
 // catch-up walk is then one LDS read.  Everything else -- marks, candidates, hop tables, hypotheses, records -- is
 // k_spec2's, in the same order and with the same results: the tables a span gets are bit for bit the ones k_spec2
-// writes (tests: AEC_S2_V4=0/1 in the tuning build give identical index results; k_spec_verify on both).
+// writes (tests/test_gpu_parity.py: both kernels index the same streams and agree with the oracle).
 // LDS: win | marks | rank | sel | mpre | [cpos cnxt ua ub] (the ones tile while F is filled) | F[W] (later chop4
 // chop16 csucc).  W = 48 kbit fits the 160 KB of a CU.
 __device__ __forceinline__ void
@@ -1713,10 +1704,8 @@ spec4_window(const uint32_t wid, const Cfg &c, const uint32_t *__restrict__ word
         }
     }
     stamp(2);
-    const bool use_fast = g.fast != 0;
     auto near_end = [&](uint32_t pos) { return pos + 4096u > s.limit; };
     auto cds1 = [&](uint32_t q, uint32_t &run) -> uint32_t {
-        if (!use_fast) return spec_cds(s, c, q, 1u, run);
         uint32_t len = spec_cds_fast<1>(win, s.limit, c, q, run);
         if (len == kSpecUnresolved) len = spec_cds(s, c, q, 1u, run);
         return len;
@@ -2081,43 +2070,6 @@ k_dense_pick(const uint32_t *__restrict__ sparse_ccnt, uint32_t sparse_core, uin
     else dccnt[w] = 0u;
 }
 
-#ifdef AEC_TUNING
-// (diagnostics) every record of the window tables against the plain parse of its RSI from device memory
-__global__ void k_spec_verify(const Cfg c, const TrStream s, const SparseTables t, uint32_t nwin, uint32_t *bad)
-{
-    const uint32_t w = blockIdx.x;
-    if (w >= nwin) return;
-    for (uint32_t i = threadIdx.x; i < t.ccnt[w]; i += blockDim.x) {
-        const uint2 rec = t.rec[(uint64_t)w * t.cap + i];
-        const uint64_t p = t.lo + (uint64_t)w * t.core + t.cpos[(uint64_t)w * t.cap + i];
-        // the position must be marked and have this index
-        uint2 r2;
-        uint32_t wv, ix;
-        if (!sparse_lookup(t, p, r2, wv, ix) || wv != w || ix != i) {
-            if (atomicAdd(&bad[0], 1u) < 4u) printf("window %u cand %u pos %llu: lookup says window %u index %u\n", w, i, (unsigned long long)p, wv, ix);
-            continue;
-        }
-        if (!rec.x) continue;
-        uint64_t q = p;
-        uint32_t b = 0;
-        bool ok = true;
-        while (b < c.rsi && ok) {
-            uint32_t nz;
-            const uint32_t len = tr_cds(s, c, q, (b == 0 && (c.flags & F_PREPROCESS)) ? 1u : 0u, nz);
-            const uint32_t nb = len ? tr_blocks(c, nz, b) : 0u;
-            if (!len || !nb || nb > c.rsi - b) ok = false;
-            q += len;
-            b += nb;
-        }
-        if (!ok || q - p != rec.x) {
-            if (atomicAdd(&bad[1], 1u) < 8u)
-                printf("window %u cand %u pos %llu: record %u, parse %llu (%s)\n", w, i, (unsigned long long)p, rec.x,
-                       (unsigned long long)(q - p), ok ? "ok" : "fails");
-        }
-    }
-}
-#endif
-
 // RSIs the window tables could not resolve because the walk ran out of its window -- longer than the look-ahead:
 // incompressible stretches in an otherwise low-entropy stream -- parsed coded data set by coded data set from the
 // stream where it lies, one lane per hypothesis on the list k_spec2 leaves (all of them around such a stretch, the
@@ -2353,10 +2305,6 @@ __global__ void k_expand2(const SparseTables t, const IdxCarry *__restrict__ car
 // wave-uniform values), but the stream is served from a 16 KiB LDS window that all 64 lanes refill
 // with coalesced 16-byte loads, so the parser never waits for HBM: a dependent global load per
 // refill of the bit window held the first version at ~5 MB/s of compressed input.
-#ifdef AEC_TUNING
-__device__ int g_dbg_serial = 0;      // (diagnostics, AEC_IDX_STATS=2: k_index names the RSIs it walks itself)
-__device__ int g_idx_no_stretch = 0;  // (A/B: AEC_IDX_STRETCH=0 gives the serial walk of round 4)
-#endif
 constexpr uint32_t kIdxWindowWords = 4096;
 constexpr uint32_t kIdxPiece = 4096;                                   // bits of a piece
 constexpr uint32_t kIdxPieceWords = kIdxPiece / 32 + 68;               // + the longest coded data set of an encoder (2118 bits)
@@ -2509,11 +2457,7 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
     // ---- the piece tables and the parse of a position from them
     const uint32_t look_words = (maxbits + 31u) / 32u + 2u;
     const uint32_t pwords = kIdxPiece / 32u + (look_words < 68u ? look_words : 68u);
-#ifdef AEC_TUNING
-    const bool stretch = g_idx_no_stretch == 0 && maxbits <= 2118u;      // (AEC_IDX_STRETCH=0: the walk as it was)
-#else
     const bool stretch = maxbits <= 2118u;
-#endif
     uint64_t piece_base = ~0ull;       // LDS window the piece was made from
     uint32_t pc0 = 0, tcnt = 0, plim = 0;
     auto build_piece = [&](uint32_t from_bit) {
@@ -2732,9 +2676,6 @@ k_index(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords, uint64
             if (lane == 0) rsi_off[r] = good;
             cur_start = good;
             n_serial++;
-#ifdef AEC_TUNING
-            if (lane == 0 && g_dbg_serial && n_serial <= 400u) printf("serial: RSI %llu at bit %llu\n", (unsigned long long)r, (unsigned long long)good);
-#endif
         }
         // keep the whole next CDS (and the readers' look-ahead) inside the LDS window
         if ((good >> 5) + (coop ? 66u : maxw + 2u) > base + kIdxWindowWords) {
@@ -2942,6 +2883,10 @@ struct Sparse2Plan {
 constexpr uint32_t kS2WindowBits = 65536;      // lead-in + core + look-ahead (16-bit positions in LDS)
 constexpr uint32_t kS4WindowBits = 49152;      // k_spec4: + 2 bytes per bit for the table of coded data set lengths
 constexpr uint32_t kS2Lead = 4096;
+constexpr uint32_t kS2CdsMax = 80;             // longest mean coded data set the sparse path takes above 4.5 bits per sample
+constexpr uint32_t kS2Stride = 64;             // Spec2Geom::stride, burn, refill
+constexpr uint32_t kS2Burn = 24;
+constexpr uint32_t kS2Refill = 16;
 constexpr uint32_t kS2SuperWindows = 4096;     // windows per launch: bounds the table workspace (~60 KB each)
 
 // The sparse speculation pays off where the coded data sets are short and unary-dominated, so that
@@ -2959,15 +2904,11 @@ Sparse2Plan sparse2_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hi
     // cover is the distance a chain needs to fall onto the true one, ~2 cds^2 bits, whatever the bits per sample
     // (round 5: 8-sample blocks at up to ~9 bits per sample came over the trunk and paid its fixed phases, 17 - 50 ms
     // for 1 - 4 MiB: tests/fuzz_index_gpu.py --time)
-    const uint64_t cds_max = tune("AEC_S2_CDS_MAX", 80);
     // (with the preprocessor only: raw samples repeat the same bits at the same place, a chain that is off the true one
     // does not find it again, and every RSI fell to the serial walker -- 16 MiB of 8-bit data, ratio 1.19: 1.4 s)
-    if (rsi_bits_hint * 2 > samples * 9 && (rsi_bits_hint > (uint64_t)c.rsi * cds_max || !(c.flags & F_PREPROCESS))) return p;
+    if (rsi_bits_hint * 2 > samples * 9 && (rsi_bits_hint > (uint64_t)c.rsi * kS2CdsMax || !(c.flags & F_PREPROCESS))) return p;
     uint64_t look = (2 * rsi_bits_hint + 1024 + 31) & ~31ull;
     if (look < 4096) look = 4096;
-    uint32_t wbits = tune("AEC_S2_WINDOW", kS2WindowBits);
-    if (wbits < 16384 || wbits > kS2WindowBits) wbits = kS2WindowBits;
-    if (look + kS2Lead + 8192 > wbits) wbits = kS2WindowBits;            // long RSIs: the largest window
     if (look > kS2WindowBits - kS2Lead - 16384) return p;
     // k_spec4: the table of every position's coded data set wants 2 bytes per bit of the window, so the window is 48
     // kbit; candidates have room for one per 12 bits (coded data sets of 16 bits and more on average)
@@ -2975,9 +2916,8 @@ Sparse2Plan sparse2_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hi
     // a wash on large streams (1 GiB of config 2: 21.3 against 20.1 ms), a gain where the input is a few windows that do
     // not fill the chip anyway (a 64 KiB chunk: 35 us of 250 per call).  So: small inputs only (up to 4 MB of stream).
     const bool small = total_bits <= (1ull << 25);
-    const bool v4 = tune("AEC_S2_V4", small ? 1u : 0u) != 0 && look + kS2Lead + 8192 <= kS4WindowBits &&
-                    rsi_bits_hint >= (uint64_t)c.rsi * 16u && !tune_set("AEC_S2_WINDOW");
-    if (v4) wbits = kS4WindowBits;
+    const bool v4 = small && look + kS2Lead + 8192 <= kS4WindowBits && rsi_bits_hint >= (uint64_t)c.rsi * 16u;
+    const uint32_t wbits = v4 ? kS4WindowBits : kS2WindowBits;
     uint64_t core = (wbits - kS2Lead - look) & ~1023ull;
     // small inputs: about one window per CU
     const uint64_t want = ((total_bits / 256 + 1023) & ~1023ull);
@@ -2985,16 +2925,14 @@ Sparse2Plan sparse2_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hi
     p.g.lead = kS2Lead;
     p.g.core = (uint32_t)core;
     p.g.look = (uint32_t)look;
-    p.g.stride = tune("AEC_S2_STRIDE", 64u);
-    p.g.burn = tune("AEC_S2_BURN", 24u);
-    p.g.fast = tune("AEC_S2_FAST", 1u);
-    p.g.refill = tune("AEC_S2_REFILL", 16u);
+    p.g.stride = kS2Stride;
+    p.g.burn = kS2Burn;
+    p.g.refill = kS2Refill;
     // (headers of one or two bits -- AEC_RESTRICTED with at most 4 bits per sample -- are no pattern to go by: eight
     // in a row happen by chance all the time there)
-    p.g.uncrun = tune("AEC_S2_UNCRUN", c.id_len >= 3u ? 1u : 0u);
+    p.g.uncrun = c.id_len >= 3u ? 1u : 0u;
     const uint32_t W = p.g.lead + p.g.core + p.g.look, nw = W / 32;
-    const uint32_t capdiv = tune("AEC_S2_CAPDIV", v4 ? 12u : 8u);
-    p.g.cap_lds = (W / (capdiv ? capdiv : 8u) + 63) & ~63u;
+    p.g.cap_lds = (W / (v4 ? 12u : 8u) + 63) & ~63u;
     p.g.cap_core = (p.g.core / 8 + 63) & ~63u;
     p.g.v4 = v4 ? 1u : 0u;
     p.lds = (size_t)(nw + 4) * 4 + (size_t)nw * 4 + (size_t)(nw + 2) * 2 * 3 + (size_t)p.g.cap_lds * 2 * 7 + 64;
@@ -3010,8 +2948,6 @@ Sparse2Plan sparse2_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hi
     // walker takes a lookup per chunk, ~2 us -- chunks of 256 windows made the three of them 0.6 ms of latency per span,
     // 17 % of the index time of a 64 MiB stream; measured 16 .. 256: 32 is best from 64 MiB to 1 GiB)
     p.wpc = p.nwin_max >= 512 ? 32u : (p.nwin_max >= 64 ? 16u : p.nwin_max);
-    p.wpc = tune("AEC_S2_WPC", p.wpc);
-    if (p.wpc == 0) p.wpc = 1;
     p.nchunk_max = (p.nwin_max + p.wpc - 1) / p.wpc;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t words = (size_t)p.nwin_max * (p.g.core / 32);
@@ -3033,7 +2969,7 @@ Sparse2Plan sparse2_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hi
     // 2 s, the reference 0.1 s).  Windows half the size with four times the room per bit resolve those; they are built
     // only where an ordinary window gave up, and the walker takes their records RSI by RSI.
     p.dense = false;
-    if (tune("AEC_S2_DENSE", 1) && look + kS2Lead + 4096 <= 32768) {
+    if (look + kS2Lead + 4096 <= 32768) {
         p.dg = p.g;
         p.dg.lead = kS2Lead;
         p.dg.look = (uint32_t)look;
@@ -3251,7 +3187,7 @@ void go_spec(bool v4, uint32_t nwin, size_t lds, hipStream_t ts, const IdxWalk &
 void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, size_t ws_bytes,
                          const uint32_t *skip_if = nullptr, uint32_t *delivered = nullptr)
 {
-    const uint32_t serial_cap = delivered ? (uint32_t)tune("AEC_IDX_SPARSE_SERIAL_CAP", kSparseSerialCap) : 0u;
+    const uint32_t serial_cap = delivered ? kSparseSerialCap : 0u;
     if (delivered) (void)hipMemsetAsync(delivered, 0, 4, w.st);
     allow_big_lds2();
     Spec2Geom geom = p.g, dgeom = p.dg;
@@ -3261,11 +3197,7 @@ void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, 
     const uint64_t span = (uint64_t)p.nwin_max * p.g.core;
     const uint64_t nspans = (w.end_bit - lo0 + span - 1) / span;
     SideStream side;
-    bool piped = nspans >= kS2PipeSpans && ws_bytes >= 2 * p.bytes && !spec2_prof_buffer(0, false);
-#ifdef AEC_TUNING
-    if (tune_set("AEC_S2_VERIFY") || tune("AEC_S2_PIPE", 1) == 0) piped = false;
-#endif
-    piped = piped && side_take(&side);
+    const bool piped = nspans >= kS2PipeSpans && ws_bytes >= 2 * p.bytes && !spec2_prof_buffer(0, false) && side_take(&side);
     if (piped) {
         (void)hipEventRecord(side.start, w.st);                       // the input is whatever `w.st` has produced so far
         (void)hipStreamWaitEvent(side.st, side.start, 0);
@@ -3307,21 +3239,6 @@ void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, 
                                (unsigned long long *)nullptr, (const uint64_t *)nullptr, 0u, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                few ? nullptr : dlist, few ? nullptr : dcount, few ? t.ccnt : nullptr, few ? p.g.core : 0u, few ? nwin : 0u);
         }
-#ifdef AEC_TUNING
-        if (tune_set("AEC_S2_VERIFY")) {
-            static uint32_t *d_bad = nullptr;
-            if (!d_bad) (void)hipMalloc(reinterpret_cast<void **>(&d_bad), 8);
-            (void)hipMemsetAsync(d_bad, 0, 8, w.st);
-            hipLaunchKernelGGL(k_spec_verify, dim3(nwin), dim3(256), 0, w.st, w.c, TrStream{w.words, w.nwords, w.end_bit}, t, nwin, d_bad);
-            uint32_t h[2] = {0, 0};
-            (void)hipStreamSynchronize(w.st);
-            (void)hipMemcpy(h, d_bad, 8, hipMemcpyDeviceToHost);
-            uint32_t nb = 0;
-            (void)hipMemcpy(&nb, blist_cnt, 4, hipMemcpyDeviceToHost);
-            fprintf(stderr, "verify: %u windows, lookup mismatches %u, wrong records %u; hypotheses for k_bridge: %u\n", nwin, h[0],
-                    h[1], nb);
-        }
-#endif
         if (piped) {
             (void)hipEventRecord(side.tab[set], ts);
             (void)hipStreamWaitEvent(w.st, side.tab[set], 0);
@@ -3335,10 +3252,8 @@ void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, 
             (void)hipMemsetAsync(tb + p.o_wide, 0, (size_t)nchunks * p.g.cap_core * sizeof(uint4), w.st);
             (void)hipMemsetAsync(centry, 0, (size_t)nchunks * sizeof(ChunkEntry), w.st);
         }
-        if (tune("AEC_S2_BRIDGE", 1))
-            hipLaunchKernelGGL(k_bridge, dim3(1024), dim3(64), 0, w.st, w.c, w.words, w.nwords, w.end_bit, t,
-                               const_cast<uint2 *>(t.rec), blist, blist_cnt, carry, first ? 1u : 0u,
-                               (uint32_t)tune("AEC_S2_BRIDGE_AFTER", kS2BridgeAfter));
+        hipLaunchKernelGGL(k_bridge, dim3(1024), dim3(64), 0, w.st, w.c, w.words, w.nwords, w.end_bit, t,
+                           const_cast<uint2 *>(t.rec), blist, blist_cnt, carry, first ? 1u : 0u, kS2BridgeAfter);
         if (!flat)
             hipLaunchKernelGGL(k_wide, dim3((p.g.cap_core + 255) / 256, nchunks), dim3(256), 0, w.st, t, nwin, w.end_bit,
                                const_cast<uint4 *>(t.wide));
@@ -3357,9 +3272,6 @@ void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, 
 #ifdef AEC_TUNING
         if (tune_set("AEC_IDX_STATS")) {                   // (diagnostics: synchronises)
             (void)hipStreamSynchronize(w.st);
-            const int dbg = tune("AEC_IDX_STATS", 0) >= 2 ? 1 : 0;
-            const hipError_t de = hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_serial), &dbg, sizeof(dbg));
-            if (de != hipSuccess) fprintf(stderr, "g_dbg_serial: %s\n", hipGetErrorString(de));
             std::vector<uint32_t> cc(nwin);
             (void)hipMemcpy(cc.data(), t.ccnt, (size_t)nwin * 4, hipMemcpyDeviceToHost);
             uint32_t gave_up = 0, most = 0, nb = 0;
@@ -3396,12 +3308,11 @@ void launch_index_sparse(const IdxWalk &w, const Sparse2Plan &p, uint8_t *base, 
 // ---- geometry and workspace of the trunk index -------------------------------------------------------
 struct TrunkPlan {
     bool ok;
-    uint32_t L, lead, rw, passes, budget, kmax, wpw, wpc, wcap, wfirst;
+    uint32_t L, lead, rw, budget, wpw, wpc, wcap, wfirst;
     uint32_t staged, margin;  // hypothesis walks: byte table of coded data set lengths or not, margin behind a group (bits)
     size_t lds;               // ... and the LDS of a workgroup
-    // coalescing hypothesis walks (aec_trunk.h section 2b): windows per group, margin, bits per mark cell (log2),
-    // parses before a walk is handed on, walks per group, LDS, list capacities
-    uint32_t co, co_wpg, co_margin, co_shift, co_tmax, co_cap, co_qcap, co_pcap, co_over, co_park;
+    // coalescing hypothesis walks (aec_trunk.h section 2b): windows per group, margin, list capacities, LDS
+    uint32_t co, co_wpg, co_margin, co_qcap, co_pcap;
     size_t co_lds, o_coq, o_cop;
     uint32_t pcap;            // pool of RSI ends inside records
     uint32_t nwin_max;        // windows per span (launch set): core + look-ahead
@@ -3416,6 +3327,13 @@ struct TrunkPlan {
 // stream and 4 GiB -- several kernels of a span take as long as the longest serial chain they hold (a trunk region,
 // a walk that was handed on, the walker's hops), whatever the span's size, so fewer and larger spans are cheaper
 constexpr size_t kTrWsWanted = 768u << 20, kTrWsMost = (size_t)4 << 30;
+constexpr uint32_t kTrPasses = 16;             // repair passes of the trunk (trunk_plan)
+constexpr uint32_t kTrStretch = 98304;         // bits of stream a staged hypothesis walk holds in LDS: group + margin
+constexpr uint32_t kTrSegGrid = 4096;          // wavefronts of k_seg_starts at most
+// coalescing walks: bits per mark cell (log2), parses before a walk is handed on, parses before it is set aside
+// inside its workgroup, walks (owners of marks) per group
+constexpr uint32_t kCoShift = 4, kCoTmax = 64, kCoParkAt = 16, kCoCap = 1024;
+static_assert(kCoCap <= kCoMaxOwners, "owners of a group are numbered in the marks");
 
 
 size_t trunk_bytes(TrunkPlan &p, uint32_t nwin)
@@ -3476,71 +3394,60 @@ TrunkPlan trunk_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, 
     // 150 / 150 / 4.7 ms.  Found by sweeping sizes and shapes the benches do not have: tests/fuzz_index_gpu.py --time.)
     uint32_t L = 32768;
     if (total_bits >= (1ull << 28) && 128 * cds > 32768) L = 65536;      // (sample shape: 32768 is better below ~100 MiB)
-    p.L = tune("AEC_TR_L", L);
+    p.L = L;
     uint64_t lead = 4 * sync;
     if (lead < 4096) lead = 4096;
     if (lead > (1u << 19)) lead = 1u << 19;            // (measured: repair passes are cheaper than longer burn-ins)
-    p.lead = tune("AEC_TR_LEAD", (uint32_t)lead);
+    p.lead = (uint32_t)lead;
     uint64_t rw = (4 * sync + p.L - 1) / p.L;
     if (rw < 1) rw = 1;
     if (rw > 8) rw = 8;
-    p.rw = tune("AEC_TR_RW", (uint32_t)rw);
+    p.rw = (uint32_t)rw;
     // (a run of k regions whose burn-in did not find the chain takes k repair passes, and a seam that stays costs far
     // more than a pass: the walks behind it cannot jump across -- 1 GiB of config 3 with one pass too few 36 .. 400 ms
     // instead of 24.  A pass with nothing to repair is a launch of a few microseconds, so there are two to spare.)
     // (Sixteen: on raw samples without the preprocessor -- every block uncompressed, the same bits at the same place in
     // every sample -- a chain off the true one does not find it again at all, whole runs of regions start wrong, and
     // every pass repairs one more of a run: 16 MiB 85 / 63 / 122 ms with five passes, 77 / 42 / 109 with sixteen; still
-    // mostly serial, an open item.)
-    p.passes = tune("AEC_TR_PASSES", 16);
-    // RSIs per record: a walk meets the trunk inside one RSI with probability about 1 - exp(-rsi bits / sync);
-    // enough RSIs that a true start fails once in 1e5
-    {
-        const double x = (double)(rsi_bits_hint ? rsi_bits_hint : (uint64_t)c.rsi * cds) / (double)sync;
-        double k = x > 0.01 ? 11.5 / x : 1e9;
-        if (k < 4) k = 4;
-        if (k > kTrMaxK) k = kTrMaxK;
-        (void)k;
-        p.kmax = tune("AEC_TR_KMAX", kTrMaxK);
-    }
-    const uint64_t budget = (uint64_t)p.kmax * c.rsi;
-    p.budget = tune("AEC_TR_BUDGET", (uint32_t)(budget < 65536 ? budget : 65536));
+    // mostly serial, an open item.)  Hence kTrPasses.
+    // RSIs per record: a walk meets the trunk inside one RSI with probability about 1 - exp(-rsi bits / sync); a record
+    // may cover kTrMaxK RSIs whatever that probability
+    const uint64_t budget = (uint64_t)kTrMaxK * c.rsi;
+    p.budget = (uint32_t)(budget < 65536 ? budget : 65536);
     // wide walker: the first windows of a chunk, whose nodes get a wide entry, hold two average RSIs; a chunk is
     // eight times that (64 windows at least)
     {
         const uint64_t rb = rsi_bits_hint ? rsi_bits_hint : (uint64_t)c.rsi * cds;
         uint64_t wf = (2 * rb + p.L - 1) / p.L + 1;
         if (wf > 512) wf = 512;
-        p.wfirst = tune("AEC_TR_WFIRST", (uint32_t)wf);
-        p.wpc = tune("AEC_TR_WPC", p.wfirst * 8u > 64u ? p.wfirst * 8u : 64u);
-        if (p.wfirst > p.wpc) p.wfirst = p.wpc;
+        p.wfirst = (uint32_t)wf;
+        p.wpc = p.wfirst * 8u > 64u ? p.wfirst * 8u : 64u;
     }
     // The hypothesis walks run on staged stretches of the stream: group + margin.  Short coded data sets get the
     // byte table (1.25 bytes of LDS per bit, stretch 96 kbit); the others stage words and marks only (0.25 bytes
     // per bit, stretch up to 480 kbit).  The margin holds an average walk -- some 150 coded data sets where the
     // trunk resynchronises fast, the resynchronisation distance where it does not; longer walks go on in device memory.
-    p.staged = tune("AEC_TR_NX", cds <= 96 ? 1u : 0u);
+    p.staged = cds <= 96 ? 1u : 0u;
     if (p.staged) {
-        const uint32_t stretch = tune("AEC_TR_STRETCH", 98304u);
         uint64_t margin = 512 * cds;
-        if (margin > stretch * 2ull / 3) margin = stretch * 2ull / 3;
+        if (margin > kTrStretch * 2ull / 3) margin = kTrStretch * 2ull / 3;
         margin = (margin + 1023) & ~1023ull;
-        p.margin = tune("AEC_TR_MARGIN", (uint32_t)margin);
-        uint32_t wpg = stretch > p.margin + p.L ? (stretch - p.margin) / p.L : 1u;
+        p.margin = (uint32_t)margin;
+        uint32_t wpg = kTrStretch > p.margin + p.L ? (kTrStretch - p.margin) / p.L : 1u;
         if (wpg > 256u) wpg = 256u;
-        p.wpw = tune("AEC_TR_WPW", wpg);
+        p.wpw = wpg;
         const uint32_t bits = p.wpw * p.L + p.margin;
         p.lds = (size_t)(bits / 32 + 8) * 4 + (size_t)(bits / 32) * 4 + (size_t)(p.wpw + 1) * 8 + bits + 64;
     } else {
         // device-memory walks: a window per wavefront (measured on C3 / typical shapes: more wavefronts beat
         // longer node lists per lane -- the walks are bound by memory latency)
-        p.wpw = tune("AEC_TR_WPW", 1u);
+        p.wpw = 1u;
     }
     // Coalescing walks where a walk does not complete its RSI before it is back on the trunk (long RSIs: config 3) --
     // a walk then meets another walk after a dozen parses instead of the trunk after a few hundred.  Groups of up to
     // 64 kbit (about a thousand nodes at most), marks of 16 bits, 64 parses before a walk is handed on (measured in
     // tests/emul on the config-3 shape: 15 + 15 parses per node against 280; 16 + 8 with 128 parses).
-    p.co = tune("AEC_TR_CO", (!p.staged && c.rsi >= 8 * cds) ? 1u : 0u);
+    p.co = (!p.staged && c.rsi >= 8 * cds) ? 1u : 0u;
     if (p.co) {
         // (measured on config 3, 1 GiB: what counts is that two or three workgroups fit a CU -- 96 kbit + 16 kbit of margin
         // 24.0 ms, 64 + 32 kbit 27.0, 128 + 16 kbit 28.0; walks that leave the margin are handed on, which costs little)
@@ -3548,24 +3455,16 @@ TrunkPlan trunk_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, 
         if (core > 98304) core = 98304;
         uint32_t wpg = (uint32_t)(core / p.L);
         if (wpg < 1) wpg = 1;
-        p.co_wpg = tune("AEC_TR_CO_WPG", wpg);
+        p.co_wpg = wpg;
         uint32_t margin = (uint32_t)((64u * cds + 1023u) & ~1023ull);
         margin = margin < 8192u ? 8192u : (margin > 32768u ? 32768u : margin);
-        p.co_margin = tune("AEC_TR_CO_MARGIN", margin) & ~31u;
-        if (p.co_margin < 2048u) p.co_margin = 2048u;
-        p.co_shift = tune("AEC_TR_CO_SHIFT", 4u);
-        if (p.co_shift < 2u || p.co_shift > 4u) p.co_shift = 4u;
-        p.co_tmax = tune("AEC_TR_CO_TMAX", 64u);
-        p.co_park = tune("AEC_TR_CO_PARK", 16u);
-        p.co_cap = tune("AEC_TR_CO_CAP", 1024u);
-        // walks whose count runs over the end of their RSI before they land:
-        // (AEC_TR_CO_OVER=1, measurements: every such walk to the plain walk.  The walks that matter among them -- true
-        // chains the trunk has not found again for a whole RSI -- are told by their counts (aec_trunk.h tr_co_rest) and
-        // get the plain walk in any case; the rest are garbage walks by the thousand, each thousands of parses long.)
-        p.co_over = tune("AEC_TR_CO_OVER", 0u);
-        if (p.co_cap > kCoMaxOwners) p.co_cap = kCoMaxOwners;
+        p.co_margin = margin;
+        // walks whose count runs over the end of their RSI before they land are dropped, not sent to the plain walk
+        // (measured with every such walk sent there: the walks that matter among them -- true chains the trunk has not
+        // found again for a whole RSI -- are told by their counts (aec_trunk.h tr_co_rest) and get the plain walk in
+        // any case; the rest are garbage walks by the thousand, each thousands of parses long.)
         const uint64_t bits = (uint64_t)p.co_wpg * p.L + p.co_margin;
-        p.co_lds = ((bits / 32 + 8) + bits / 32 + ((bits >> p.co_shift) + 2) + 2 * ((size_t)p.co_wpg + 1)) * 4 + (size_t)p.co_cap * 8 + 64;
+        p.co_lds = ((bits / 32 + 8) + bits / 32 + ((bits >> kCoShift) + 2) + 2 * ((size_t)p.co_wpg + 1)) * 4 + (size_t)kCoCap * 8 + 64;
         if (bits + 0x1000 >= 0x40000 || p.co_lds + sizeof(CoParked) * kCoPark + 64 > 160 * 1024) p.co = 0;     // (k_hyp_walk_co packs distances inside a group into 19 bits)
     }
     {
@@ -3619,7 +3518,7 @@ void allow_big_lds_walk()
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64) dev = 0;
     std::call_once(once[dev], [] {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_hyp_walk<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_hyp_walk), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024) != hipSuccess)
             (void)hipGetLastError();
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_hyp_walk_co), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3651,7 +3550,7 @@ void launch_index_trunk(const IdxWalk &w, TrunkPlan p, uint8_t *base, const uint
         g.nwin = (uint32_t)(left < p.nwin_max ? left : p.nwin_max);
         g.ncore = (uint32_t)(left < ncore_span ? left : ncore_span);
         g.budget = p.budget;
-        g.kmax = p.kmax;
+        g.kmax = kTrMaxK;
         g.pcap = p.pcap;
         TrTables t{};
         t.bitmap = reinterpret_cast<uint32_t *>(base + p.o_bitmap);
@@ -3678,14 +3577,14 @@ void launch_index_trunk(const IdxWalk &w, TrunkPlan p, uint8_t *base, const uint
         // (... and where the regions are few: a wavefront's parse is mostly scalar work, and the one scalar unit of a CU
         // serves all its wavefronts -- measured on spans of 5167 regions: 4.5 ms against 6.1 for the lanes, whose time
         // is the latency of ONE region whatever their number)
-        const bool coop = tune("AEC_TR_COOP", nreg <= 6144u ? 1u : 0u) && w.c.id_len + 1u + w.c.bps + w.c.bs * w.c.bps + 128u <= 2048u;
+        const bool coop = nreg <= 6144u && w.c.id_len + 1u + w.c.bps + w.c.bs * w.c.bps + 128u <= 2048u;
         const uint32_t cgrid = nreg < 256u * 20u ? nreg : 256u * 20u;
         if (coop)
             hipLaunchKernelGGL(k_trunk_coop, dim3(cgrid), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)nullptr, ex[0], 0u);
         else
             hipLaunchKernelGGL(k_trunk, dim3((nreg + 63) / 64), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)nullptr, ex[0], 0u);
         uint32_t cur = 0;
-        for (uint32_t k = 0; k < p.passes; k++) {
+        for (uint32_t k = 0; k < kTrPasses; k++) {
             if (coop)
                 hipLaunchKernelGGL(k_trunk_coop, dim3(cgrid), dim3(64), 0, w.st, w.c, s, g, t, (const uint64_t *)ex[cur],
                                    ex[cur ^ 1u], 1u);
@@ -3707,20 +3606,19 @@ void launch_index_trunk(const IdxWalk &w, TrunkPlan p, uint8_t *base, const uint
             ls.counts = reinterpret_cast<uint32_t *>(base + 56);    // (behind the carry record and the pool counter)
             ls.qcap = p.co_qcap;
             ls.pcap = p.co_pcap;
-            ls.over_plain = p.co_over;
             (void)hipMemsetAsync(ls.counts, 0, 8, w.st);
             const uint32_t ng = (g.ncore + p.co_wpg - 1) / p.co_wpg;
             const size_t lds_wg = p.co_lds + sizeof(CoParked) * kCoPark + 64;          // (dynamic + the kernel's own)
             const uint32_t per_cu = (uint32_t)(160 * 1024 / lds_wg) ? (uint32_t)(160 * 1024 / lds_wg) : 1u;
             const uint32_t grid = ng < 256u * per_cu ? ng : 256u * per_cu;
             hipLaunchKernelGGL(k_hyp_walk_co, dim3(grid), dim3(256), p.co_lds, w.st, w.c, s, g, t, p.co_wpg, p.co_margin, ng,
-                               p.co_shift, p.co_tmax, p.co_cap, ls, p.co_park);
+                               kCoShift, kCoTmax, kCoCap, ls, kCoParkAt);
             hipLaunchKernelGGL(k_hyp_walk_rest, dim3((p.co_qcap + 63) / 64 < 16384u ? (p.co_qcap + 63) / 64 : 16384u), dim3(64), 0,
                                w.st, w.c, s, g, t, ls);
             hipLaunchKernelGGL(k_hyp_defer, dim3(g.ncore), dim3(256), 0, w.st, w.c, g, t, ls);
         } else if (p.staged) {
             const uint32_t grid = ngroups < 256u ? ngroups : 256u;                           // (one workgroup per CU)
-            hipLaunchKernelGGL((k_hyp_walk<true>), dim3(grid), dim3(1024), p.lds, w.st, w.c, s, g, t, p.wpw, p.margin, ngroups);
+            hipLaunchKernelGGL(k_hyp_walk, dim3(grid), dim3(1024), p.lds, w.st, w.c, s, g, t, p.wpw, p.margin, ngroups);
         } else {
             hipLaunchKernelGGL(k_hyp_walk_mem, dim3(ngroups), dim3(64), 0, w.st, w.c, s, g, t, p.wpw);
         }
@@ -3759,8 +3657,7 @@ void launch_index_trunk(const IdxWalk &w, TrunkPlan p, uint8_t *base, const uint
         if (w.d_seg_bits) {
             // (at most one RSI per minimal coded RSI of the span; a wavefront each, the rest in turn)
             const uint64_t most = (uint64_t)g.ncore * g.L / ((uint64_t)w.c.segs_per_rsi * (w.c.id_len + 2u)) + 2u;
-            const uint32_t gmax = tune("AEC_TR_SEG_GRID", 4096u);
-            const uint32_t grid = (uint32_t)(most < gmax ? most : gmax);
+            const uint32_t grid = (uint32_t)(most < kTrSegGrid ? most : kTrSegGrid);
             hipLaunchKernelGGL(k_seg_starts, dim3(grid), dim3(64), 0, w.st, w.c, s, g, t, w.d_rsi_off, carry, w.d_res,
                                w.d_seg_bits, w.max_rsi + 1u);
         }
@@ -3770,15 +3667,13 @@ void launch_index_trunk(const IdxWalk &w, TrunkPlan p, uint8_t *base, const uint
     if (tune_set("AEC_IDX_STATS")) {                       // (diagnostics: synchronises)
         IdxCarry h{};
         (void)hipStreamSynchronize(w.st);
-        const int dbg = tune("AEC_IDX_STATS", 0) >= 2 ? 1 : 0;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_serial), &dbg, sizeof(dbg));
         (void)hipMemcpy(&h, carry, sizeof(h), hipMemcpyDeviceToHost);
         uint32_t co_counts[2] = {0, 0};
         if (p.co) (void)hipMemcpy(co_counts, base + 56, 8, hipMemcpyDeviceToHost);
         fprintf(stderr, "trunk index: L %u lead %u rw %u kmax %u wpw %u nwin/span %u ncap %u | RSIs %llu, walked serially %u, "
                 "table lookups %u | coalescing %u (groups of %u windows + %u bits, %u-bit cells, %u parses): last span handed on "
-                "%u walks, left %u nodes to the plain walk\n", p.L, p.lead, p.rw, p.kmax, p.wpw, p.nwin_max, p.ncap,
-                (unsigned long long)h.r, h.n_serial, h.n_lookups, p.co, p.co_wpg, p.co_margin, 1u << p.co_shift, p.co_tmax,
+                "%u walks, left %u nodes to the plain walk\n", p.L, p.lead, p.rw, kTrMaxK, p.wpw, p.nwin_max, p.ncap,
+                (unsigned long long)h.r, h.n_serial, h.n_lookups, p.co, p.co_wpg, p.co_margin, 1u << kCoShift, kCoTmax,
                 co_counts[0], co_counts[1]);
     }
 #endif
@@ -3845,91 +3740,6 @@ __device__ __forceinline__ void lk_step(const TrStream &s, const Cfg &c, LkState
     if (x.b >= c.rsi) x.b = 0u;
 }
 
-// the guess for the entry of every region but the first: 64 chains from 64 places in front of it
-__global__ void __launch_bounds__(64)
-k_lock_guess(const Cfg c, const TrStream s, const LockTables t)
-{
-    if (t.skip_if && *t.skip_if) return;
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t r = 1u + blockIdx.x; r < t.nreg; r += gridDim.x) {
-        const uint64_t rstart = t.lo + (uint64_t)r * t.region_bits;
-        uint64_t from = rstart > t.lo + t.lead ? rstart - t.lead : t.lo;
-        LkState x{from + (uint64_t)lane * 37u, 0u, 0u};
-        // (a chain that cannot go on starts again one bit further: it is a guess either way)
-        uint32_t steps = 0;
-        const uint32_t most = 4u * (t.lead / (c.id_len + 1u) + 64u);
-        while (x.pos < rstart && steps++ < most) {
-            const uint32_t b_was = x.b;
-            lk_step(s, c, x);
-            if (x.st) {
-                if (x.st == 1u) break;
-                // (a zero run that does not fit the RSI by this chain's count: the count is wrong -- an RSI may start here;
-                // refused with the count at zero as well: one bit on)
-                if (b_was == 0u) x.pos++;
-                x.b = 0u;
-                x.st = 0u;
-            }
-        }
-        const bool have = x.st == 0u && x.pos >= rstart;
-        // the state most lanes stand on
-        uint64_t left = __ballot(have);
-        LkState best{rstart, 0u, 0u};
-        uint32_t best_n = 0;
-        for (uint32_t round = 0; round < 8u && left; round++) {
-            const uint32_t l0 = (uint32_t)__builtin_ctzll(left);
-            const uint64_t p0 = __shfl(x.pos, (int)l0);
-            const uint32_t b0 = (uint32_t)__shfl((int)x.b, (int)l0);
-            const uint64_t same = __ballot(have && x.pos == p0 && x.b == b0);
-            const uint32_t n = (uint32_t)__popcll(same);
-            if (n > best_n) {
-                best_n = n;
-                best = LkState{p0, b0, 0u};
-            }
-            left &= ~same;
-        }
-        if (lane == 0) t.entry[r] = best;
-    }
-}
-
-// mode 0: count from the guessed entries; 1: repair (regions whose entry is not the exit of the region in front)
-__global__ void __launch_bounds__(64)
-k_lock_walk(const Cfg c, const TrStream s, const LockTables t, const LkState *exit_prev, LkState *exit_out, uint32_t mode,
-            uint64_t start_bit, uint32_t start_block)
-{
-    if (t.skip_if && *t.skip_if) return;
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= t.nreg) return;
-    LkState x;
-    if (r == 0u) {
-        if (mode) {
-            exit_out[0] = exit_prev[0];
-            return;
-        }
-        x = LkState{start_bit, start_block, 0u};
-        t.entry[0] = x;
-    } else if (!mode) {
-        x = t.entry[r];
-    } else {
-        const LkState prev = exit_prev[r - 1u], mine = t.entry[r];
-        if (prev.st || (prev.pos == mine.pos && prev.b == mine.b)) {
-            exit_out[r] = exit_prev[r];
-            return;
-        }
-        x = LkState{prev.pos, prev.b, 0u};
-        t.entry[r] = x;
-    }
-    // (the last region has no end: its walk stops where the input does)
-    const uint64_t rend = r + 1u == t.nreg ? ~0ull : t.lo + (uint64_t)(r + 1u) * t.region_bits;
-    uint32_t n = 0;
-    while (x.pos < rend) {
-        n += x.b == 0u ? 1u : 0u;
-        lk_step(s, c, x);
-        if (x.st) break;
-    }
-    t.cnt[r] = n;
-    exit_out[r] = x;
-}
-
 // one workgroup: the first region in which the walk ended (those behind it are dead: nobody confirmed their
 // guesses), do the live regions agree, RSI starts in front of every region
 __global__ void __launch_bounds__(1024)
@@ -3986,97 +3796,6 @@ k_lock_scan(const LockTables t, const LkState *exit_last)
     }
 }
 
-// the RSI starts, and the result record; the first region in which the walk ended writes the record
-__global__ void __launch_bounds__(64)
-k_lock_fill(const Cfg c, const TrStream s, const LockTables t, const LkState *exit_last, const uint32_t *__restrict__ words,
-            uint64_t nwords, uint64_t *__restrict__ rsi_off, uint64_t max_rsi, DecResult *res, uint32_t tail_slot,
-            uint64_t rsi_start_in, uint32_t start_block)
-{
-    if (t.skip_if && *t.skip_if) return;
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= t.nreg || t.flags[1] || r > t.flags[2]) return;      // (not agreed, or behind the region that ended the walk)
-    const uint64_t rend = r + 1u == t.nreg ? ~0ull : t.lo + (uint64_t)(r + 1u) * t.region_bits;
-    LkState x = t.entry[r];
-    // A walk that resumes INSIDE an RSI (streaming callers: start_block blocks of it lie in front of the input): that
-    // RSI is number 0 and began at rsi_start_in, the first RSI start the chains meet is number 1 (as k_index counts).
-    const uint64_t off = start_block ? 1u : 0u;
-    uint64_t idx = t.base[r] + off;
-    if (off && r == 0u && max_rsi) rsi_off[0] = rsi_start_in;
-    // (regions behind the caller's bound have nothing to deliver: the ONE region in which RSI number max_rsi starts
-    // writes the record -- every region behind it would meet "idx >= max_rsi" at its first RSI start as well)
-    if (idx > max_rsi) return;
-    // the last RSI start in front of this region (the RSI the walk is in when it enters): found by walking the nearest
-    // region in front that met one -- only the lane that ends the walk asks
-    auto start_in_front = [&]() -> uint64_t {
-        for (uint32_t q = r; q-- > 0u;) {
-            if (!t.cnt[q]) continue;
-            LkState y = t.entry[q];
-            const uint64_t qend = t.lo + (uint64_t)(q + 1u) * t.region_bits;
-            uint64_t last = rsi_start_in;
-            while (y.pos < qend) {
-                if (y.b == 0u) last = y.pos;
-                lk_step(s, c, y);
-                if (y.st) break;
-            }
-            return last;
-        }
-        return rsi_start_in;
-    };
-    uint64_t cur = 0;                                    // start of the RSI the walk is in, if it began in this region
-    bool met = false, clipped = false;
-    while (x.pos < rend) {
-        if (x.b == 0u) {
-            if (idx == max_rsi) {                        // the caller's bound: ends on this RSI start
-                clipped = true;
-                break;
-            }
-            rsi_off[idx] = x.pos;
-            cur = x.pos;
-            met = true;
-            idx++;
-        }
-        lk_step(s, c, x);
-        if (x.st) break;
-    }
-    if (!clipped && !x.st) return;                       // the walk goes on in the next region
-    if (clipped) {
-        // (only the region that holds RSI number max_rsi gets here with idx == max_rsi at an RSI start)
-        res->n_rsi = max_rsi;
-        res->tail_blocks = 0;
-        res->end_bit = x.pos;
-        res->status = DEC_OK;                            // (the whole record: the walker behind does not start it then)
-        res->pad = 0u;
-        res->bad_rsi = ~0ull;
-        if (tail_slot) rsi_off[max_rsi] = met ? cur : start_in_front();
-        __threadfence();
-        t.flags[0] = 1u;
-        return;
-    }
-    // the walk ended here: only "the input ends inside this coded data set", confirmed by the sequential reader, is
-    // delivered; anything else is the serial walker's to report
-    if (x.st != 1u) return;
-    // (st 1 is also what a unary part beyond the parser's reach reports -- a foreign encoder's coded data set of 12 800
-    // bits: only within that reach of the end of the input does it mean that the input ended)
-    if (s.end_bit - x.pos > kTrMaxScan) return;
-    {
-        BitReaderT<QuadFetch> br;
-        br.init(QuadFetch{words, nwords}, s.end_bit, x.pos);
-        uint32_t nblk = 1;
-        if (skip_cds(br, c, (x.b == 0u && (c.flags & F_PREPROCESS)) ? 1u : 0u, x.b, nblk) != DEC_NEED_INPUT) return;
-    }
-    // RSI starts met = idx; the last of them began an RSI that is not complete (or nothing at all behind it)
-    if (idx == 0) return;                                // (cannot happen: the first state is an RSI start)
-    res->n_rsi = idx - 1u;
-    res->tail_blocks = x.b;
-    res->end_bit = x.pos;
-    res->status = DEC_OK;
-    res->pad = 1u;
-    res->bad_rsi = ~0ull;
-    if (tail_slot) rsi_off[max_rsi] = met ? cur : start_in_front();
-    __threadfence();
-    t.flags[0] = 1u;
-}
-
 // ---- the same three walks, a WAVEFRONT per region (round 5; aec_stretch.h) ---------------------------------------
 // A lane that follows a chain through device memory takes 2.5 us per coded data set, and the pass was three such walks
 // of a region one behind the other (guess, count, fill) plus a repair pass per wrong guess: 2.1 ms for a 64 KiB chunk
@@ -4084,8 +3803,9 @@ k_lock_fill(const Cfg c, const TrStream s, const LockTables t, const LkState *ex
 // core.  Here a wavefront owns the region: the 64 lanes parse the coded data sets that would begin at the next 64 bits,
 // with and without a reference sample, and the chain with the RSI's bookkeeping is a lane read per coded data set.  The
 // guess keeps its 64 chains per region, one per lane, but they parse out of the wavefront's LDS tables (they stand
-// within a few kbit of each other) instead of device memory.  Same states, same tables, same results as the kernels
-// above (tune AEC_IDX_LOCK_WAVE=0 runs those).
+// within a few kbit of each other) instead of device memory.  Same states, same tables, same results as the
+// lane-per-region walks of round 4, which were removed once every parameter set make_cfg admits fitted the wavefront's
+// look-ahead; k_lock_scan and lk_step are what is left of them.
 
 // one step of the bookkeeping from an entry; false = the entry does not resolve it (lk_step from memory then)
 __device__ __forceinline__ bool lk_apply(const Cfg &c, LkState &x, uint32_t e, uint32_t rf)
@@ -4347,6 +4067,13 @@ constexpr uint32_t kLpConfirmOk = 6;       // ... and how many of their options 
 constexpr uint32_t kLpPhased = 16;         // RSIs of fewer blocks: the scoring chains carry the count of blocks (find_anchor_phased)
 constexpr uint32_t kLpLost = 3;            // fewer than this along the plain chain: the walk has lost the true one
 constexpr uint32_t kLpSpan = 10240;        // bits of the window in front of the walk (a confirmation's coded data sets)
+constexpr uint32_t kLpCdsMin = 32;         // shortest mean coded data set guessed by plausibility: RSIs of up to kLockMaxRsi blocks, options of 4 bits ...
+constexpr uint32_t kLpCdsMinLong = 96;     // ... and any other shape
+constexpr uint32_t kLpCoopCds = 96;        // mean coded data sets from which on the walks parse one at a time (LockTables::coop)
+// the 64 agreeing chains (lock_plan): RSIs that code to this many bits at most take them whatever their blocks; the
+// lead-in is kLockLeadFactor x cds^2 x rsi bits, kLockLeadMin at least; a region is 1 / kLockRegionDiv of it, of
+// kLockRegionMin bits at least in a small stream
+constexpr uint32_t kLockTinyBits = 256, kLockLeadFactor = 2, kLockLeadMin = 4096, kLockRegionDiv = 16, kLockRegionMin = 1024;
 // (tests/emul-style check on the reference's sample file, 120 region starts: 116 entries right, 2 without an anchor in a
 // noisy stretch, 2 lost next to the start of the stream; with 12 steps, options within 1 and all of 5 confirmations: 22 of 31)
 
@@ -4776,7 +4503,7 @@ k_lock_fill_w(const Cfg c, const TrStream s, const LockTables t, const LkState *
     if (r >= t.nreg || t.flags[1] || t.flags[3] || r > t.flags[2]) return;
     const uint64_t rend = r + 1u == t.nreg ? ~0ull : t.lo + (uint64_t)(r + 1u) * t.region_bits;
     LkState x = t.entry[r];
-    const uint64_t off = start_block ? 1u : 0u;          // (k_lock_fill: a walk that resumes inside an RSI)
+    const uint64_t off = start_block ? 1u : 0u;          // (k_lock_fill_w: a walk that resumes inside an RSI)
     uint64_t idx = t.base[r] + off;
     if (off && r == 0u && max_rsi && lane == 0) rsi_off[0] = rsi_start_in;
     if (idx > max_rsi) return;
@@ -4892,8 +4619,7 @@ static LockPlan lock_plan_p(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits
     const uint64_t cds = rsi_bits_hint / c.rsi;
     // (RSIs of fewer than 16 blocks: a scoring chain of 16 coded data sets passes an RSI start or three -- there the
     // chains carry the count of blocks, one set of chains per count: k_lock_guess_p, find_anchor_phased)
-    const uint64_t cds_min = (c.rsi <= kLockMaxRsi && c.id_len >= 4u) ? (uint64_t)tune("AEC_IDX_LOCK_P_CDS", 32)
-                                                              : (uint64_t)tune("AEC_IDX_LOCK_P_CDS_LONG", 96);
+    const uint64_t cds_min = (c.rsi <= kLockMaxRsi && c.id_len >= 4u) ? kLpCdsMin : kLpCdsMinLong;
     if (cds < cds_min || c.rsi >= 8 * cds || c.segs_per_rsi >= 8u || total_bits < 4 * rsi_bits_hint) return p;
     if (c.id_len + 1u + c.bps + c.bs * c.bps > (kSwLookWords - 2u) * 32u) return p;
     // regions of 1 .. 8 RSIs: large streams pay the guess (two RSIs walked per region) less often, small ones get
@@ -4907,7 +4633,7 @@ static LockPlan lock_plan_p(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits
     const uint64_t nreg = (total_bits + region - 1) / region;
     if (nreg > (1u << 24) || region > 0xFFFFFFFFull) return p;
     p.mode = 1;
-    p.coop = cds >= (uint64_t)tune("AEC_IDX_LOCK_COOP_CDS", 96) ? 1u : 0u;
+    p.coop = cds >= kLpCoopCds ? 1u : 0u;
     p.nreg = (uint32_t)nreg;
     p.region_bits = (uint32_t)region;
     p.lead = 0;
@@ -4926,12 +4652,12 @@ LockPlan lock_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, ui
 {
     LockPlan p{};
     // (without the preprocessor no coded data set holds a reference sample: nothing a chain could lock its count on)
-    // (a walk that resumes inside an RSI numbers that RSI 0 and the first RSI start it meets 1: k_lock_fill)
+    // (a walk that resumes inside an RSI numbers that RSI 0 and the first RSI start it meets 1: k_lock_fill_w)
     (void)start_block;
     // RSIs of at most 32 blocks -- or of any number of blocks that code to next to nothing: constant data, fill values
     // (an RSI of 128 zero blocks is two coded data sets, 26 bits; as many candidates per window as the tables of neither
     // kind have room for, and the serial walk took 64 ms for 64 MiB of a constant)
-    const bool tiny = rsi_bits_hint != 0 && rsi_bits_hint <= tune("AEC_IDX_LOCK_TINY", 256u);
+    const bool tiny = rsi_bits_hint != 0 && rsi_bits_hint <= kLockTinyBits;
     if (!tune("AEC_IDX_LOCK", 1) || (c.flags & F_PAD_RSI) || !(c.flags & F_PREPROCESS)) return p;
     if (c.rsi > kLockMaxRsi && !tiny) return allow_p ? lock_plan_p(c, total_bits, rsi_bits_hint) : p;
     if (total_bits < (1u << 16)) return p;               // (a thousand coded data sets: the serial walker is as fast)
@@ -4944,9 +4670,8 @@ LockPlan lock_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, ui
     // halves the guesses' cost and is faster where it locks -- 16 MiB of 16-bit data, rsi 32: 8.8 against 10.6 ms -- but
     // its guesses are wrong in longer runs, and it moves streams of long coded data sets from the trunk to this scheme
     // with lead-ins of megabits: 16 MiB of 24-bit data in blocks of 64, rsi 16: 380 ms instead of 6.  2 it stays.)
-    uint64_t lead = (uint64_t)tune("AEC_IDX_LOCK_LEAD", 2) * cds * cds * c.rsi;
-    const uint64_t lmin = tune("AEC_IDX_LOCK_LMIN", 4096);
-    if (lead < lmin) lead = lmin;
+    uint64_t lead = (uint64_t)kLockLeadFactor * cds * cds * c.rsi;
+    if (lead < kLockLeadMin) lead = kLockLeadMin;
     // (long coded data sets: a lead-in that is a good part of the stream is as good as a serial walk -- 1 MiB of 16-bit
     // data in blocks of 32, rsi 16: 17 ms, five times the reference on one core -- where the options of real data tell
     // the true chain from the others in a dozen coded data sets: mode 1)
@@ -4956,7 +4681,7 @@ LockPlan lock_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, ui
     // more -- with three, 8-bit data, half of the guesses are wrong: 16 MiB of 16-bit data in blocks of 16, rsi 32: 11.3
     // -> 3.2 ms, rsi 16: 6.4 -> 2.9; a walk to the next RSI start is 32 coded data sets at most)
     if (allow_p && ((cds >= 96 && (lead * 8 > total_bits || c.rsi < kLpPhased)) ||
-                    (c.rsi >= kLpPhased && c.id_len >= 4u && cds >= (uint64_t)tune("AEC_IDX_LOCK_P_CDS", 32)))) {
+                    (c.rsi >= kLpPhased && c.id_len >= 4u && cds >= kLpCdsMin))) {
         const LockPlan q = lock_plan_p(c, total_bits, rsi_bits_hint);
         if (q.ok) return q;
     }
@@ -4964,11 +4689,10 @@ LockPlan lock_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint, ui
     if (lead > (1u << 24) || (lead > (1u << 22) && total_bits < 4 * lead))
         return allow_p ? lock_plan_p(c, total_bits, rsi_bits_hint) : p;
     // (small streams: short regions -- the pass is as long as one lane's walk of a region, three times over)
-    const uint64_t rmin = total_bits < (1u << 22) ? tune("AEC_IDX_LOCK_RMIN", 1024) : 16384;
+    const uint64_t rmin = total_bits < (1u << 22) ? kLockRegionMin : 16384;
     // (a region per wavefront now: regions a fraction of the lead-in, so that the walks -- one behind the other: count,
     // repairs, fill -- are short and the chip has wavefronts to run; the guesses cost the lead-in per region either way)
-    const uint64_t rdiv = tune("AEC_IDX_LOCK_DIV", 16);
-    uint64_t region = lead / (rdiv ? rdiv : 1) < rmin ? rmin : lead / (rdiv ? rdiv : 1);
+    uint64_t region = lead / kLockRegionDiv < rmin ? rmin : lead / kLockRegionDiv;
     region = (region + 1023) & ~1023ull;
     const uint64_t nreg = (total_bits + region - 1) / region;
     if (nreg > (1u << 24)) return p;
@@ -5020,128 +4744,69 @@ void launch_index_locked(const IdxWalk &w, const LockPlan &p, uint8_t *base, boo
     t.skip_if = skip_if;
     t.lo = w.start_bit;
     (void)hipMemsetAsync(t.flags, 0, 64, w.st);
-    // a wavefront per region (k_lock_*_w) -- unless the parameters are beyond its tables' look-ahead
-    const bool wave = p.mode == 1u ||
-                      (tune("AEC_IDX_LOCK_WAVE", 1) != 0 && w.c.id_len + 1u + w.c.bps + w.c.bs * w.c.bps <= (kSwLookWords - 2u) * 32u);
+    // a wavefront per region (k_lock_*_w): the longest coded data set make_cfg admits -- id_len 5, 32 bits per sample,
+    // blocks of 64: 2086 bits -- lies within its tables' look-ahead
+    static_assert(5u + 1u + 32u + 64u * 32u <= (kSwLookWords - 2u) * 32u, "a coded data set beyond the look-ahead");
     const uint32_t wpw = 4;                                             // wavefronts per workgroup
     const size_t wlds = (size_t)wpw * kSwWaveWords * 4;
-    if (wave) {
-        LkState *ex[2] = {t.exit0, t.exit1};
-        if (p.nreg > 1 && p.mode == 1u)
-            hipLaunchKernelGGL(k_lock_guess_p, dim3(p.nreg - 1), dim3(64), (size_t)sw_wave_words(kLpPiece) * 4, w.st, w.c, s, t, p.back);
-        else if (p.nreg > 1)
-            hipLaunchKernelGGL(k_lock_guess_w, dim3((p.nreg - 1 + wpw - 1) / wpw), dim3(64 * wpw), wlds, w.st, w.c, s, t);
-        const uint32_t wg = (p.nreg + wpw - 1) / wpw;
-        LkState *en[2] = {t.entry, reinterpret_cast<LkState *>(base + p.o_entry1)};
-        hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)nullptr, ex[0], en[0], 0u,
-                           w.start_bit, w.start_block);
-        if (p.mode == 1u) hipLaunchKernelGGL(k_lock_judge, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[0]);
-#ifdef AEC_TUNING
-        if (tune_set("AEC_IDX_DUMP")) {                    // (diagnostics: the guesses against the exits in front)
-            (void)hipStreamSynchronize(w.st);
-            std::vector<LkState> en0(p.nreg), ex0(p.nreg);
-            (void)hipMemcpy(en0.data(), en[0], p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(ex0.data(), ex[0], p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
-            uint32_t shown = 0;
-            for (uint32_t r = 1; r < p.nreg && shown < 24; r++) {
-                const bool mis = ex0[r - 1].pos != en0[r].pos || ex0[r - 1].b != en0[r].b;
-                if (!mis && r > 6) continue;
-                shown++;
-                fprintf(stderr, "  region %u (from bit %llu): guess (%llu, %u) | exit in front (%llu, %u, st %u)%s\n", r,
-                        (unsigned long long)(w.start_bit + (uint64_t)r * p.region_bits), (unsigned long long)en0[r].pos, en0[r].b,
-                        (unsigned long long)ex0[r - 1].pos, ex0[r - 1].b, ex0[r - 1].st, mis ? "  <-- differ" : "");
-            }
-        }
-#endif
-        uint32_t cur = 0;
-        // a few parallel repair passes (each mends the first region of every run of regions in doubt; an idle one is a
-        // launch of 5 us, and 48 of them were a quarter of a millisecond on a 64 KiB chunk), then one wavefront mends
-        // what is left run by run at the speed of the walk
-        // (a small chunk: four passes -- one costs as much as the walk of a region, which is what the wavefront behind
-        // them takes per region it mends; sixteen were 0.19 of the 0.59 ms of a 64 KiB chunk.  Not for 16 MiB: 16-bit
-        // data with rsi 32 went from 11 to 33 ms with four.)
-        const uint32_t passes = tune("AEC_IDX_LOCK_PASSES", p.mode == 1u ? 8u : p.nreg <= 256u ? 4u : 16u);
-        for (uint32_t k = 0; k < passes; k++) {
-            t.entry = en[cur];
-            hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u],
-                               en[cur ^ 1u], 1u, w.start_bit, w.start_block);
-            cur ^= 1u;
-        }
-        t.entry = en[cur];
-        hipLaunchKernelGGL(k_lock_fix_w, dim3(1), dim3(64), (size_t)kSwWaveWords * 4, w.st, w.c, s, t, ex[cur]);
-        hipLaunchKernelGGL(k_lock_scan, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[cur]);
-        hipLaunchKernelGGL(k_lock_fill_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)ex[cur], w.words, w.nwords,
-                           w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, w.rsi_start, w.start_block);
-#ifdef AEC_TUNING
-        if (tune_set("AEC_IDX_STATS")) {                   // (diagnostics: synchronises)
-            (void)hipStreamSynchronize(w.st);
-            uint32_t fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            (void)hipMemcpy(fl, t.flags, 32, hipMemcpyDeviceToHost);
-            std::vector<LkState> en(p.nreg), exs(p.nreg);
-            (void)hipMemcpy(en.data(), t.entry, p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(exs.data(), ex[cur], p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
-            uint32_t mism = 0;
-            for (uint32_t r = 1; r < p.nreg; r++) mism += exs[r - 1].st == 0 && (exs[r - 1].pos != en[r].pos || exs[r - 1].b != en[r].b);
-            if (p.mode == 1u) {
-                unsigned long long h[16];
-                (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_lp_prof), sizeof(h));
-                const double n = p.nreg > 1 ? p.nreg - 1 : 1, us = 1e-2;   // (100 MHz shader clock counter)
-                fprintf(stderr, "guesses, per region: %.1f us (anchors %.2f: %.1f us; walk %.0f steps with %.1f confirmations: %.1f us; "
-                        "all but the exact walk %.1f us), %.1f parses from device memory; RSI start found %.0f%%, in front of the "
-                        "region %.0f%% | the slowest: %.1f us (%.1f without the exact walk), most steps %llu, most new anchors %llu; chain lost %llu times\n",
-                        h[6] / n * us, h[1] / n, h[0] / n * us, h[5] / n, h[3] / n, h[2] / n * us, h[4] / n * us,
-                        h[7] / n, 100.0 * h[8] / n, 100.0 * h[9] / n, h[10] * us, h[13] * us, h[11], h[12], h[14]);
-                unsigned long long z[16] = {0};
-                (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lp_prof), z, sizeof(z));
-            }
-            fprintf(stderr, "locked chains (mode %u): %u regions of %u bits | delivered %u, inconsistent %u, walk ended in region %u, "
-                    "abandoned %u | guesses that did not hold after the first walk: %u; entries that are not the exit in front "
-                    "after repairs: %u\n", p.mode, p.nreg, p.region_bits, fl[0], fl[1], fl[2], fl[3], fl[4], mism);
-        }
-#endif
-        if (skip_if) hipLaunchKernelGGL(k_lock_merge, dim3(1), dim3(1), 0, w.st, t.flags, skip_if);
-        if (final) go_index(w, {.skip_if = t.flags});    // (else the next scheme is enqueued behind, skipped if this delivered)
-        return;
-    }
-    if (p.nreg > 1)
-        hipLaunchKernelGGL(k_lock_guess, dim3(p.nreg - 1 < 65536u ? p.nreg - 1 : 65536u), dim3(64), 0, w.st, w.c, s, t);
-    const uint32_t wgrid = (p.nreg + 63) / 64;
     LkState *ex[2] = {t.exit0, t.exit1};
-    hipLaunchKernelGGL(k_lock_walk, dim3(wgrid), dim3(64), 0, w.st, w.c, s, t, (const LkState *)nullptr, ex[0], 0u, w.start_bit,
-                       w.start_block);
+    if (p.nreg > 1 && p.mode == 1u)
+        hipLaunchKernelGGL(k_lock_guess_p, dim3(p.nreg - 1), dim3(64), (size_t)sw_wave_words(kLpPiece) * 4, w.st, w.c, s, t, p.back);
+    else if (p.nreg > 1)
+        hipLaunchKernelGGL(k_lock_guess_w, dim3((p.nreg - 1 + wpw - 1) / wpw), dim3(64 * wpw), wlds, w.st, w.c, s, t);
+    const uint32_t wg = (p.nreg + wpw - 1) / wpw;
+    LkState *en[2] = {t.entry, reinterpret_cast<LkState *>(base + p.o_entry1)};
+    hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)nullptr, ex[0], en[0], 0u,
+                       w.start_bit, w.start_block);
+    if (p.mode == 1u) hipLaunchKernelGGL(k_lock_judge, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[0]);
     uint32_t cur = 0;
-    // (a stretch of k regions with wrong guesses -- incompressible data, where a chain needs far longer to lock -- takes
-    // k passes; a pass with nothing to repair is a few microseconds)
-    const uint32_t passes = tune("AEC_IDX_LOCK_PASSES", 48);
+    // a few parallel repair passes (each mends the first region of every run of regions in doubt; an idle one is a
+    // launch of 5 us, and 48 of them were a quarter of a millisecond on a 64 KiB chunk), then one wavefront mends
+    // what is left run by run at the speed of the walk
+    // (a small chunk: four passes -- one costs as much as the walk of a region, which is what the wavefront behind
+    // them takes per region it mends; sixteen were 0.19 of the 0.59 ms of a 64 KiB chunk.  Not for 16 MiB: 16-bit
+    // data with rsi 32 went from 11 to 33 ms with four.)
+    const uint32_t passes = p.mode == 1u ? 8u : p.nreg <= 256u ? 4u : 16u;
     for (uint32_t k = 0; k < passes; k++) {
-        hipLaunchKernelGGL(k_lock_walk, dim3(wgrid), dim3(64), 0, w.st, w.c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u], 1u,
-                           w.start_bit, w.start_block);
+        t.entry = en[cur];
+        hipLaunchKernelGGL(k_lock_walk_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)ex[cur], ex[cur ^ 1u],
+                           en[cur ^ 1u], 1u, w.start_bit, w.start_block);
         cur ^= 1u;
     }
+    t.entry = en[cur];
+    hipLaunchKernelGGL(k_lock_fix_w, dim3(1), dim3(64), (size_t)kSwWaveWords * 4, w.st, w.c, s, t, ex[cur]);
     hipLaunchKernelGGL(k_lock_scan, dim3(1), dim3(1024), 0, w.st, t, (const LkState *)ex[cur]);
-    hipLaunchKernelGGL(k_lock_fill, dim3(wgrid), dim3(64), 0, w.st, w.c, s, t, (const LkState *)ex[cur], w.words, w.nwords,
+    hipLaunchKernelGGL(k_lock_fill_w, dim3(wg), dim3(64 * wpw), wlds, w.st, w.c, s, t, (const LkState *)ex[cur], w.words, w.nwords,
                        w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, w.rsi_start, w.start_block);
 #ifdef AEC_TUNING
-    if (tune_set("AEC_IDX_STATS")) {                       // (diagnostics: synchronises)
+    if (tune_set("AEC_IDX_STATS")) {                   // (diagnostics: synchronises)
         (void)hipStreamSynchronize(w.st);
-        uint32_t fl[4] = {0, 0, 0, 0};
-        (void)hipMemcpy(fl, t.flags, 16, hipMemcpyDeviceToHost);
+        uint32_t fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        (void)hipMemcpy(fl, t.flags, 32, hipMemcpyDeviceToHost);
         std::vector<LkState> en(p.nreg), exs(p.nreg);
         (void)hipMemcpy(en.data(), t.entry, p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
         (void)hipMemcpy(exs.data(), ex[cur], p.nreg * sizeof(LkState), hipMemcpyDeviceToHost);
-        uint32_t mism = 0, ended = 0, refused = 0;
+        uint32_t mism = 0;
         for (uint32_t r = 1; r < p.nreg; r++) mism += exs[r - 1].st == 0 && (exs[r - 1].pos != en[r].pos || exs[r - 1].b != en[r].b);
-        for (uint32_t r = 0; r < p.nreg; r++) {
-            ended += exs[r].st == 1;
-            refused += exs[r].st == 2;
+        if (p.mode == 1u) {
+            unsigned long long h[16];
+            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_lp_prof), sizeof(h));
+            const double n = p.nreg > 1 ? p.nreg - 1 : 1, us = 1e-2;   // (100 MHz shader clock counter)
+            fprintf(stderr, "guesses, per region: %.1f us (anchors %.2f: %.1f us; walk %.0f steps with %.1f confirmations: %.1f us; "
+                    "all but the exact walk %.1f us), %.1f parses from device memory; RSI start found %.0f%%, in front of the "
+                    "region %.0f%% | the slowest: %.1f us (%.1f without the exact walk), most steps %llu, most new anchors %llu; chain lost %llu times\n",
+                    h[6] / n * us, h[1] / n, h[0] / n * us, h[5] / n, h[3] / n, h[2] / n * us, h[4] / n * us,
+                    h[7] / n, 100.0 * h[8] / n, 100.0 * h[9] / n, h[10] * us, h[13] * us, h[11], h[12], h[14]);
+            unsigned long long z[16] = {0};
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lp_prof), z, sizeof(z));
         }
-        fprintf(stderr, "locked chains: %u regions of %u bits, lead %u | delivered %u, inconsistent %u, walk ended in region %u | "
-                "entries that are not the exit in front: %u, regions ended %u, refused %u\n", p.nreg, p.region_bits, p.lead, fl[0],
-                fl[1], fl[2], mism, ended, refused);
+        fprintf(stderr, "locked chains (mode %u): %u regions of %u bits | delivered %u, inconsistent %u, walk ended in region %u, "
+                "abandoned %u | guesses that did not hold after the first walk: %u; entries that are not the exit in front "
+                "after repairs: %u\n", p.mode, p.nreg, p.region_bits, fl[0], fl[1], fl[2], fl[3], fl[4], mism);
     }
 #endif
     if (skip_if) hipLaunchKernelGGL(k_lock_merge, dim3(1), dim3(1), 0, w.st, t.flags, skip_if);
-    if (final) go_index(w, {.skip_if = t.flags});
+    if (final) go_index(w, {.skip_if = t.flags});    // (else the next scheme is enqueued behind, skipped if this delivered)
 }
 
 // ---- small streams: EVERY bit parsed, the chain of RSI starts by pointer doubling ---------------------------------
@@ -5162,6 +4827,10 @@ void launch_index_locked(const IdxWalk &w, const LockPlan &p, uint8_t *base, boo
 constexpr uint64_t kSmMaxBits = 1ull << 24;      // 2 MiB of stream
 constexpr uint32_t kSmMaxRsi = 64;               // (step 2 is rsi dependent loads per bit)
 constexpr uint32_t kSmGrid = 4096;               // most workgroups of 256 per launch (16 per CU); the kernels stride
+constexpr uint64_t kSmPpBits = 1ull << 25;       // small_plan: streams this long at most, in place of guesses by plausibility
+constexpr uint64_t kSmLongRsiBits = 1ull << 20;  // ... and with RSIs of more than kSmMaxRsi blocks where the window tables serve the stream
+constexpr uint32_t kSmHopRsi = 16;               // RSIs of more blocks: step 2 goes through a table of hops
+constexpr uint64_t kSmFbBits = 1ull << 28, kSmFbBitsLong = 1ull << 25;   // small_fallback_plan: RSIs of fewer than 64 blocks, of more
 
 struct SmallPlan {
     bool ok;
@@ -5200,21 +4869,20 @@ static SmallPlan small_plan(const Cfg &c, uint64_t total_bits, uint64_t max_rsi,
     //    long as this scheme's pass (4 MiB of 16-bit data, rsi 256: 4.2 of 7.2 ms when they are judged wrong, 5.4 against
     //    3.0 when they hold; 1 MiB of 8-bit data in blocks of 32, rsi 64: 1.5 against 0.45)
     //    (RSIs of more than 32 blocks; with 16 .. 32 the guesses are cheap: 16 MiB of 16-bit data, rsi 32: 2.9 against 3.5 ms)
-    const bool by_plausibility = pp && c.rsi > kLockMaxRsi && total_bits <= (uint64_t)tune("AEC_IDX_SMALL_PP_BITS", 1u << 25) &&
+    const bool by_plausibility = pp && c.rsi > kLockMaxRsi && total_bits <= kSmPpBits &&
                                  lock_plan(c, total_bits, rsi_bits_hint, start_block).mode == 1u;
     const bool pp_pieces = pp && (forced || by_plausibility);
-    if (total_bits > kSmMaxBits && ((pp && !pp_pieces) || (c.rsi > kSmMaxRsi && c.bps <= 8u) || !tune("AEC_IDX_SMALL_PIECES", 1) ||
-                                    total_bits >= (1ull << 40)))
+    if (total_bits > kSmMaxBits && ((pp && !pp_pieces) || (c.rsi > kSmMaxRsi && c.bps <= 8u) || total_bits >= (1ull << 40)))
         return p;
     //  * RSIs of more than 256 blocks (hops of hops): one piece;
-    if (c.rsi > 256u && (total_bits > kSmMaxBits || !tune("AEC_IDX_SMALL_HOP2", 1))) return p;
+    if (c.rsi > 256u && total_bits > kSmMaxBits) return p;
     //  * with the preprocessor, where the window tables serve the stream: RSIs of up to 44 blocks always (the tables do
     //    not resolve them); 45 .. 64 up to 512 KiB of stream (5 MiB of 8-bit data with rsi 64: 1.1 against 1.7 ms); more
     //    than 64 up to 128 KiB (the 8-bit SZIP shape, rsi 128: 64 KiB 0.24 -> 0.19 ms, 1 MiB 0.39 against 0.49).  Where
     //    the tables do not serve it -- long coded data sets, high entropy -- the stream would go over the trunk, whose
     //    dozen launches cost a 1 MiB stream 4 .. 9 ms: here it stays.
     if (pp && c.rsi > kLockMaxRsi && !forced && !by_plausibility) {
-        const uint64_t most_bits = c.rsi <= (uint32_t)tune("AEC_IDX_SMALL_RSI", kSmMaxRsi) ? (1u << 22) : (uint64_t)tune("AEC_IDX_SMALL_RSI_BITS", 1u << 20);
+        const uint64_t most_bits = c.rsi <= kSmMaxRsi ? (1u << 22) : kSmLongRsiBits;
         if (total_bits > most_bits && sparse2_plan(c, total_bits, rsi_bits_hint).ok) return p;
     }
     const uint64_t piece = total_bits < kSmMaxBits ? total_bits : kSmMaxBits;
@@ -5238,7 +4906,7 @@ static SmallPlan small_plan(const Cfg &c, uint64_t total_bits, uint64_t max_rsi,
     p.o_jb = p.o_e0;                                     // (the second table of the doubling: over the parses, done with by then)
     p.o_ja = o;    o = up(o + ((size_t)p.nbits + 1) * 4);
     p.o_s = o;     o = up(o + (size_t)p.scap * 4);
-    p.hops = c.rsi > 256u ? 2u : (c.rsi > (uint32_t)tune("AEC_IDX_SMALL_HOP_RSI", 16) ? 1u : 0u);
+    p.hops = c.rsi > 256u ? 2u : (c.rsi > kSmHopRsi ? 1u : 0u);
     p.o_h = o;
     if (p.hops) o = up(o + ((size_t)p.nbits + 1) * 4);
     p.o_h2 = o;
@@ -5484,9 +5152,8 @@ static void launch_index_small(const IdxWalk &w, const SmallPlan &p, uint8_t *ba
             hipLaunchKernelGGL(k_small_double, dim3(g), dim3(256), 0, w.st, (const SmCursor *)cur, w.end_bit, p.nbits,
                                (const uint32_t *)j[k & 1u], j[(k & 1u) ^ 1u], sidx, quarter, p.scap, last);
         }
-        if (tune("AEC_IDX_SMALL_FINISH", 1))
-            hipLaunchKernelGGL(k_small_finish, dim3(1), dim3(1024), 0, w.st, w.c, s, cur, p.nbits, (const uint32_t *)sidx, p.scap, w.words,
-                               w.nwords, w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, flags, w.start_block);
+        hipLaunchKernelGGL(k_small_finish, dim3(1), dim3(1024), 0, w.st, w.c, s, cur, p.nbits, (const uint32_t *)sidx, p.scap, w.words,
+                           w.nwords, w.d_rsi_off, w.max_rsi, w.d_res, w.tail_slot, flags, w.start_block);
     }
     // whatever was not delivered: the serial walker, which returns at once otherwise
     go_index(w, {.skip_if = flags});
@@ -5591,19 +5258,6 @@ k_bsmall_finish(const Cfg c, const uint32_t *__restrict__ words, uint64_t nwords
 
 }  // namespace
 
-// (tuning build: the A/B switches that live in device globals)
-static void idx_tuning_sync()
-{
-#ifdef AEC_TUNING
-    static const int no_stretch = tune("AEC_IDX_STRETCH", 1) == 0 ? 1 : 0;
-    static std::once_flag once[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) dev = 0;
-    std::call_once(once[dev], [] { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_idx_no_stretch), &no_stretch, sizeof(int)); });
-#endif
-}
-
 // The every-bit scheme as the FALLBACK behind a scheme that may give a stream up (round 6; tests/fuzz_index_gpu.py --time
 // listed thirteen shapes of 300 below 0.6 GB/s, all of them such streams):
 //  * behind the chains by plausibility (lock_plan mode 1), in place of the 64 agreeing chains and the trunk, which took
@@ -5615,12 +5269,10 @@ static void idx_tuning_sync()
 static SmallPlan small_fallback_plan(const Cfg &c, uint64_t total_bits, uint64_t max_rsi, uint32_t start_block,
                                      uint64_t rsi_bits_hint, bool behind_tables)
 {
-    if (!tune("AEC_IDX_SMALL_FALLBACK", 1)) return SmallPlan{};
     // (behind the chains by plausibility: RSIs of 64 blocks and more are the trunk's from 4 MiB of stream on -- its
     // block counts take 27 MiB with rsi 64 in 3 ms, the pieces 21 -- and below that its dozen launches cost more than
     // the pieces: 4 MiB of 16-bit data with rsi 256: 9.9 against 3.0 ms)
-    const uint64_t most = behind_tables ? kSmMaxBits
-                          : (c.rsi < 64u ? (uint64_t)tune("AEC_IDX_SMALL_FB_BITS", 1u << 28) : (uint64_t)tune("AEC_IDX_SMALL_FB_BITS_LONG", 1u << 25));
+    const uint64_t most = behind_tables ? kSmMaxBits : (c.rsi < 64u ? kSmFbBits : kSmFbBitsLong);
     if (total_bits > most) return SmallPlan{};
     return small_plan(c, total_bits, max_rsi, start_block, rsi_bits_hint, true);
 }
@@ -5774,7 +5426,6 @@ bool launch_index(const Cfg &c, const uint8_t *d_in, size_t in_bytes, uint64_t s
 {
     const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, start_bit,
                     d_rsi_off, max_rsi, d_res, st, start_block, tail_slot, rsi_start, d_seg_bits, stop_near};
-    idx_tuning_sync();
     const IdxOpt o{.start_block = start_block, .max_rsi = max_rsi, .segments = d_seg_bits != nullptr, .piece = stop_near != 0,
                    .ws_bytes = d_ws ? ws_bytes : 0};
     const IdxChain ch = index_chain(c, in_bytes, start_bit, rsi_bits_hint, o);
@@ -5827,7 +5478,6 @@ void launch_index_batch(const Cfg &c, const uint8_t *d_in, size_t in_bytes, cons
                         hipStream_t st, void *d_ws, size_t ws_bytes, size_t max_chunk_bytes, uint64_t rsi_bits_hint)
 {
     if (n_chunks == 0) return;
-    idx_tuning_sync();
     // (every stream a walk of its own from its first bit: rsi_per_chunk offsets and a result record each)
     const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, 0, d_rsi_off,
                     rsi_per_chunk, d_res, st, 0u, 0u, 0, nullptr, 0};
@@ -5865,7 +5515,6 @@ void launch_index_chunks(const Cfg &c, const uint8_t *d_in, size_t in_bytes, con
                          uint8_t *ws, uint32_t *d_how)
 {
     if (n_chunks == 0) return;
-    idx_tuning_sync();
     const IdxWalk w{c, reinterpret_cast<const uint32_t *>(d_in), (in_bytes + 3) / 4, (uint64_t)in_bytes * 8, 0, d_rsi_off,
                     0, d_res, st, 0u, 0u, 0, nullptr, 0};
     const bool every_bit = plan && rounds && ws && plan->taken;

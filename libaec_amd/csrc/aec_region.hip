@@ -315,7 +315,7 @@ k_rg_scan(const RgTables t, uint32_t cur)
 }
 
 // the RSI starts (and segment starts), and the result record: written by the region in which the walk ended or the
-// caller's bound was met (as k_lock_fill of aec_idx.hip, whose record conventions these are)
+// caller's bound was met (as k_lock_fill_w of aec_idx.hip, whose record conventions these are)
 __global__ void __launch_bounds__(64)
 k_rg_fill(const Cfg c, const TrStream s, const RgTables t, uint32_t cur, uint64_t *__restrict__ rsi_off, uint64_t max_rsi,
           DecResult *res, uint32_t tail_slot, uint64_t rsi_start_in, uint32_t start_block, uint64_t *__restrict__ seg_bits)
@@ -496,12 +496,10 @@ RegionPlan region_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint
     if (c.rsi < 48u || cds < 8u) return p;
     // regions: enough of them to fill the chip's lanes a few times over (the passes are as long as one lane's walk), but
     // of a few RSIs, 16 kbit at least: the guess walks an RSI or two whatever the region's size
-    uint64_t region = (uint64_t)tune("AEC_IDX_REGION_BITS", 0);
-    if (!region) {
-        region = total_bits / (uint64_t)tune("AEC_IDX_REGION_LANES", 196608);
-        const uint64_t rmin = rsi_bits_hint > 16384 ? rsi_bits_hint : 16384;
-        if (region < rmin) region = rmin;
-    }
+    constexpr uint64_t kRgLanes = 196608;                // (three regions per lane of the chip)
+    uint64_t region = total_bits / kRgLanes;
+    const uint64_t rmin = rsi_bits_hint > 16384 ? rsi_bits_hint : 16384;
+    if (region < rmin) region = rmin;
     region = (region + 63) & ~63ull;
     const uint64_t nreg = (total_bits + region - 1) / region;
     // (long coded data sets -- config 3, the sample file: a region is an RSI and a lane's walk of it takes milliseconds
@@ -509,14 +507,14 @@ RegionPlan region_plan(const Cfg &c, uint64_t total_bits, uint64_t rsi_bits_hint
     // (and only where RSIs have eight segments and more: shorter ones with long coded data sets -- the sample file -- are
     // the plausibility scheme's of aec_idx.hip, a wavefront per region: 16 against 24 ms per GiB)
     if (cds > 128u && c.segs_per_rsi < 8u) return p;
-    if (nreg < (cds > 128u ? (uint64_t)tune("AEC_IDX_REGIONS_LONG", 3072) : 16u) || nreg > (1u << 22)) return p;
+    if (nreg < (cds > 128u ? 3072u : 16u) || nreg > (1u << 22)) return p;
     p.nreg = (uint32_t)nreg;
     p.region_bits = region;
     p.avg_cds = (uint32_t)(rsi_bits_hint / c.rsi);
     // (the guess: an anchor -- two parses per bit of a coded data set --, the walk to an RSI start, tests, and the
     // candidate's RSI once more where RSIs are short; three-bit options say less: more of it)
-    p.budget = tune("AEC_IDX_REGION_BUDGET", (uint32_t)((c.rsi <= kRgVerifyMaxRsi ? (c.id_len <= 3u ? 4u : 3u) : 2u) * c.rsi + 384u + 3u * cds));
-    p.passes = tune("AEC_IDX_REGION_PASSES", 8);
+    p.budget = (uint32_t)((c.rsi <= kRgVerifyMaxRsi ? (c.id_len <= 3u ? 4u : 3u) : 2u) * c.rsi + 384u + 3u * cds);
+    p.passes = 8;                                        // (mending passes)
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t o = 0;
     p.o_flags = o;  o = up(o + 64);
@@ -563,7 +561,7 @@ void launch_index_regions(const IdxWalk &w, const RegionPlan &p, uint8_t *base, 
     (void)hipMemsetAsync(t.flags, 0, 64, w.st);
     const uint32_t wg = (p.nreg + 63u) / 64u;
     const uint32_t gwg = wg < 2560u ? wg : 2560u;        // (the guesses come from a queue: as many wavefronts as the chip holds)
-    const bool small_ring = p.avg_cds <= (uint32_t)tune("AEC_IDX_REGION_RING32", 32);
+    const bool small_ring = p.avg_cds <= 32u;           // (short coded data sets: the ring of 32 words)
     hipLaunchKernelGGL(k_rg_guess, dim3(gwg), dim3(64), rg_lds_bytes(64u), w.st, w.c, s, t);
     hipLaunchKernelGGL(k_rg_link, dim3((p.nreg + 255u) / 256u), dim3(256), 0, w.st, t, w.start_bit, w.start_block);
     hipLaunchKernelGGL(k_rg_judge, dim3(1), dim3(1), 0, w.st, t);

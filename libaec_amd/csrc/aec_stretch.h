@@ -9,7 +9,7 @@
 // 1-bit behind the header, ones[rank(q1) + n - 1] (aec_spec.h) -- so the 64 lanes parse the coded data sets that would
 // begin at 64 CONSECUTIVE bits at once, with and without a reference sample, and the chain through those 64 bits is
 // one lane read per coded data set (~0.5 us per 64 bits + 0.05 us per coded data set).  The same tables also serve 64
-// chains of a wavefront that stand near each other (k_lock_guess): every lane parses at its OWN position.
+// chains of a wavefront that stand near each other (k_lock_guess_w): every lane parses at its OWN position.
 // Whatever the tables do not resolve (a coded data set longer than an encoder writes, the end of the stream) is the
 // caller's to take with tr_cds: entries are exact or 0, never wrong.
 #pragma once

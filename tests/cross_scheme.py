@@ -117,6 +117,9 @@ def main():
                (8, 8, 128, PP, 20 * MiB, 1.2), (16, 64, 256, PP | MSB, 20 * MiB, 40.0)]
     # AEC_PAD_RSI: every RSI begins on a byte (the every-bit scheme from round 6 on, the trunk, the serial walker)
     shapes += [(16, 16, 8, PP | PAD, 100 * KiB, 2.0), (8, 8, 64, PP | PAD | MSB, 600 * KiB, 1.2), (16, 16, 128, PAD, 600 * KiB, 30.0)]
+    # long RSIs of long coded data sets (noise of ~12 bits: 106 bits a coded data set, rsi >= 8 of them): the trunk's
+    # coalescing walks (k_hyp_walk_co, k_hyp_walk_rest, k_hyp_defer), which no shape above reaches
+    shapes += [(16, 8, 1024, PP, 3 * MiB, 12000.0)]
     want = None
     if args.narrow:
         import narrow_cases
