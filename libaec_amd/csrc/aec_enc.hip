@@ -111,6 +111,10 @@ __device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill)
     return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false);               // wave_shr:1
 }
 __device__ __forceinline__ uint32_t wave_last(uint32_t v) { return __builtin_amdgcn_readlane(v, 63); }
+// a wave-uniform value the optimiser cannot trace to its source from here on (no instruction; it stays a scalar register):
+// what is derived from it is computed where it is used and not hoisted to live across a whole loop
+__device__ __forceinline__ void uniform_opaque(uint32_t &v) { asm volatile("" : "+s"(v)); }
+__device__ __forceinline__ void uniform_opaque(uint64_t &v) { asm volatile("" : "+s"(v)); }
 // lane l's 64-bit value, wave-uniform
 __device__ __forceinline__ uint64_t wave_get64(uint64_t v, uint32_t l)
 {
@@ -787,7 +791,8 @@ k_analyze_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDe
 template <int BS, int BYTES>
 __device__ __forceinline__ uint32_t analyze_segment(const Cfg &c, const Seg &g, const uint32_t *rows, uint32_t stride,
                                                     uint32_t lane, uint32_t &tot, uint32_t &cl,
-                                                    const uint32_t *direct = nullptr)   // the lane's block from direct_finish
+                                                    const uint32_t *direct = nullptr,   // the lane's block from direct_finish
+                                                    uint32_t *len_incl = nullptr)       // out: inclusive sums of the lengths
 {
     const uint32_t bs = BS ? (uint32_t)BS : c.bs;
     const bool pp = c.flags & F_PREPROCESS;
@@ -842,7 +847,9 @@ __device__ __forceinline__ uint32_t analyze_segment(const Cfg &c, const Seg &g, 
             if (c.id_len > 1) kc = KClamp{ch.klo, ch.khi};
         }
     }
-    tot = wave_last(wave_incl_sum(meta_len(m), lane));
+    const uint32_t incl_l = wave_incl_sum(meta_len(m), lane);
+    if (len_incl) *len_incl = incl_l;
+    tot = wave_last(incl_l);
     // The summary of a block that updates k carries the COMPOSITION of the clamps of the segment's blocks up to
     // and including it (not its own plateau): the pack kernel then gets the block's k as one clamp of the
     // segment's carried-in k, without scanning the clamps a second time.
@@ -1409,13 +1416,14 @@ template <int BS, int BYTES>
 __device__ __forceinline__ void emit_segment(const Cfg &c, const Seg &g, const uint32_t *rows, uint32_t stride,
                                              uint32_t *obuf, uint32_t lane, uint32_t m, uint32_t kin, uint32_t lead,
                                              uint32_t ref_sample, uint32_t pending, uint32_t &total,
-                                             const uint32_t *direct = nullptr)   // the lane's block from direct_finish
+                                             const uint32_t *direct = nullptr,     // the lane's block from direct_finish
+                                             const uint32_t *len_incl = nullptr)   // analyze_segment's sums (else scanned here)
 {
     const uint32_t bs = BS ? (uint32_t)BS : c.bs;
     const bool pp = c.flags & F_PREPROCESS;
     const bool valid = lane < g.nv;
     const uint32_t len = meta_len(m), opt = meta_opt(m);
-    const uint32_t incl = wave_incl_sum(len, lane);
+    const uint32_t incl = len_incl ? *len_incl : wave_incl_sum(len, lane);
     total = wave_last(incl);
     const uint32_t excl = incl - len;
 
@@ -1541,6 +1549,27 @@ k_pack_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDesc 
 #undef AEC_WAVE_INDEX
 }
 
+// The kernel's arguments are ONE struct, so that the kernel's argument segment is this struct: what only the end of a run
+// needs -- the four per-segment arrays the first pass stores behind its run -- is read from there where it is used
+// (local_args) instead of holding eight scalar registers through the segment loop.
+struct LocalArgs {
+    Cfg c;
+    const uint8_t *in;
+    uint32_t *seg_bits;
+    uint16_t *seg_clamp;
+    const uint8_t *seg_kin;
+    const uint64_t *seg_start;
+    LocalLaunch l;
+    uint32_t obuf_words, fast_ok;
+};
+typedef const __attribute__((address_space(4))) LocalArgs LocalArgsK;
+__device__ __forceinline__ LocalArgsK *local_args()
+{
+    uint64_t p = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    uniform_opaque(p);           // (a load through it is no copy of one the compiler did at the kernel's start)
+    return (LocalArgsK *)p;
+}
+
 // ----------------------------------------------------------------------------------------------
 // K1 and the emission of K3 on the block while it is in registers (aec_enc_local.h)
 // ----------------------------------------------------------------------------------------------
@@ -1551,61 +1580,68 @@ k_pack_chunks(const Cfg call, const uint8_t *__restrict__ d_in, const ChunkDesc 
 // the positions inside the slot from seg_start, and nothing is written but the slot, whose layout the carried k does
 // not move.
 // (The redo of blocks of 16 8-bit samples is told to stay at the seven waves per SIMD it had: left alone the allocator takes
-// 73 registers, one more than seven waves allow; with the hint 71, no scratch.  The other instantiations are not bound.)
+// 73 registers, one more than seven waves allow; with the hint 71, no scratch -- that was with 46 scalar registers spilled;
+// without them it takes 60 with the hint and 62 without, and the hint has stayed.  The other instantiations are not bound.)
 template <int BS, int BYTES, bool REDO>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REDO && BS == 16 && BYTES == 1 ? 7 : 1)))
-k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict__ seg_bits,
-               uint16_t *__restrict__ seg_clamp, const uint8_t *__restrict__ seg_kin,
-               const uint64_t *__restrict__ seg_start, const LocalLaunch l,
-               uint32_t obuf_words, uint32_t fast_ok)
+k_encode_local(const LocalArgs a)
 {
+    const LocalLaunch &l = a.l;
+    const uint8_t *__restrict__ in = a.in;
+    const uint8_t *__restrict__ seg_kin = a.seg_kin;
+    const uint64_t *__restrict__ seg_start = a.seg_start;
+    const uint32_t obuf_words = a.obuf_words;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr uint32_t stride = Rows<BS, BYTES>::stride_words(BS);
     const uint32_t per_wave = 64u * stride + obuf_words;
-    uint32_t *rows = smem + (size_t)wave * per_wave;
-    uint32_t *obuf = rows + 64u * stride;
-    const bool pp = c.flags & F_PREPROCESS, msb = c.flags & F_MSB;
+    uint32_t rows_at = wave * per_wave;             // the wavefront's rows in smem, the segment's image behind them
+    uint32_t *rows = smem + rows_at, *obuf = rows + 64u * stride;
+    Cfg c = a.c;                 // (these pass through uniform_opaque once a segment, see the loop)
+    c.bs = BS;                   // what the instantiation fixes: sample and byte offsets by shifts, two registers fewer
+    c.bytes = BYTES;
+    uint32_t guess = l.guess, fast_ok = a.fast_ok;
 
     const uint64_t gwave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    uint64_t sg = gwave * l.segs_per_wave;
-    uint64_t sg_end = sg + l.segs_per_wave;
-    if (sg_end > c.total_segs) sg_end = c.total_segs;
-    if (sg >= sg_end) return;
+    const uint64_t run0 = gwave * l.segs_per_wave;      // the run's first segment
+    if (run0 >= c.total_segs) return;
+    // a run is at most 32 segments (local_plan): inside it a segment is a 32-bit index from run0
+    const uint64_t left = c.total_segs - run0;
+    const uint32_t nrun = left < l.segs_per_wave ? (uint32_t)left : l.segs_per_wave;
+    uint32_t si = 0, si_end = nrun;                     // segments [si, si_end) of the run are coded
     uint32_t *__restrict__ slot = l.image + gwave * l.slot_words;
     uint32_t pending = 0;        // open tail word of the previous segment
     uint32_t pos = 0;            // bits of the run so far = where the segment starts in the slot
     bool merge_tail = false;     // REDO: the last segment coded again ends in a word that goes on with an untouched one
-    const uint64_t run0 = sg;    // the run's first segment
     uint32_t keep_bk = 0, keep_cf = 0;      // lane s: bits | k used << 24 and clamp | first clamp << 16 of segment run0 + s
     if (REDO) {
         bool miss = false;
-        const uint64_t s = sg + lane;
-        if (s < sg_end) miss = local_missed(l.seg_first[s], l.seg_kused[s], seg_kin[s]);
+        const uint64_t s = run0 + lane;
+        if (lane < nrun) miss = local_missed(l.seg_first[s], l.seg_kused[s], seg_kin[s]);
         const uint64_t missed = __ballot(miss);
         if (!missed) return;
         // only the segments from the first to the last miss (aec_enc_local.h): positions from the scan, the open words
         // at both ends shared with what stays in the slot
         const LocalRedo range = local_redo_range(missed);
-        merge_tail = run0 + range.end < sg_end;
-        sg_end = run0 + range.end;
-        sg = run0 + range.first;
-        pos = (uint32_t)(seg_start[sg] - seg_start[run0]);
+        merge_tail = range.end < nrun;
+        si_end = range.end;
+        si = range.first;
+        pos = (uint32_t)(seg_start[run0 + si] - seg_start[run0]);
         if (pos & 31u) pending = local_redo_head(slot[pos >> 5], pos);
     }
 
     Feeder<BS, BYTES> feeder;
     feeder.init(c, fast_ok);
-    Seg gnext = seg_geom(c, sg);
+    Seg gnext = seg_geom(c, run0 + si);
     feeder.prefetch_direct(c, in, gnext, lane);
     uint32_t k = l.k_in;         // carried k (exact from the first k-updating block on)
     bool have_k = gwave == 0;    // ... or from the start, for the call's first wavefront
     for (uint32_t w = lane; w < obuf_words; w += kWave) obuf[w] = 0u;
 
-    auto do_segment = [&](const Seg &g, uint32_t ref_sample, uint64_t sgi, const uint32_t *direct) {
+    auto do_segment = [&](const Seg &g, uint32_t ref_sample, uint32_t at, const uint32_t *direct) {
         wave_lds_fence();
-        uint32_t tot, cl;
-        const uint32_t m = analyze_segment<BS, BYTES>(c, g, rows, stride, lane, tot, cl, direct);
+        uint32_t tot, cl, incl;
+        const uint32_t m = analyze_segment<BS, BYTES>(c, g, rows, stride, lane, tot, cl, direct, &incl);
         const uint32_t opt = meta_opt(m);
         const uint64_t upd = __ballot(lane < g.nv && opt != OPT_ZERO && opt != OPT_ZCONT && c.id_len > 1);
         // (the summary of the FIRST block that updates k holds that block's own clamp: nothing is composed in front)
@@ -1613,32 +1649,32 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
         if (upd) first = __builtin_amdgcn_readlane(__builtin_amdgcn_perm(0u, m, 0x0c0c0302u), (int)__builtin_ctzll(upd));
         uint32_t kin;
         if (REDO) {
-            kin = seg_kin[sgi];
+            kin = seg_kin[run0 + at];
         } else {
             if (!have_k && upd) {
-                k = local_guess(first, l.guess);
+                k = local_guess(first, guess);
                 have_k = true;
             }
             kin = k;
             // what the segment leaves for the scan and the redo: lane s keeps segment s of the run (all four are
             // wave-uniform; a segment is less than 2^24 bits, a k less than 2^8), stored once behind the run
-            const uint32_t at = (uint32_t)(sgi - run0);
             keep_bk = wave_set_lane(keep_bk, lane, at, tot | (kin << 24));
             keep_cf = wave_set_lane(keep_cf, lane, at, (cl & 0xFFFFu) | (first << 16));
             k = kclamp_apply(clamp_unpack(cl), k);
         }
         const uint32_t lead = pos & 31u;
         uint32_t total;
-        emit_segment<BS, BYTES>(c, g, rows, stride, obuf, lane, m, kin, lead, ref_sample, pending, total, direct);
+        // (the lengths were scanned for `tot`: emit_segment takes the sums as they are)
+        emit_segment<BS, BYTES>(c, g, rows, stride, obuf, lane, m, kin, lead, ref_sample, pending, total, direct, &incl);
         // copy-out as k_pack's, without its shared words: the slot is this wavefront's alone
         const uint32_t nwords = (lead + total + 31u) >> 5, gw = pos >> 5;
-        const bool carry_tail = ((lead + total) & 31u) != 0 && sgi + 1 != sg_end && nwords > 0;
+        const bool carry_tail = ((lead + total) & 31u) != 0 && at + 1 != si_end && nwords > 0;
         const uint32_t tail_word = carry_tail ? obuf[nwords - 1] : 0u;
         const uint32_t tail = (lead + total) & 31u;
         for (uint32_t w = lane; w < nwords; w += kWave) {
             uint32_t v = obuf[w];
             obuf[w] = 0u;
-            if (REDO && merge_tail && tail != 0 && sgi + 1 == sg_end && w == nwords - 1)
+            if (REDO && merge_tail && tail != 0 && at + 1 == si_end && w == nwords - 1)
                 v = local_redo_tail(v, slot[gw + w], tail);
             if (!(carry_tail && w == nwords - 1)) slot[gw + w] = v;
         }
@@ -1647,7 +1683,18 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
         wave_lds_fence();
     };
 
-    for (; sg < sg_end; sg++) {
+    for (; si < si_end; si++) {
+        // What follows from the parameters alone -- masks, sums, shifted constants, every flag as a 64-bit lane mask -- the
+        // compiler computes in front of the loop and keeps for all of it: some forty scalar registers more than there are,
+        // spilled to the lanes of a vector register and read back one v_readlane at a time inside the segment.  Behind
+        // uniform_opaque the values are the segment's own: computed where a segment uses them, on the scalar unit.
+        uniform_opaque(c.bps); uniform_opaque(c.flags); uniform_opaque(c.id_len); uniform_opaque(c.kmax);
+        uniform_opaque(c.xmax); uniform_opaque(guess); uniform_opaque(rows_at);
+        uniform_opaque(c.total_samples); uniform_opaque(fast_ok);
+        rows = smem + rows_at;
+        obuf = rows + 64u * stride;
+        feeder.init(c, fast_ok);          // (the feeder's limits and its flag, a lane mask, are derived values too)
+        const bool pp = c.flags & F_PREPROCESS, msb = c.flags & F_MSB;
         const auto cur = feeder.pre_direct;
         const Seg g = gnext;
         const bool direct = feeder.direct_ok(c, g);
@@ -1661,22 +1708,23 @@ k_encode_local(const Cfg c, const uint8_t *__restrict__ in, uint32_t *__restrict
             else if (lane == 0)
                 ref_sample = load_sample_bytes(in + g.samp0 * c.bytes, c.bytes, msb) & low_mask32(c.bps);
         }
-        if (sg + 1 < sg_end) gnext = seg_next(c, gnext);
+        if (si + 1 < si_end) gnext = seg_next(c, gnext);
         feeder.prefetch_direct(c, in, gnext, lane);       // the next segment's loads fly during this one
         if (direct) {
             uint32_t w[BS / 2];
             direct_finish<BS, BYTES>(c, g, cur, lane, w);
-            do_segment(g, ref_sample, sg, w);
+            do_segment(g, ref_sample, si, w);
         } else {
             feeder.feed_now(c, in, g, rows, stride, lane);
-            do_segment(g, ref_sample, sg, nullptr);
+            do_segment(g, ref_sample, si, nullptr);
         }
     }
-    if (!REDO && run0 + lane < sg_end) {        // (a run is at most 32 segments: local_plan)
-        seg_bits[run0 + lane] = keep_bk & 0xFFFFFFu;
-        seg_clamp[run0 + lane] = (uint16_t)keep_cf;
-        l.seg_first[run0 + lane] = (uint16_t)(keep_cf >> 16);
-        l.seg_kused[run0 + lane] = (uint8_t)(keep_bk >> 24);
+    if (!REDO && lane < si_end) {
+        const LocalArgsK *k_args = local_args();
+        k_args->seg_bits[run0 + lane] = keep_bk & 0xFFFFFFu;
+        k_args->seg_clamp[run0 + lane] = (uint16_t)keep_cf;
+        k_args->l.seg_first[run0 + lane] = (uint16_t)(keep_cf >> 16);
+        k_args->l.seg_kused[run0 + lane] = (uint8_t)(keep_bk >> 24);
     }
 }
 
@@ -1742,12 +1790,11 @@ void launch_local_t(bool redo, const Cfg &c, const uint8_t *in, const EncWorkspa
         const LaunchGeom g = make_geom(c, true);
         const uint64_t waves = (c.total_segs + l.segs_per_wave - 1) / l.segs_per_wave;
         const uint32_t grid = (uint32_t)((waves + g.waves_per_block - 1) / g.waves_per_block);
+        const LocalArgs a{c, in, ws.seg_bits, ws.seg_clamp, ws.seg_kin, ws.seg_start, l, g.obuf_words, fast_ok};
         if (redo)
-            hipLaunchKernelGGL((k_encode_local<BS, BYTES, true>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, c,
-                               in, ws.seg_bits, ws.seg_clamp, ws.seg_kin, ws.seg_start, l, g.obuf_words, fast_ok);
+            hipLaunchKernelGGL((k_encode_local<BS, BYTES, true>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, a);
         else
-            hipLaunchKernelGGL((k_encode_local<BS, BYTES, false>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, c,
-                               in, ws.seg_bits, ws.seg_clamp, ws.seg_kin, ws.seg_start, l, g.obuf_words, fast_ok);
+            hipLaunchKernelGGL((k_encode_local<BS, BYTES, false>), dim3(grid), dim3(64 * g.waves_per_block), g.lds_bytes, st, a);
     } else {
         // local_plan opens the route for direct_shape() only: a launch without a kernel leaves the call's launch error set
         (void)hipLaunchKernel(nullptr, dim3(1), dim3(1), nullptr, 0, st);
