@@ -43,8 +43,20 @@
  *
  * X lie little-endian in containers of 1 byte (nbits <= 8), 2 bytes (<= 16) or 4 bytes (<= 32), never 3.
  *
- * OUT OF SCOPE: section 6 bitmaps and missing values (the caller compacts the field first); second-order and JPEG
- * packings; parsing or writing GRIB messages themselves; a quantiser fused into the encoder.
+ * SECTION 6 BITMAPS (the *_bitmap_* calls at the end of this header)
+ * A field of N = n_points[i] grid points has a bitmap of N bits in ceil(N / 8) bytes at d_bitmap + bitmap_offsets[i] (any
+ * byte; neighbouring bitmaps may touch): point k is bit 7 - k % 8 of byte k / 8, most significant bit first, 1 = present,
+ * what numpy.packbits writes.  Section 7 holds the X of the present points only, in grid order; n_values[i] -- section 5
+ * octets 6-9 -- is the number of present points and stays a HOST number: the rooms, the coder's tables and out_bound are
+ * host arithmetic over it.  A reader takes it from the message; a writer, whose mask is static, gets it once from
+ * aec_gpu_grib_bitmap_async.  The device still counts every bitmap: a field whose bitmap does not hold n_values[i] ones
+ * gets status bit 3 (AEC_GPU_GRIB_MISMATCH); its X, stream and values are unspecified, but no access leaves its room, its
+ * bitmap or its n_points elements whatever the bitmap holds, and every other field of the batch is exact.  Bits of the last
+ * byte behind point N - 1 are ignored when read and written as 0.
+ *
+ * OUT OF SCOPE: fields without a present point (a writer sets nbits 0 and drops section 7), bitmap indicator 254 and
+ * predefined bitmaps (the caller hands over whichever bitmap applies); second-order and JPEG packings; parsing or writing
+ * GRIB messages themselves; a quantiser fused into the encoder.
  */
 #ifndef AEC_GPU_GRIB_H
 #define AEC_GPU_GRIB_H 1
@@ -63,6 +75,8 @@ extern "C" {
 #define AEC_GPU_GRIB_CONSTANT 2u  /* status bit 1: lo == hi */
 #define AEC_GPU_GRIB_CLAMPED  4u  /* status bit 2: an X of a field that is not bad was held to [0, M] -- under have_params,
                                      or where E was held at 127 */
+#define AEC_GPU_GRIB_MISMATCH 8u  /* status bit 3 (the *_bitmap_* calls): the field's bitmap does not hold n_values[i] ones; its
+                                     X, stream and values are unspecified, every other field of the batch is exact */
 
 /* Template 5.42 as far as it is shared by a batch */
 typedef struct aec_gpu_grib_template_s {
@@ -164,6 +178,83 @@ AEC_GPU_API int aec_gpu_grib_quantise_async(aec_gpu_ctx *ctx, const aec_gpu_grib
 AEC_GPU_API int aec_gpu_grib_dequantise_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_work,
                                               const uint64_t *n_values, const aec_gpu_grib_field *params,
                                               const uint64_t *dst_offsets, uint64_t n_fields, void *d_dst, void *stream);
+
+/*
+ * ---- section 6 bitmaps ----------------------------------------------------------------------------------------------------
+ * aec_gpu_grib_bitmap_plan is host arithmetic only (1 = taken, 0 = refused).  plan is what aec_gpu_grib_plan gives for
+ * n_values (rooms, work_offsets, out_bound and rsi_entries are identical), its workspace_bytes grown by this layer's
+ * bitmap descriptors, per-tile counts and bases and the tile table.  tile_points (AEC_GPU_GRIB_TILE_POINTS) is the grid
+ * points one wavefront of the bitmap kernels owns, tiles the sum of ceil(n_points[i] / tile_points).  Refused, and
+ * AEC_CONF_ERROR from the calls below with nothing enqueued: whatever aec_gpu_grib_plan refuses (n_values[i] == 0 among it:
+ * a field without a present point has no section 7); n_values[i] > n_points[i]; a field of 2^35 bytes or more; more than
+ * 2^25 wavefronts (tiles) in a launch.
+ */
+#define AEC_GPU_GRIB_TILE_POINTS 1024u
+typedef struct aec_gpu_grib_bitmap_plan_s {
+    aec_gpu_grib_plan_t plan;
+    uint64_t tile_points;
+    uint64_t tiles;
+} aec_gpu_grib_bitmap_plan_t;
+AEC_GPU_API int aec_gpu_grib_bitmap_plan(const aec_gpu_grib_template *t, int elem, const uint64_t *n_points,
+                                         const uint64_t *n_values, uint64_t n_fields, aec_gpu_grib_bitmap_plan_t *plan,
+                                         uint64_t *work_offsets);
+
+/*
+ * Section 6 from values: point k of field i (n_points[i] >= 1 elements at d_src + src_offsets[i]) is MISSING iff its value
+ * == (T)missing -- IEEE equality, so either zero matches a zero missing -- and, if missing is a NaN, iff it is a NaN.
+ * Exactly ceil(n_points[i] / 8) bytes are written at d_bitmap + bitmap_offsets[i] (HOST array, any byte), the unused low
+ * bits of the last byte 0, and nothing else.  d_counts[i] (n_fields uint64_t on the device) receives the number of ones:
+ * the n_values[i] of the calls below.  Refused: an elem that is neither, a field without a point or of 2^35 bytes or more,
+ * more than 2^25 tiles.
+ */
+AEC_GPU_API int aec_gpu_grib_bitmap_async(aec_gpu_ctx *ctx, int elem, const void *d_src, const uint64_t *src_offsets,
+                                          const uint64_t *n_points, double missing, uint64_t n_fields, void *d_bitmap,
+                                          const uint64_t *bitmap_offsets, uint64_t *d_counts, void *stream);
+
+/*
+ * aec_gpu_grib_pack_async over fields with bitmaps.  src_offsets[i] and n_points[i] describe the WHOLE grid, n_values[i] the
+ * present points.  Absent points are loaded at most: they never enter the minimum, the maximum, the status or an X and
+ * may hold NaN, Inf or 1e300.  Everything the call leaves -- d_work, d_out, d_chunks, the RSI table, d_result, d_fields --
+ * is byte for byte what aec_gpu_grib_pack_async leaves for the fields compacted to their present points (a field whose
+ * bitmap is all ones: exactly that call's); no compacted copy of the floats is written anywhere.  The exception is a
+ * field with AEC_GPU_GRIB_MISMATCH in its record, and, the streams lying back to back, the places (not the bytes) of the
+ * streams behind it.  have_params as there.
+ */
+AEC_GPU_API int aec_gpu_grib_pack_bitmap_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_src,
+                                               const uint64_t *src_offsets, const uint64_t *n_values, const int32_t *D,
+                                               int have_params, const aec_gpu_grib_field *params, uint64_t n_fields, void *d_work,
+                                               void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
+                                               uint64_t *d_rsi_bit_offsets, aec_gpu_grib_field *d_fields,
+                                               aec_gpu_enc_result *d_result, const void *d_bitmap, const uint64_t *bitmap_offsets,
+                                               const uint64_t *n_points, void *stream);
+
+/*
+ * aec_gpu_grib_unpack_async into whole grids.  Exactly n_points[i] elements are written at d_dst + dst_offsets[i]: a
+ * present point k gets the dequantised X of rank (ones in front of k), an absent point the bits of (T)missing -- the HOST
+ * casts it once and the kernel stores those bits, so a NaN's payload is the host's.  d_status (n_fields uint32_t on the
+ * device): 0 or AEC_GPU_GRIB_MISMATCH.  With the pack's table or bare (have_table == 0), as there.
+ */
+AEC_GPU_API int aec_gpu_grib_unpack_bitmap_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_in,
+                                                 size_t in_bytes, const uint64_t *in_offsets, const uint64_t *in_bytes_each,
+                                                 const uint64_t *n_values, const aec_gpu_grib_field *params,
+                                                 const uint64_t *dst_offsets, uint64_t n_fields, uint64_t *d_rsi_bit_offsets,
+                                                 int have_table, void *d_work, void *d_dst, aec_gpu_dec_result *d_results,
+                                                 aec_gpu_dec_result *d_result, const void *d_bitmap,
+                                                 const uint64_t *bitmap_offsets, const uint64_t *n_points, double missing,
+                                                 uint32_t *d_status, void *stream);
+
+/* The two halves alone, as aec_gpu_grib_quantise_async / aec_gpu_grib_dequantise_async */
+AEC_GPU_API int aec_gpu_grib_quantise_bitmap_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_src,
+                                                   const uint64_t *src_offsets, const uint64_t *n_values, const int32_t *D,
+                                                   int have_params, const aec_gpu_grib_field *params, uint64_t n_fields,
+                                                   void *d_work, aec_gpu_grib_field *d_fields, const void *d_bitmap,
+                                                   const uint64_t *bitmap_offsets, const uint64_t *n_points, void *stream);
+AEC_GPU_API int aec_gpu_grib_dequantise_bitmap_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem,
+                                                     const void *d_work, const uint64_t *n_values,
+                                                     const aec_gpu_grib_field *params, const uint64_t *dst_offsets,
+                                                     uint64_t n_fields, void *d_dst, const void *d_bitmap,
+                                                     const uint64_t *bitmap_offsets, const uint64_t *n_points, double missing,
+                                                     uint32_t *d_status, void *stream);
 
 #ifdef __cplusplus
 }

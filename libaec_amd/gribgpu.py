@@ -14,6 +14,7 @@ from .api import AEC_DATA_PREPROCESS
 AEC_CONF_ERROR = -1
 F32, F64 = 4, 8                       # elem: the element type by its size
 BAD, CONSTANT, CLAMPED = 1, 2, 4      # status bits of a field record
+MISMATCH = 8                          # ... of the bitmap calls: the bitmap does not hold n_values ones
 
 
 class Template(C.Structure):
@@ -30,6 +31,11 @@ class Plan(C.Structure):
     """aec_gpu_grib_plan_t"""
     _fields_ = [("coder", gpu.Params), ("work_bytes", C.c_size_t), ("out_bound", C.c_size_t), ("rsi_entries", C.c_uint64),
                 ("workspace_bytes", C.c_size_t)]
+
+
+class BitmapPlan(C.Structure):
+    """aec_gpu_grib_bitmap_plan_t"""
+    _fields_ = [("plan", Plan), ("tile_points", C.c_uint64), ("tiles", C.c_uint64)]
 
 
 FIELD_DTYPE = np.dtype([("R", "<f4"), ("E", "<i4"), ("D", "<i4"), ("status", "<u4")])      # aec_gpu_grib_field
@@ -57,6 +63,21 @@ def _lib():
         lib.aec_gpu_grib_quantise_async.argtypes = [vp, pt, C.c_int, vp, vp, vp, vp, C.c_int, vp, u64, vp, vp, vp]
         lib.aec_gpu_grib_dequantise_async.restype = C.c_int
         lib.aec_gpu_grib_dequantise_async.argtypes = [vp, pt, C.c_int, vp, vp, vp, vp, u64, vp, vp]
+        if not hasattr(lib, "aec_gpu_grib_pack_bitmap_async"):
+            raise RuntimeError("this libaec.so.0 has no bitmap calls (aec_gpu_grib_*_bitmap_*): rebuild it")
+        dbl = C.c_double
+        lib.aec_gpu_grib_bitmap_plan.restype = C.c_int
+        lib.aec_gpu_grib_bitmap_plan.argtypes = [pt, C.c_int, vp, vp, u64, C.POINTER(BitmapPlan), vp]
+        lib.aec_gpu_grib_bitmap_async.restype = C.c_int
+        lib.aec_gpu_grib_bitmap_async.argtypes = [vp, C.c_int, vp, vp, vp, dbl, u64, vp, vp, vp, vp]
+        lib.aec_gpu_grib_pack_bitmap_async.restype = C.c_int
+        lib.aec_gpu_grib_pack_bitmap_async.argtypes = lib.aec_gpu_grib_pack_async.argtypes[:-1] + [vp, vp, vp, vp]
+        lib.aec_gpu_grib_unpack_bitmap_async.restype = C.c_int
+        lib.aec_gpu_grib_unpack_bitmap_async.argtypes = lib.aec_gpu_grib_unpack_async.argtypes[:-1] + [vp, vp, vp, dbl, vp, vp]
+        lib.aec_gpu_grib_quantise_bitmap_async.restype = C.c_int
+        lib.aec_gpu_grib_quantise_bitmap_async.argtypes = lib.aec_gpu_grib_quantise_async.argtypes[:-1] + [vp, vp, vp, vp]
+        lib.aec_gpu_grib_dequantise_bitmap_async.restype = C.c_int
+        lib.aec_gpu_grib_dequantise_bitmap_async.argtypes = lib.aec_gpu_grib_dequantise_async.argtypes[:-1] + [vp, vp, vp, dbl, vp, vp]
         _bound = True
     return lib
 
@@ -108,6 +129,23 @@ def plan(nbits, options, block_size, rsi, elem, n_values):
     return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
                 out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
                 work_offsets=offs[:n_values.size])
+
+
+def bitmap_plan(nbits, options, block_size, rsi, elem, n_points, n_values):
+    """aec_gpu_grib_bitmap_plan (host arithmetic, no device needed) for grids of n_points points of which n_values are
+    present: the dict of plan() plus tile_points and tiles, or None where the batch would be refused"""
+    t = Template(nbits, options, block_size, rsi)
+    n_points, n_values = _u64(n_points), _u64(n_values)
+    if n_points.size != n_values.size:
+        raise ValueError("n_points and n_values are per field")
+    offs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    bp = BitmapPlan()
+    if not _lib().aec_gpu_grib_bitmap_plan(C.byref(t), elem, _host(n_points), _host(n_values), n_values.size, C.byref(bp), _host(offs)):
+        return None
+    p = bp.plan
+    return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
+                out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
+                work_offsets=offs[:n_values.size], tile_points=int(bp.tile_points), tiles=int(bp.tiles))
 
 
 def _elem_of(t):
@@ -197,7 +235,128 @@ class GribCodec:
         return self.lib.aec_gpu_grib_dequantise_async(self.ctx, C.byref(self.t), elem, _ptr(d_work), _host(nv), _host(ph),
                                                       _host(dso), nv.size, _ptr(d_dst), self._stream(stream))
 
+    # ---- enqueue, fields with section 6 bitmaps ----------------------------------------------------
+    def bitmap_plan(self, n_points, n_values, elem=F32):
+        t = self.t
+        return bitmap_plan(t.nbits, t.options, t.block_size, t.rsi, elem, n_points, n_values)
+
+    def bitmap_async(self, elem, d_src, src_offsets, n_points, missing, d_bitmap, bitmap_offsets, d_counts, stream=None):
+        """section 6 from values: a point is missing iff it == missing (a NaN: iff it is a NaN).  src_offsets / bitmap_offsets
+        (bytes), n_points: uint64 arrays on the host; d_bitmap: uint8 tensor; d_counts: int64 tensor, a count per field."""
+        offs, npts, bmo = _u64(src_offsets), _u64(n_points), _u64(bitmap_offsets)
+        return self.lib.aec_gpu_grib_bitmap_async(self.ctx, elem, _ptr(d_src), _host(offs), _host(npts), float(missing), npts.size,
+                                                  _ptr(d_bitmap), _host(bmo), _ptr(d_counts), self._stream(stream))
+
+    def pack_bitmap_async(self, elem, d_src, src_offsets, n_values, D, params, d_work, d_out, out_cap, d_chunks, d_table, d_fields,
+                          d_result, d_bitmap, bitmap_offsets, n_points, stream=None):
+        """pack_async over whole grids: src_offsets / n_points describe the grids, n_values the present points, d_bitmap /
+        bitmap_offsets (bytes, host) the bitmaps"""
+        offs, nv, bmo, npts = _u64(src_offsets), _u64(n_values), _u64(bitmap_offsets), _u64(n_points)
+        Dh = None if D is None else np.ascontiguousarray(D, dtype=np.int32)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_pack_bitmap_async(self.ctx, C.byref(self.t), elem, _ptr(d_src), _host(offs), _host(nv), _host(Dh),
+                                                       int(ph is not None), _host(ph), nv.size, _ptr(d_work), _ptr(d_out), out_cap,
+                                                       _ptr(d_chunks), _ptr(d_table), _ptr(d_fields), _ptr(d_result), _ptr(d_bitmap),
+                                                       _host(bmo), _host(npts), self._stream(stream))
+
+    def unpack_bitmap_async(self, elem, d_in, in_bytes, in_offsets, in_sizes, n_values, params, dst_offsets, d_table, have_table, d_work,
+                            d_dst, d_results, d_result, d_bitmap, bitmap_offsets, n_points, missing, d_status, stream=None):
+        """unpack_async into whole grids: n_points elements per field at dst_offsets, absent points get the bits of missing;
+        d_status: int32 tensor, 0 or MISMATCH per field"""
+        ino, ins, nv, dso = _u64(in_offsets), _u64(in_sizes), _u64(n_values), _u64(dst_offsets)
+        bmo, npts = _u64(bitmap_offsets), _u64(n_points)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_unpack_bitmap_async(self.ctx, C.byref(self.t), elem, _ptr(d_in), in_bytes, _host(ino), _host(ins),
+                                                         _host(nv), _host(ph), _host(dso), nv.size, _ptr(d_table), int(bool(have_table)),
+                                                         _ptr(d_work), _ptr(d_dst), _ptr(d_results), _ptr(d_result), _ptr(d_bitmap),
+                                                         _host(bmo), _host(npts), float(missing), _ptr(d_status), self._stream(stream))
+
+    def quantise_bitmap_async(self, elem, d_src, src_offsets, n_values, D, params, d_work, d_fields, d_bitmap, bitmap_offsets, n_points,
+                              stream=None):
+        """pack_bitmap_async without the encoder"""
+        offs, nv, bmo, npts = _u64(src_offsets), _u64(n_values), _u64(bitmap_offsets), _u64(n_points)
+        Dh = None if D is None else np.ascontiguousarray(D, dtype=np.int32)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_quantise_bitmap_async(self.ctx, C.byref(self.t), elem, _ptr(d_src), _host(offs), _host(nv), _host(Dh),
+                                                           int(ph is not None), _host(ph), nv.size, _ptr(d_work), _ptr(d_fields),
+                                                           _ptr(d_bitmap), _host(bmo), _host(npts), self._stream(stream))
+
+    def dequantise_bitmap_async(self, elem, d_work, n_values, params, dst_offsets, d_dst, d_bitmap, bitmap_offsets, n_points, missing,
+                                d_status, stream=None):
+        """unpack_bitmap_async without the decoder"""
+        nv, dso, bmo, npts = _u64(n_values), _u64(dst_offsets), _u64(bitmap_offsets), _u64(n_points)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_dequantise_bitmap_async(self.ctx, C.byref(self.t), elem, _ptr(d_work), _host(nv), _host(ph),
+                                                             _host(dso), nv.size, _ptr(d_dst), _ptr(d_bitmap), _host(bmo), _host(npts),
+                                                             float(missing), _ptr(d_status), self._stream(stream))
+
     # ---- convenience (synchronising) -------------------------------------------------------------
+    def bitmap(self, d_values, offsets, n_points, missing):
+        """grids of n_points[i] elements at ELEMENT offsets[i] of the float tensor d_values -> (d_bitmap, bitmap_offsets,
+        counts): the bitmaps back to back in a uint8 tensor, their byte offsets and the present points of every grid as a
+        NumPy array -- the n_values of pack_bitmap.  SYNCHRONISES (the counts come to the host): call it once per mask."""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        npts = _u64(n_points)
+        sizes = (npts + np.uint64(7)) // np.uint64(8)
+        bm_offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+        d_bitmap = torch.zeros(max(1, int(bm_offsets[-1])), dtype=torch.uint8, device=d_values.device)
+        d_counts = torch.zeros(max(1, npts.size), dtype=torch.int64, device=d_values.device)
+        self._check(self.bitmap_async(elem, d_values, _u64(offsets) * np.uint64(elem), npts, missing, d_bitmap, bm_offsets[:-1], d_counts),
+                    "aec_gpu_grib_bitmap_async")
+        return d_bitmap, bm_offsets[:-1], d_counts.cpu().numpy()[:npts.size].astype(np.uint64)
+
+    def pack_bitmap(self, d_values, offsets, n_points, d_bitmap, bitmap_offsets, n_values, D, params=None, want_offsets=False):
+        """pack() over whole grids with bitmaps (of bitmap(), or a message's): -> (d_out, spans, fields, d_table)"""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        pl = self.bitmap_plan(n_points, n_values, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_bitmap_plan)")
+        n, dev = len(n_values), d_values.device
+        d_out = torch.empty(pl["out_bound"], dtype=torch.uint8, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_rec = torch.zeros(max(1, n) * 2, dtype=torch.int64, device=dev)
+        d_fields = torch.zeros(max(1, n) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_res = torch.zeros(gpu.ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev) if want_offsets else None
+        Dh = np.broadcast_to(np.asarray(D, dtype=np.int32), (n,))
+        self._check(self.pack_bitmap_async(elem, d_values, _u64(offsets) * np.uint64(elem), n_values, Dh, params, d_work, d_out,
+                                           d_out.numel(), d_rec, d_table, d_fields, d_res, d_bitmap, bitmap_offsets, n_points),
+                    "aec_gpu_grib_pack_bitmap_async")
+        if n and d_res.cpu().numpy().view(gpu.ENC_RESULT_DTYPE)[0]["overflow"]:
+            raise RuntimeError("encode overflow")
+        rec = d_rec.cpu().numpy().view(np.uint64).view(BATCH_CHUNK_DTYPE)[:n]
+        spans = [(int(r["base_bits"]) // 8, (int(r["bits"]) + 7) // 8) for r in rec]
+        return d_out, spans, d_fields.cpu().numpy().view(FIELD_DTYPE)[:n], d_table
+
+    def unpack_bitmap(self, d_streams, spans, params, n_values, n_points, d_bitmap, bitmap_offsets, missing=9999.0, d_table=None,
+                      dtype=None):
+        """unpack() into whole grids: -> (float tensor with the grids back to back, per-field decode records, per-field
+        status: 0 or MISMATCH)"""
+        torch = self.torch
+        dtype = dtype or torch.float32
+        elem = F32 if dtype == torch.float32 else F64
+        pl = self.bitmap_plan(n_points, n_values, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_bitmap_plan)")
+        n, dev = len(n_values), d_streams.device
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(n_points, dtype=np.uint64))]).astype(np.uint64) * np.uint64(elem)
+        d_dst = torch.empty(int(dst_offsets[-1]) // elem, dtype=dtype, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        have = d_table is not None
+        if not have:
+            d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev)
+        d_results = torch.zeros(max(1, n) * gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_result = torch.zeros(gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        in_offs = None if have else [s for s, _ in spans]
+        in_sizes = None if have else [b for _, b in spans]
+        self._check(self.unpack_bitmap_async(elem, d_streams, d_streams.numel(), in_offs, in_sizes, n_values, params, dst_offsets[:n],
+                                             d_table, have, d_work, d_dst, d_results, d_result, d_bitmap, bitmap_offsets, n_points, missing,
+                                             d_status), "aec_gpu_grib_unpack_bitmap_async")
+        return d_dst, d_results.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[:n], d_status.cpu().numpy()[:n].astype(np.uint32)
+
     def _check(self, rc, what):
         if rc != 0:
             raise ValueError(f"not a batch for one call ({what} -> AEC_CONF_ERROR)") if rc == AEC_CONF_ERROR else \
