@@ -1,6 +1,7 @@
 /*
- * aec_gpu_grib.h -- GRIB2 CCSDS packing (data representation template 5.42 / 7.42, ecCodes' grid_ccsds) that stays on
- * the device: float fields to section-7 streams and back.
+ * aec_gpu_grib.h -- GRIB2 CCSDS packing (data representation template 5.42 / 7.42, ecCodes' grid_ccsds) and simple packing
+ * (template 5.0 / 7.0, grid_simple) that stay on the device: float fields to section-7 streams and back, and one kind of
+ * stream to the other.
  *
  * Between a field of floats and the coder (aec_gpu.h) sits GRIB2's simple packing, WMO regulation 92.9.4:
  *       Y * 10^D = R + X * 2^E
@@ -54,9 +55,21 @@
  * bitmap or its n_points elements whatever the bitmap holds, and every other field of the batch is exact.  Bits of the last
  * byte behind point N - 1 are ignored when read and written as 0.
  *
+ * SIMPLE PACKING (template 5.0 / 7.0, ecCodes' grid_simple; the *_simple_* and *_bits_* calls at the end of this header)
+ * The same R, E, D and X under the same aec_gpu_grib_template, with X stored as a plain string of nbits-bit integers instead
+ * of going through the coder: value j of a field of n = n_values[i] values is the bits [j * nbits, (j + 1) * nbits) of its
+ * stream, bit b of a stream is bit 7 - b % 8 of byte b / 8, most significant bit first, and the unused low bits of the last
+ * of its S = ceil(n * nbits / 8) bytes are 0 -- the big-endian integer sum X_j * 2^(nbits * (n - 1 - j)) shifted left to a
+ * whole byte.  Streams lie at d_simple + simple_offsets[i] (HOST array): at any byte, neighbours may touch, in any order.
+ * Rooms, work_offsets and containers are those of aec_gpu_grib_plan (block_size and rsi still size the rooms), so the
+ * calls compose with everything above through d_work: floats to 5.0 streams and back, 5.0 streams to 5.42 streams and back
+ * without a float being touched (R, E, D and nbits pass from one section 5 to the other unchanged: lossless by
+ * construction), and, through aec_gpu_grib_quantise_bitmap_async / aec_gpu_grib_dequantise_bitmap_async, fields with
+ * bitmaps -- these need no entry point of their own.
+ *
  * OUT OF SCOPE: fields without a present point (a writer sets nbits 0 and drops section 7), bitmap indicator 254 and
- * predefined bitmaps (the caller hands over whichever bitmap applies); second-order and JPEG packings; parsing or writing
- * GRIB messages themselves; a quantiser fused into the encoder.
+ * predefined bitmaps (the caller hands over whichever bitmap applies); complex, second-order and JPEG packings; parsing or
+ * writing GRIB messages themselves; a quantiser fused into the encoder or into the bit packer.
  */
 #ifndef AEC_GPU_GRIB_H
 #define AEC_GPU_GRIB_H 1
@@ -255,6 +268,83 @@ AEC_GPU_API int aec_gpu_grib_dequantise_bitmap_async(aec_gpu_ctx *ctx, const aec
                                                      uint64_t n_fields, void *d_dst, const void *d_bitmap,
                                                      const uint64_t *bitmap_offsets, const uint64_t *n_points, double missing,
                                                      uint32_t *d_status, void *stream);
+
+/*
+ * ---- simple packing (templates 5.0 / 7.0) ---------------------------------------------------------------------------------
+ * aec_gpu_grib_simple_plan is host arithmetic only (1 = taken, 0 = refused; it refuses whatever aec_gpu_grib_plan refuses).
+ * plan is what aec_gpu_grib_plan gives for n_values; this layer's descriptors and wavefront table take the place of the
+ * GRIB layer's in the context's buffer, so workspace_bytes grows by nothing.  simple_bytes is the sum of S_i =
+ * ceil(n_values[i] * nbits / 8); simple_offsets (optional, n_fields entries) receives their running sum: streams back to
+ * back, no padding.  nbits is 1 .. 32.
+ */
+typedef struct aec_gpu_grib_simple_plan_s {
+    aec_gpu_grib_plan_t plan;
+    size_t simple_bytes;
+} aec_gpu_grib_simple_plan_t;
+AEC_GPU_API int aec_gpu_grib_simple_plan(const aec_gpu_grib_template *t, int elem, const uint64_t *n_values, uint64_t n_fields,
+                                         aec_gpu_grib_simple_plan_t *plan, uint64_t *work_offsets, uint64_t *simple_offsets);
+
+/*
+ * Rooms to streams: the X of field i, in the plan's room at d_work + work_offsets[i] (16-byte aligned, as everywhere), to the
+ * S_i bytes at d_simple + simple_offsets[i].  Exactly those bytes are written, each once, and nothing else; X is taken
+ * modulo 2^nbits, so a stray high bit in a container never reaches a neighbouring value.  n_fields == 0: AEC_OK, nothing
+ * is enqueued (so for every call below).
+ */
+AEC_GPU_API int aec_gpu_grib_bits_pack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, const uint64_t *n_values,
+                                             uint64_t n_fields, const void *d_work, void *d_simple, const uint64_t *simple_offsets,
+                                             void *stream);
+
+/*
+ * Streams to rooms.  The whole room of every field is written, the last block padded with the last X: byte for byte the room
+ * aec_gpu_grib_quantise_async leaves for the same X; the up to 15 bytes between rooms are not written.  simple_bytes_each
+ * (optional, HOST array) gives section 7's data length per message.  AEC_CONF_ERROR with nothing enqueued: a field with
+ * simple_bytes_each[i] < S_i, or a stream that leaves [0, simple_bytes).  No load leaves [d_simple, d_simple + simple_bytes).
+ */
+AEC_GPU_API int aec_gpu_grib_bits_unpack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, const uint64_t *n_values,
+                                               uint64_t n_fields, const void *d_simple, size_t simple_bytes,
+                                               const uint64_t *simple_offsets, const uint64_t *simple_bytes_each, void *d_work,
+                                               void *stream);
+
+/*
+ * Floats to 5.0 streams: aec_gpu_grib_quantise_async (same arguments, same refusals, have_params as there; d_work and d_fields
+ * come out exactly as it leaves them), then aec_gpu_grib_bits_pack_async.  The stream of a field whose record says bad is
+ * unspecified, S_i bytes all the same.
+ */
+AEC_GPU_API int aec_gpu_grib_simple_pack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_src,
+                                               const uint64_t *src_offsets, const uint64_t *n_values, const int32_t *D,
+                                               int have_params, const aec_gpu_grib_field *params, uint64_t n_fields, void *d_work,
+                                               aec_gpu_grib_field *d_fields, void *d_simple, const uint64_t *simple_offsets,
+                                               void *stream);
+
+/* 5.0 streams to floats: aec_gpu_grib_bits_unpack_async into d_work, then aec_gpu_grib_dequantise_async. */
+AEC_GPU_API int aec_gpu_grib_simple_unpack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem, const void *d_simple,
+                                                 size_t simple_bytes, const uint64_t *simple_offsets,
+                                                 const uint64_t *simple_bytes_each, const uint64_t *n_values,
+                                                 const aec_gpu_grib_field *params, const uint64_t *dst_offsets, uint64_t n_fields,
+                                                 void *d_work, void *d_dst, void *stream);
+
+/*
+ * grid_simple to grid_ccsds: aec_gpu_grib_bits_unpack_async, then aec_gpu_encode_chunks_async over the rooms.  d_work, d_out,
+ * d_chunks, d_rsi_bit_offsets and d_result are byte for byte what aec_gpu_grib_pack_async leaves for fields that quantise to
+ * the same X.  No float is touched and no d_fields is written: the caller carries R, E, D and nbits over from section 5.
+ */
+AEC_GPU_API int aec_gpu_grib_simple_to_ccsds_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, const void *d_simple,
+                                                   size_t simple_bytes, const uint64_t *simple_offsets,
+                                                   const uint64_t *simple_bytes_each, const uint64_t *n_values, uint64_t n_fields,
+                                                   void *d_work, void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
+                                                   uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result, void *stream);
+
+/*
+ * grid_ccsds to grid_simple: aec_gpu_decode_chunks_async into d_work (with the pack's table, or bare with have_table == 0;
+ * d_in .. have_table, d_results and d_result as in aec_gpu_grib_unpack_async), then aec_gpu_grib_bits_pack_async.  A field
+ * whose record in d_results is not clean gets an unspecified stream of exactly its S_i bytes; every other field is exact.
+ */
+AEC_GPU_API int aec_gpu_grib_ccsds_to_simple_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, const void *d_in,
+                                                   size_t in_bytes, const uint64_t *in_offsets, const uint64_t *in_bytes_each,
+                                                   const uint64_t *n_values, uint64_t n_fields, uint64_t *d_rsi_bit_offsets,
+                                                   int have_table, void *d_work, aec_gpu_dec_result *d_results,
+                                                   aec_gpu_dec_result *d_result, void *d_simple, const uint64_t *simple_offsets,
+                                                   void *stream);
 
 #ifdef __cplusplus
 }

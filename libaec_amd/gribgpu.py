@@ -1,5 +1,5 @@
-"""GRIB2 CCSDS packing that stays on the device (include/aec_gpu_grib.h) for torch tensors living in HBM: float fields to
-section-7 streams and back.
+"""GRIB2 CCSDS packing and simple packing that stay on the device (include/aec_gpu_grib.h) for torch tensors living in HBM:
+float fields to section-7 streams and back, and template 5.0 streams to template 5.42 streams and back.
 
 torch is used for device memory and streams only; the minimum / maximum, the parameters, the quantisation and the coder are
 kernels launched by libaec.so.0 through the C entry points declared in aec_gpu_grib.h.
@@ -36,6 +36,11 @@ class Plan(C.Structure):
 class BitmapPlan(C.Structure):
     """aec_gpu_grib_bitmap_plan_t"""
     _fields_ = [("plan", Plan), ("tile_points", C.c_uint64), ("tiles", C.c_uint64)]
+
+
+class SimplePlan(C.Structure):
+    """aec_gpu_grib_simple_plan_t"""
+    _fields_ = [("plan", Plan), ("simple_bytes", C.c_size_t)]
 
 
 FIELD_DTYPE = np.dtype([("R", "<f4"), ("E", "<i4"), ("D", "<i4"), ("status", "<u4")])      # aec_gpu_grib_field
@@ -78,6 +83,22 @@ def _lib():
         lib.aec_gpu_grib_quantise_bitmap_async.argtypes = lib.aec_gpu_grib_quantise_async.argtypes[:-1] + [vp, vp, vp, vp]
         lib.aec_gpu_grib_dequantise_bitmap_async.restype = C.c_int
         lib.aec_gpu_grib_dequantise_bitmap_async.argtypes = lib.aec_gpu_grib_dequantise_async.argtypes[:-1] + [vp, vp, vp, dbl, vp, vp]
+        if not hasattr(lib, "aec_gpu_grib_bits_pack_async"):
+            raise RuntimeError("this libaec.so.0 has no simple packing (aec_gpu_grib_simple_*, aec_gpu_grib_bits_*): rebuild it")
+        lib.aec_gpu_grib_simple_plan.restype = C.c_int
+        lib.aec_gpu_grib_simple_plan.argtypes = [pt, C.c_int, vp, u64, C.POINTER(SimplePlan), vp, vp]
+        lib.aec_gpu_grib_bits_pack_async.restype = C.c_int
+        lib.aec_gpu_grib_bits_pack_async.argtypes = [vp, pt, vp, u64, vp, vp, vp, vp]
+        lib.aec_gpu_grib_bits_unpack_async.restype = C.c_int
+        lib.aec_gpu_grib_bits_unpack_async.argtypes = [vp, pt, vp, u64, vp, sz, vp, vp, vp, vp]
+        lib.aec_gpu_grib_simple_pack_async.restype = C.c_int
+        lib.aec_gpu_grib_simple_pack_async.argtypes = [vp, pt, C.c_int, vp, vp, vp, vp, C.c_int, vp, u64, vp, vp, vp, vp, vp]
+        lib.aec_gpu_grib_simple_unpack_async.restype = C.c_int
+        lib.aec_gpu_grib_simple_unpack_async.argtypes = [vp, pt, C.c_int, vp, sz, vp, vp, vp, vp, vp, u64, vp, vp, vp]
+        lib.aec_gpu_grib_simple_to_ccsds_async.restype = C.c_int
+        lib.aec_gpu_grib_simple_to_ccsds_async.argtypes = [vp, pt, vp, sz, vp, vp, vp, u64, vp, vp, sz, vp, vp, vp, vp]
+        lib.aec_gpu_grib_ccsds_to_simple_async.restype = C.c_int
+        lib.aec_gpu_grib_ccsds_to_simple_async.argtypes = [vp, pt, vp, sz, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         _bound = True
     return lib
 
@@ -148,6 +169,22 @@ def bitmap_plan(nbits, options, block_size, rsi, elem, n_points, n_values):
                 work_offsets=offs[:n_values.size], tile_points=int(bp.tile_points), tiles=int(bp.tiles))
 
 
+def simple_plan(nbits, options, block_size, rsi, elem, n_values):
+    """aec_gpu_grib_simple_plan (host arithmetic, no device needed): the dict of plan() plus simple_bytes and simple_offsets
+    (the streams back to back), or None where the batch would be refused"""
+    t = Template(nbits, options, block_size, rsi)
+    n_values = _u64(n_values)
+    offs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    soffs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    sp = SimplePlan()
+    if not _lib().aec_gpu_grib_simple_plan(C.byref(t), elem, _host(n_values), n_values.size, C.byref(sp), _host(offs), _host(soffs)):
+        return None
+    p = sp.plan
+    return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
+                out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
+                work_offsets=offs[:n_values.size], simple_bytes=int(sp.simple_bytes), simple_offsets=soffs[:n_values.size])
+
+
 def _elem_of(t):
     import torch
     if t.dtype == torch.float32:
@@ -159,7 +196,8 @@ def _elem_of(t):
 
 class GribCodec:
     """One template 5.42 (nbits, compression options, block size, reference sample interval) and one aec_gpu context
-    (workspace) on the current torch device."""
+    (workspace) on the current torch device.  The simple_* and bits_* methods read and write template 5.0 / 7.0 (simple
+    packing) under the same nbits; block size and interval then only size the rooms of the work buffer."""
 
     def __init__(self, nbits, block_size=32, rsi=128, mask=AEC_DATA_PREPROCESS):
         import torch
@@ -290,7 +328,187 @@ class GribCodec:
                                                              _host(dso), nv.size, _ptr(d_dst), _ptr(d_bitmap), _host(bmo), _host(npts),
                                                              float(missing), _ptr(d_status), self._stream(stream))
 
+    # ---- enqueue, simple packing (templates 5.0 / 7.0) ------------------------------------------------
+    def simple_plan(self, n_values, elem=F32):
+        t = self.t
+        return simple_plan(t.nbits, t.options, t.block_size, t.rsi, elem, n_values)
+
+    def bits_pack_async(self, n_values, d_work, d_simple, simple_offsets, stream=None):
+        """rooms to streams: the X in the plan's rooms of d_work to ceil(n_values[i] * nbits / 8) bytes at d_simple +
+        simple_offsets[i] (bytes, a uint64 array on the host, any byte)"""
+        nv, so = _u64(n_values), _u64(simple_offsets)
+        return self.lib.aec_gpu_grib_bits_pack_async(self.ctx, C.byref(self.t), _host(nv), nv.size, _ptr(d_work), _ptr(d_simple), _host(so),
+                                                     self._stream(stream))
+
+    def bits_unpack_async(self, n_values, d_simple, simple_bytes, simple_offsets, simple_sizes, d_work, stream=None):
+        """streams to rooms; simple_sizes: section 7's data length per message (uint64 on the host) or None"""
+        nv, so, ss = _u64(n_values), _u64(simple_offsets), _u64(simple_sizes)
+        return self.lib.aec_gpu_grib_bits_unpack_async(self.ctx, C.byref(self.t), _host(nv), nv.size, _ptr(d_simple), simple_bytes, _host(so),
+                                                       _host(ss), _ptr(d_work), self._stream(stream))
+
+    def simple_pack_async(self, elem, d_src, src_offsets, n_values, D, params, d_work, d_fields, d_simple, simple_offsets, stream=None):
+        """quantise_async, then bits_pack_async"""
+        offs, nv, so = _u64(src_offsets), _u64(n_values), _u64(simple_offsets)
+        Dh = None if D is None else np.ascontiguousarray(D, dtype=np.int32)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_simple_pack_async(self.ctx, C.byref(self.t), elem, _ptr(d_src), _host(offs), _host(nv), _host(Dh),
+                                                       int(ph is not None), _host(ph), nv.size, _ptr(d_work), _ptr(d_fields), _ptr(d_simple),
+                                                       _host(so), self._stream(stream))
+
+    def simple_unpack_async(self, elem, d_simple, simple_bytes, simple_offsets, simple_sizes, n_values, params, dst_offsets, d_work, d_dst,
+                            stream=None):
+        """bits_unpack_async, then dequantise_async"""
+        so, ss, nv, dso = _u64(simple_offsets), _u64(simple_sizes), _u64(n_values), _u64(dst_offsets)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_simple_unpack_async(self.ctx, C.byref(self.t), elem, _ptr(d_simple), simple_bytes, _host(so), _host(ss),
+                                                         _host(nv), _host(ph), _host(dso), nv.size, _ptr(d_work), _ptr(d_dst),
+                                                         self._stream(stream))
+
+    def simple_to_ccsds_async(self, d_simple, simple_bytes, simple_offsets, simple_sizes, n_values, d_work, d_out, out_cap, d_chunks, d_table,
+                              d_result, stream=None):
+        """template 5.0 streams to template 5.42 streams: bits_unpack_async, then the chunk encoder; the outputs are pack_async's"""
+        so, ss, nv = _u64(simple_offsets), _u64(simple_sizes), _u64(n_values)
+        return self.lib.aec_gpu_grib_simple_to_ccsds_async(self.ctx, C.byref(self.t), _ptr(d_simple), simple_bytes, _host(so), _host(ss),
+                                                           _host(nv), nv.size, _ptr(d_work), _ptr(d_out), out_cap, _ptr(d_chunks),
+                                                           _ptr(d_table), _ptr(d_result), self._stream(stream))
+
+    def ccsds_to_simple_async(self, d_in, in_bytes, in_offsets, in_sizes, n_values, d_table, have_table, d_work, d_results, d_result,
+                              d_simple, simple_offsets, stream=None):
+        """template 5.42 streams to template 5.0 streams: the chunk decoder (with the pack's table, or bare), then bits_pack_async"""
+        ino, ins, nv, so = _u64(in_offsets), _u64(in_sizes), _u64(n_values), _u64(simple_offsets)
+        return self.lib.aec_gpu_grib_ccsds_to_simple_async(self.ctx, C.byref(self.t), _ptr(d_in), in_bytes, _host(ino), _host(ins), _host(nv),
+                                                           nv.size, _ptr(d_table), int(bool(have_table)), _ptr(d_work), _ptr(d_results),
+                                                           _ptr(d_result), _ptr(d_simple), _host(so), self._stream(stream))
+
     # ---- convenience (synchronising) -------------------------------------------------------------
+    def _simple_plan_or_raise(self, n_values, elem=F32):
+        pl = self.simple_plan(n_values, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_simple_plan)")
+        return pl
+
+    def bits_pack(self, d_work, n_values):
+        """X in the plan's rooms of d_work -> (uint8 tensor with the template 7.0 streams back to back, their byte offsets)"""
+        pl = self._simple_plan_or_raise(n_values)
+        d_simple = self.torch.empty(max(1, pl["simple_bytes"]), dtype=self.torch.uint8, device=d_work.device)
+        self._check(self.bits_pack_async(n_values, d_work, d_simple, pl["simple_offsets"]), "aec_gpu_grib_bits_pack_async")
+        return d_simple[:pl["simple_bytes"]], pl["simple_offsets"]
+
+    def bits_unpack(self, d_simple, simple_offsets, n_values, simple_sizes=None):
+        """template 7.0 streams at simple_offsets (bytes) of the uint8 tensor d_simple -> (d_work with the X in the plan's rooms,
+        the plan)"""
+        pl = self._simple_plan_or_raise(n_values)
+        d_work = self.torch.zeros(pl["work_bytes"] + 16, dtype=self.torch.uint8, device=d_simple.device)
+        self._check(self.bits_unpack_async(n_values, d_simple, d_simple.numel(), simple_offsets, simple_sizes, d_work),
+                    "aec_gpu_grib_bits_unpack_async")
+        return d_work, pl
+
+    def simple_pack(self, d_values, offsets, n_values, D, params=None):
+        """fields of n_values[i] elements at ELEMENT offsets[i] of the float tensor d_values -> (d_simple, simple_offsets, fields):
+        section 7 of field i under template 5.0 is d_simple[simple_offsets[i]:][:ceil(n_values[i] * nbits / 8)], fields the
+        FIELD_DTYPE records (R, E, D, status) of section 5"""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        pl = self._simple_plan_or_raise(n_values, elem)
+        n, dev = len(n_values), d_values.device
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_fields = torch.zeros(max(1, n) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_simple = torch.empty(max(1, pl["simple_bytes"]), dtype=torch.uint8, device=dev)
+        Dh = np.broadcast_to(np.asarray(D, dtype=np.int32), (n,))
+        self._check(self.simple_pack_async(elem, d_values, _u64(offsets) * np.uint64(elem), n_values, Dh, params, d_work, d_fields, d_simple,
+                                           pl["simple_offsets"]), "aec_gpu_grib_simple_pack_async")
+        return d_simple[:pl["simple_bytes"]], pl["simple_offsets"], d_fields.cpu().numpy().view(FIELD_DTYPE)[:n]
+
+    def simple_unpack(self, d_simple, simple_offsets, params, n_values, simple_sizes=None, dtype=None):
+        """template 7.0 streams -> a float tensor with the fields back to back; params the FIELD_DTYPE records of section 5"""
+        torch = self.torch
+        dtype = dtype or torch.float32
+        elem = F32 if dtype == torch.float32 else F64
+        pl = self._simple_plan_or_raise(n_values, elem)
+        n = len(n_values)
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(n_values, dtype=np.uint64))]).astype(np.uint64) * np.uint64(elem)
+        d_dst = torch.empty(int(dst_offsets[-1]) // elem, dtype=dtype, device=d_simple.device)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=d_simple.device)
+        self._check(self.simple_unpack_async(elem, d_simple, d_simple.numel(), simple_offsets, simple_sizes, n_values, params, dst_offsets[:n],
+                                             d_work, d_dst), "aec_gpu_grib_simple_unpack_async")
+        return d_dst
+
+    def simple_to_ccsds(self, d_simple, simple_offsets, n_values, simple_sizes=None, want_offsets=False):
+        """template 7.0 streams -> (d_out, spans, d_table) as pack() gives them: section 7 under template 5.42 of field i is
+        d_out[spans[i][0]:][:spans[i][1]].  R, E, D and nbits of section 5 stay as they are."""
+        torch = self.torch
+        pl = self._simple_plan_or_raise(n_values)
+        n, dev = len(n_values), d_simple.device
+        d_out = torch.empty(pl["out_bound"], dtype=torch.uint8, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_rec = torch.zeros(max(1, n) * 2, dtype=torch.int64, device=dev)
+        d_res = torch.zeros(gpu.ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev) if want_offsets else None
+        self._check(self.simple_to_ccsds_async(d_simple, d_simple.numel(), simple_offsets, simple_sizes, n_values, d_work, d_out, d_out.numel(),
+                                               d_rec, d_table, d_res), "aec_gpu_grib_simple_to_ccsds_async")
+        if n and d_res.cpu().numpy().view(gpu.ENC_RESULT_DTYPE)[0]["overflow"]:
+            raise RuntimeError("encode overflow")
+        rec = d_rec.cpu().numpy().view(np.uint64).view(BATCH_CHUNK_DTYPE)[:n]
+        return d_out, [(int(r["base_bits"]) // 8, (int(r["bits"]) + 7) // 8) for r in rec], d_table
+
+    def ccsds_to_simple(self, d_streams, spans, n_values, d_table=None):
+        """template 7.42 streams (spans[i] = (start, bytes) of the uint8 tensor d_streams; with d_table no index pass runs) ->
+        (d_simple, simple_offsets, per-field decode records)"""
+        torch = self.torch
+        pl = self._simple_plan_or_raise(n_values)
+        n, dev = len(n_values), d_streams.device
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_simple = torch.empty(max(1, pl["simple_bytes"]), dtype=torch.uint8, device=dev)
+        have = d_table is not None
+        if not have:
+            d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev)
+        d_results = torch.zeros(max(1, n) * gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_result = torch.zeros(gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        in_offs = None if have else [s for s, _ in spans]
+        in_sizes = None if have else [b for _, b in spans]
+        self._check(self.ccsds_to_simple_async(d_streams, d_streams.numel(), in_offs, in_sizes, n_values, d_table, have, d_work, d_results,
+                                               d_result, d_simple, pl["simple_offsets"]), "aec_gpu_grib_ccsds_to_simple_async")
+        return d_simple[:pl["simple_bytes"]], pl["simple_offsets"], d_results.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[:n]
+
+    def simple_pack_bitmap(self, d_values, offsets, n_points, d_bitmap, bitmap_offsets, n_values, D, params=None):
+        """simple_pack() over whole grids with bitmaps, as the two calls the header names: quantise_bitmap_async, then
+        bits_pack_async -> (d_simple, simple_offsets, fields); the streams hold the X of the present points only"""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        if self.bitmap_plan(n_points, n_values, elem) is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_bitmap_plan)")
+        pl = self._simple_plan_or_raise(n_values, elem)
+        n, dev = len(n_values), d_values.device
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_fields = torch.zeros(max(1, n) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_simple = torch.empty(max(1, pl["simple_bytes"]), dtype=torch.uint8, device=dev)
+        Dh = np.broadcast_to(np.asarray(D, dtype=np.int32), (n,))
+        self._check(self.quantise_bitmap_async(elem, d_values, _u64(offsets) * np.uint64(elem), n_values, Dh, params, d_work, d_fields,
+                                               d_bitmap, bitmap_offsets, n_points), "aec_gpu_grib_quantise_bitmap_async")
+        self._check(self.bits_pack_async(n_values, d_work, d_simple, pl["simple_offsets"]), "aec_gpu_grib_bits_pack_async")
+        return d_simple[:pl["simple_bytes"]], pl["simple_offsets"], d_fields.cpu().numpy().view(FIELD_DTYPE)[:n]
+
+    def simple_unpack_bitmap(self, d_simple, simple_offsets, params, n_values, n_points, d_bitmap, bitmap_offsets, missing=9999.0,
+                             simple_sizes=None, dtype=None):
+        """simple_unpack() into whole grids: bits_unpack_async, then dequantise_bitmap_async -> (float tensor with the grids
+        back to back, per-field status: 0 or MISMATCH)"""
+        torch = self.torch
+        dtype = dtype or torch.float32
+        elem = F32 if dtype == torch.float32 else F64
+        if self.bitmap_plan(n_points, n_values, elem) is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_bitmap_plan)")
+        pl = self._simple_plan_or_raise(n_values, elem)
+        n, dev = len(n_values), d_simple.device
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(n_points, dtype=np.uint64))]).astype(np.uint64) * np.uint64(elem)
+        d_dst = torch.empty(int(dst_offsets[-1]) // elem, dtype=dtype, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(max(1, n), dtype=torch.int32, device=dev)
+        self._check(self.bits_unpack_async(n_values, d_simple, d_simple.numel(), simple_offsets, simple_sizes, d_work),
+                    "aec_gpu_grib_bits_unpack_async")
+        self._check(self.dequantise_bitmap_async(elem, d_work, n_values, params, dst_offsets[:n], d_dst, d_bitmap, bitmap_offsets, n_points,
+                                                 missing, d_status), "aec_gpu_grib_dequantise_bitmap_async")
+        return d_dst, d_status.cpu().numpy()[:n].astype(np.uint32)
+
     def bitmap(self, d_values, offsets, n_points, missing):
         """grids of n_points[i] elements at ELEMENT offsets[i] of the float tensor d_values -> (d_bitmap, bitmap_offsets,
         counts): the bitmaps back to back in a uint8 tensor, their byte offsets and the present points of every grid as a
