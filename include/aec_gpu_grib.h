@@ -1,7 +1,7 @@
 /*
  * aec_gpu_grib.h -- GRIB2 CCSDS packing (data representation template 5.42 / 7.42, ecCodes' grid_ccsds) and simple packing
  * (template 5.0 / 7.0, grid_simple) that stay on the device: float fields to section-7 streams and back, and one kind of
- * stream to the other.
+ * stream to the other; and complex packing (templates 5.2 / 5.3), read into floats or into either kind of stream.
  *
  * Between a field of floats and the coder (aec_gpu.h) sits GRIB2's simple packing, WMO regulation 92.9.4:
  *       Y * 10^D = R + X * 2^E
@@ -67,9 +67,53 @@
  * construction), and, through aec_gpu_grib_quantise_bitmap_async / aec_gpu_grib_dequantise_bitmap_async, fields with
  * bitmaps -- these need no entry point of their own.
  *
+ * COMPLEX PACKING (templates 5.2 / 7.2 and, with spatial differencing, 5.3 / 7.3 -- what NCEP writes GFS, NAM, HRRR and RAP
+ * in; the *_complex_* calls at the end of this header).  READING only: streams to X rooms, and from there to floats, to 5.42
+ * streams or (through aec_gpu_grib_bits_pack_async) to 5.0 streams.  R, E and D pass from one section 5 to the other
+ * unchanged and only the integers X move from one container to the other, so the conversions are lossless.
+ * Bits are counted as in simple packing (bit b of a stream is bit 7 - b % 8 of byte b / 8; an integer of w bits is
+ * big-endian).  What section 5 says comes per field in a HOST aec_gpu_grib_complex_field.  Section 7 of field i is the
+ * complex_bytes_each[i] bytes at d_complex + complex_offsets[i] (HOST arrays; any byte, neighbours may touch, any order):
+ *   1. extra descriptors, for order >= 1 and extra_octets > 0: ival1, then ival2 if order = 2, then minsd, each extra_octets
+ *      octets in sign-magnitude form (the first bit is the sign, the rest the magnitude; "minus zero" is 0).  With
+ *      extra_octets = 0 all three are 0.
+ *   2. group references: NG integers of ref_bits bits, then zero bits up to a whole byte (ref_bits 0: all 0, the part is empty)
+ *   3. group widths: NG integers of width_bits bits, padded to a byte; width_g = width_ref + stored
+ *   4. group lengths: NG integers of length_bits bits, padded to a byte; len_g = length_ref + stored * length_inc, except
+ *      len_(NG-1) = last_length (the stored value of the last group is ignored)
+ *   5. packed values: group after group without padding, len_g integers of width_g bits each (none for width 0)
+ * With n = n_values[i]:  s_j = ref_g + packed_j for value j of group g;  order 0: X_j = s_j;  order 1: X_0 = ival1,
+ * X_j = X_(j-1) + s_j + minsd;  order 2: X_0 = ival1, X_1 = ival2, X_j = 2 X_(j-1) - X_(j-2) + s_j + minsd.  The first `order`
+ * values of the packed string are parsed and ignored; with n = 1 and order 2, ival2 is read past and not used.  ALL
+ * ARITHMETIC IS TWO'S COMPLEMENT MODULO 2^64: a second-order sum may pass through values far outside 32 bits and still land
+ * exactly.
+ * X goes into the plan's rooms under the TARGET template t: containers follow t->nbits, the last block is padded with the
+ * last X -- byte for byte the room aec_gpu_grib_quantise_async leaves for the same X.  d_cx (n_fields aec_gpu_grib_cx on the
+ * device) receives x_min and x_max, the signed reading of the modulo-2^64 X, and status bits:
+ *   AEC_GPU_GRIB_CX_RANGE      some X lies outside [0, 2^nbits - 1].  The stored X are taken modulo 2^nbits (the coder never
+ *                              sees a sample out of range); x_min and x_max are exact, so the caller can choose a wider
+ *                              nbits and call again.
+ *   AEC_GPU_GRIB_CX_MALFORMED  the group lengths do not sum to n, or a width exceeds 32, or the packed values end behind
+ *                              complex_bytes_each[i].  The field's X, x_min, x_max and RANGE bit are then unspecified, its
+ *                              whole room is still written, and every other field is exact.
+ * No load leaves [d_complex + complex_offsets[i], + complex_bytes_each[i]), no store leaves the field's room, d_cx or the
+ * context's workspace, whatever the bytes contain.  The device's running sums do not wrap -- THE RULE: a group length above n
+ * counts as n + 1, a width above 32 counts as all the bits the stream has left and one more, and the running sums of lengths
+ * and of bits are held at n + 1 and at 8 * (bytes behind the tables) + 1; a sum that reached its cap is MALFORMED.  An
+ * integer that would cross the stream's end reads as 0.
+ * The host answers AEC_CONF_ERROR with nothing enqueued for: whatever aec_gpu_grib_plan refuses for t and n_values;
+ * missing != 0; order > 2; extra_octets > 8 (order >= 1); a bit count above 32; n_groups == 0 or n_groups > n_values[i];
+ * complex_bytes_each[i] smaller than the extra descriptors plus the three tables, or 2^35 and more; a stream that leaves
+ * [0, complex_bytes); more than 2^31 - 1 groups or 2^25 tiles of 64 groups in a batch.
+ * Out of scope: missing-value management 1 and 2 (it needs the present-point count back on the host; a follow-up that maps
+ * onto the bitmap calls); NG = 0 (constant fields); WRITING complex packing (it needs a group-splitting heuristic); the
+ * row-by-row packings 5.50 and up.  Fields with a section 6 bitmap compose through d_work with
+ * aec_gpu_grib_dequantise_bitmap_async, as for simple packing.
+ *
  * OUT OF SCOPE: fields without a present point (a writer sets nbits 0 and drops section 7), bitmap indicator 254 and
- * predefined bitmaps (the caller hands over whichever bitmap applies); complex, second-order and JPEG packings; parsing or
- * writing GRIB messages themselves; a quantiser fused into the encoder or into the bit packer.
+ * predefined bitmaps (the caller hands over whichever bitmap applies); writing complex packing, complex packing with
+ * missing-value management or without a group, the row-by-row (second-order) packings 5.50 and up and the JPEG and PNG
+ * packings; parsing or writing GRIB messages themselves; a quantiser fused into the encoder or into the bit packer.
  */
 #ifndef AEC_GPU_GRIB_H
 #define AEC_GPU_GRIB_H 1
@@ -345,6 +389,79 @@ AEC_GPU_API int aec_gpu_grib_ccsds_to_simple_async(aec_gpu_ctx *ctx, const aec_g
                                                    int have_table, void *d_work, aec_gpu_dec_result *d_results,
                                                    aec_gpu_dec_result *d_result, void *d_simple, const uint64_t *simple_offsets,
                                                    void *stream);
+
+/*
+ * ---- complex packing (templates 5.2 / 5.3), reading -----------------------------------------------------------------------
+ * What section 5 of one message says (HOST; the contract is COMPLEX PACKING at the head of this file).
+ */
+typedef struct aec_gpu_grib_complex_field_s {
+    uint32_t ref_bits;      /* octet 20: bits of a group reference, 0..32 */
+    uint32_t n_groups;      /* octets 32-35: NG >= 1 */
+    uint32_t width_ref;     /* octet 36 */
+    uint32_t width_bits;    /* octet 37: 0..32 */
+    uint32_t length_ref;    /* octets 38-41 */
+    uint32_t length_inc;    /* octet 42 */
+    uint32_t last_length;   /* octets 43-46: true length of the last group */
+    uint32_t length_bits;   /* octet 47: 0..32 */
+    uint32_t order;         /* 0: template 5.2; 1 or 2: template 5.3 octet 48 */
+    uint32_t extra_octets;  /* 5.3 octet 49: 0..8; ignored for order 0 */
+    uint32_t missing;       /* octet 23: must be 0 (see out of scope) */
+} aec_gpu_grib_complex_field;
+
+#define AEC_GPU_GRIB_CX_RANGE     1u  /* some X lies outside [0, 2^nbits - 1]; the stored X are taken modulo 2^nbits */
+#define AEC_GPU_GRIB_CX_MALFORMED 2u  /* lengths do not sum to n, a width above 32, or the packed values leave the stream */
+
+/* the per-field record of an expansion, on the device (d_cx), 24 bytes */
+typedef struct aec_gpu_grib_cx_s {
+    int64_t x_min, x_max;   /* the signed reading of the modulo-2^64 X */
+    uint32_t status;        /* AEC_GPU_GRIB_CX_* bits */
+    uint32_t pad;           /* written as 0 */
+} aec_gpu_grib_cx;
+
+/*
+ * Host arithmetic only (1 = taken, 0 = refused: whatever aec_gpu_grib_plan refuses, and what the contract lists of the
+ * descriptors).  plan is what aec_gpu_grib_plan gives for t and n_values, its workspace_bytes grown by this layer's
+ * descriptors, group tables (24 bytes a group) and tile aggregates.  tile_values = 1024 / container is the values one
+ * wavefront of the value kernels owns (1 KiB of room), value_tiles the sum of ceil(room_i / 1024), group_tiles the sum of
+ * ceil(n_groups_i / 64).
+ */
+typedef struct aec_gpu_grib_complex_plan_s {
+    aec_gpu_grib_plan_t plan;
+    uint64_t tile_values;
+    uint64_t value_tiles;
+    uint64_t group_tiles;
+} aec_gpu_grib_complex_plan_t;
+AEC_GPU_API int aec_gpu_grib_complex_plan(const aec_gpu_grib_template *t, int elem, const uint64_t *n_values,
+                                          const aec_gpu_grib_complex_field *fields, uint64_t n_fields,
+                                          aec_gpu_grib_complex_plan_t *plan, uint64_t *work_offsets);
+
+/* Streams to rooms, and d_cx (8-byte aligned).  d_work: the plan's work_bytes, 16-byte aligned; the up to 15 bytes between
+ * rooms are not written.  n_fields == 0: AEC_OK, nothing is enqueued (so for the two calls below). */
+AEC_GPU_API int aec_gpu_grib_complex_expand_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t,
+                                                  const aec_gpu_grib_complex_field *fields, const uint64_t *n_values,
+                                                  uint64_t n_fields, const void *d_complex, size_t complex_bytes,
+                                                  const uint64_t *complex_offsets, const uint64_t *complex_bytes_each, void *d_work,
+                                                  aec_gpu_grib_cx *d_cx, void *stream);
+
+/* 5.2 / 5.3 streams to floats: the expansion, then aec_gpu_grib_dequantise_async with the caller's R, E and D (params,
+ * dst_offsets and d_dst as there).  The values of a field whose record says RANGE or MALFORMED are those of its stored X. */
+AEC_GPU_API int aec_gpu_grib_complex_unpack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t, int elem,
+                                                  const aec_gpu_grib_complex_field *fields, const void *d_complex, size_t complex_bytes,
+                                                  const uint64_t *complex_offsets, const uint64_t *complex_bytes_each,
+                                                  const uint64_t *n_values, const aec_gpu_grib_field *params,
+                                                  const uint64_t *dst_offsets, uint64_t n_fields, void *d_work, void *d_dst,
+                                                  aec_gpu_grib_cx *d_cx, void *stream);
+
+/* 5.2 / 5.3 streams to 5.42 streams: the expansion, then aec_gpu_encode_chunks_async over the rooms.  d_work, d_out, d_chunks,
+ * d_rsi_bit_offsets and d_result are byte for byte what aec_gpu_grib_pack_async leaves for fields that quantise to the same
+ * X.  No float is touched: the caller carries R, E and D over from section 5 and writes t->nbits into the new one. */
+AEC_GPU_API int aec_gpu_grib_complex_to_ccsds_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t,
+                                                    const aec_gpu_grib_complex_field *fields, const void *d_complex,
+                                                    size_t complex_bytes, const uint64_t *complex_offsets,
+                                                    const uint64_t *complex_bytes_each, const uint64_t *n_values, uint64_t n_fields,
+                                                    void *d_work, void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
+                                                    uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result,
+                                                    aec_gpu_grib_cx *d_cx, void *stream);
 
 #ifdef __cplusplus
 }

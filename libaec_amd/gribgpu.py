@@ -1,5 +1,6 @@
 """GRIB2 CCSDS packing and simple packing that stay on the device (include/aec_gpu_grib.h) for torch tensors living in HBM:
-float fields to section-7 streams and back, and template 5.0 streams to template 5.42 streams and back.
+float fields to section-7 streams and back, template 5.0 streams to template 5.42 streams and back, and complex packing
+(templates 5.2 / 5.3) read into floats, template 5.42 streams or template 5.0 streams.
 
 torch is used for device memory and streams only; the minimum / maximum, the parameters, the quantisation and the coder are
 kernels launched by libaec.so.0 through the C entry points declared in aec_gpu_grib.h.
@@ -15,6 +16,7 @@ AEC_CONF_ERROR = -1
 F32, F64 = 4, 8                       # elem: the element type by its size
 BAD, CONSTANT, CLAMPED = 1, 2, 4      # status bits of a field record
 MISMATCH = 8                          # ... of the bitmap calls: the bitmap does not hold n_values ones
+CX_RANGE, CX_MALFORMED = 1, 2         # status bits of a complex-packing record (CX_DTYPE)
 
 
 class Template(C.Structure):
@@ -43,6 +45,18 @@ class SimplePlan(C.Structure):
     _fields_ = [("plan", Plan), ("simple_bytes", C.c_size_t)]
 
 
+class ComplexField(C.Structure):
+    """aec_gpu_grib_complex_field: what section 5 of a template 5.2 / 5.3 message says"""
+    _fields_ = [(k, C.c_uint32) for k in ("ref_bits", "n_groups", "width_ref", "width_bits", "length_ref", "length_inc", "last_length",
+                                          "length_bits", "order", "extra_octets", "missing")]
+
+
+class ComplexPlan(C.Structure):
+    """aec_gpu_grib_complex_plan_t"""
+    _fields_ = [("plan", Plan), ("tile_values", C.c_uint64), ("value_tiles", C.c_uint64), ("group_tiles", C.c_uint64)]
+
+
+CX_DTYPE = np.dtype([("x_min", "<i8"), ("x_max", "<i8"), ("status", "<u4"), ("pad", "<u4")])     # aec_gpu_grib_cx
 FIELD_DTYPE = np.dtype([("R", "<f4"), ("E", "<i4"), ("D", "<i4"), ("status", "<u4")])      # aec_gpu_grib_field
 BATCH_CHUNK_DTYPE = np.dtype([("base_bits", "<u8"), ("bits", "<u8")])
 
@@ -99,8 +113,28 @@ def _lib():
         lib.aec_gpu_grib_simple_to_ccsds_async.argtypes = [vp, pt, vp, sz, vp, vp, vp, u64, vp, vp, sz, vp, vp, vp, vp]
         lib.aec_gpu_grib_ccsds_to_simple_async.restype = C.c_int
         lib.aec_gpu_grib_ccsds_to_simple_async.argtypes = [vp, pt, vp, sz, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+        if not hasattr(lib, "aec_gpu_grib_complex_expand_async"):
+            raise RuntimeError("this libaec.so.0 has no complex packing (aec_gpu_grib_complex_*): rebuild it")
+        lib.aec_gpu_grib_complex_plan.restype = C.c_int
+        lib.aec_gpu_grib_complex_plan.argtypes = [pt, C.c_int, vp, vp, u64, C.POINTER(ComplexPlan), vp]
+        lib.aec_gpu_grib_complex_expand_async.restype = C.c_int
+        lib.aec_gpu_grib_complex_expand_async.argtypes = [vp, pt, vp, vp, u64, vp, sz, vp, vp, vp, vp, vp]
+        lib.aec_gpu_grib_complex_unpack_async.restype = C.c_int
+        lib.aec_gpu_grib_complex_unpack_async.argtypes = [vp, pt, C.c_int, vp, vp, sz, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]
+        lib.aec_gpu_grib_complex_to_ccsds_async.restype = C.c_int
+        lib.aec_gpu_grib_complex_to_ccsds_async.argtypes = [vp, pt, vp, vp, sz, vp, vp, vp, u64, vp, vp, sz, vp, vp, vp, vp, vp]
         _bound = True
     return lib
+
+
+def complex_fields(fields):
+    """a host array of aec_gpu_grib_complex_field from ComplexField objects, dicts with its members' names, or such an array"""
+    if isinstance(fields, C.Array):
+        return fields
+    arr = (ComplexField * max(1, len(fields)))()
+    for i, f in enumerate(fields):
+        arr[i] = f if isinstance(f, ComplexField) else ComplexField(**{k: int(v) for k, v in f.items()})
+    return arr
 
 
 def _u64(a):
@@ -183,6 +217,24 @@ def simple_plan(nbits, options, block_size, rsi, elem, n_values):
     return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
                 out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
                 work_offsets=offs[:n_values.size], simple_bytes=int(sp.simple_bytes), simple_offsets=soffs[:n_values.size])
+
+
+def complex_plan(nbits, options, block_size, rsi, elem, n_values, fields):
+    """aec_gpu_grib_complex_plan (host arithmetic, no device needed): the dict of plan() plus tile_values, value_tiles and
+    group_tiles, or None where the batch would be refused"""
+    t = Template(nbits, options, block_size, rsi)
+    n_values = _u64(n_values)
+    if len(fields) != n_values.size:
+        raise ValueError("fields and n_values are per field")
+    offs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    cp = ComplexPlan()
+    if not _lib().aec_gpu_grib_complex_plan(C.byref(t), elem, _host(n_values), complex_fields(fields), n_values.size, C.byref(cp), _host(offs)):
+        return None
+    p = cp.plan
+    return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
+                out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
+                work_offsets=offs[:n_values.size], tile_values=int(cp.tile_values), value_tiles=int(cp.value_tiles),
+                group_tiles=int(cp.group_tiles))
 
 
 def _elem_of(t):
@@ -380,7 +432,96 @@ class GribCodec:
                                                            nv.size, _ptr(d_table), int(bool(have_table)), _ptr(d_work), _ptr(d_results),
                                                            _ptr(d_result), _ptr(d_simple), _host(so), self._stream(stream))
 
+    # ---- enqueue, complex packing (templates 5.2 / 5.3), reading ---------------------------------------
+    def complex_plan(self, n_values, fields, elem=F32):
+        t = self.t
+        return complex_plan(t.nbits, t.options, t.block_size, t.rsi, elem, n_values, fields)
+
+    def complex_expand_async(self, fields, n_values, d_complex, complex_bytes, complex_offsets, complex_sizes, d_work, d_cx, stream=None):
+        """streams to rooms: fields as complex_fields() takes them; complex_offsets / complex_sizes (section 7's data length per
+        message): uint64 arrays on the host; d_cx: n * 24 bytes (CX_DTYPE)"""
+        nv, co, cs = _u64(n_values), _u64(complex_offsets), _u64(complex_sizes)
+        return self.lib.aec_gpu_grib_complex_expand_async(self.ctx, C.byref(self.t), complex_fields(fields), _host(nv), nv.size, _ptr(d_complex),
+                                                          complex_bytes, _host(co), _host(cs), _ptr(d_work), _ptr(d_cx), self._stream(stream))
+
+    def complex_unpack_async(self, elem, fields, d_complex, complex_bytes, complex_offsets, complex_sizes, n_values, params, dst_offsets,
+                             d_work, d_dst, d_cx, stream=None):
+        """complex_expand_async, then dequantise_async"""
+        nv, co, cs, dso = _u64(n_values), _u64(complex_offsets), _u64(complex_sizes), _u64(dst_offsets)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        return self.lib.aec_gpu_grib_complex_unpack_async(self.ctx, C.byref(self.t), elem, complex_fields(fields), _ptr(d_complex), complex_bytes,
+                                                          _host(co), _host(cs), _host(nv), _host(ph), _host(dso), nv.size, _ptr(d_work),
+                                                          _ptr(d_dst), _ptr(d_cx), self._stream(stream))
+
+    def complex_to_ccsds_async(self, fields, d_complex, complex_bytes, complex_offsets, complex_sizes, n_values, d_work, d_out, out_cap,
+                               d_chunks, d_table, d_result, d_cx, stream=None):
+        """template 5.2 / 5.3 streams to template 5.42 streams: complex_expand_async, then the chunk encoder; the outputs are
+        pack_async's"""
+        nv, co, cs = _u64(n_values), _u64(complex_offsets), _u64(complex_sizes)
+        return self.lib.aec_gpu_grib_complex_to_ccsds_async(self.ctx, C.byref(self.t), complex_fields(fields), _ptr(d_complex), complex_bytes,
+                                                            _host(co), _host(cs), _host(nv), nv.size, _ptr(d_work), _ptr(d_out), out_cap,
+                                                            _ptr(d_chunks), _ptr(d_table), _ptr(d_result), _ptr(d_cx), self._stream(stream))
+
     # ---- convenience (synchronising) -------------------------------------------------------------
+    def _complex_plan_or_raise(self, n_values, fields, elem=F32):
+        pl = self.complex_plan(n_values, fields, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_complex_plan)")
+        return pl
+
+    def complex_expand(self, d_complex, complex_offsets, complex_sizes, fields, n_values):
+        """template 7.2 / 7.3 streams at complex_offsets (bytes) of the uint8 tensor d_complex -> (d_work with the X in the plan's
+        rooms, the plan, the CX_DTYPE records: x_min, x_max and status per field)"""
+        torch = self.torch
+        pl = self._complex_plan_or_raise(n_values, fields)
+        n = len(n_values)
+        d_work = torch.zeros(pl["work_bytes"] + 16, dtype=torch.uint8, device=d_complex.device)
+        d_cx = torch.zeros(max(1, n) * CX_DTYPE.itemsize, dtype=torch.uint8, device=d_complex.device)
+        self._check(self.complex_expand_async(fields, n_values, d_complex, d_complex.numel(), complex_offsets, complex_sizes, d_work, d_cx),
+                    "aec_gpu_grib_complex_expand_async")
+        return d_work, pl, d_cx.cpu().numpy().view(CX_DTYPE)[:n]
+
+    def complex_unpack(self, d_complex, complex_offsets, complex_sizes, fields, params, n_values, dtype=None):
+        """template 7.2 / 7.3 streams -> (a float tensor with the fields back to back, the CX_DTYPE records); params the
+        FIELD_DTYPE records (R, E, D) of section 5"""
+        torch = self.torch
+        dtype = dtype or torch.float32
+        elem = F32 if dtype == torch.float32 else F64
+        pl = self._complex_plan_or_raise(n_values, fields, elem)
+        n, dev = len(n_values), d_complex.device
+        dst_offsets = np.concatenate([[0], np.cumsum(np.asarray(n_values, dtype=np.uint64))]).astype(np.uint64) * np.uint64(elem)
+        d_dst = torch.empty(int(dst_offsets[-1]) // elem, dtype=dtype, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_cx = torch.zeros(max(1, n) * CX_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self._check(self.complex_unpack_async(elem, fields, d_complex, d_complex.numel(), complex_offsets, complex_sizes, n_values, params,
+                                              dst_offsets[:n], d_work, d_dst, d_cx), "aec_gpu_grib_complex_unpack_async")
+        return d_dst, d_cx.cpu().numpy().view(CX_DTYPE)[:n]
+
+    def complex_to_ccsds(self, d_complex, complex_offsets, complex_sizes, fields, n_values, want_offsets=False):
+        """template 7.2 / 7.3 streams -> (d_out, spans, d_table, the CX_DTYPE records): section 7 under template 5.42 of field i is
+        d_out[spans[i][0]:][:spans[i][1]].  R, E and D of section 5 stay as they are; nbits becomes this codec's."""
+        torch = self.torch
+        pl = self._complex_plan_or_raise(n_values, fields)
+        n, dev = len(n_values), d_complex.device
+        d_out = torch.empty(pl["out_bound"], dtype=torch.uint8, device=dev)
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_rec = torch.zeros(max(1, n) * 2, dtype=torch.int64, device=dev)
+        d_res = torch.zeros(gpu.ENC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_cx = torch.zeros(max(1, n) * CX_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev) if want_offsets else None
+        self._check(self.complex_to_ccsds_async(fields, d_complex, d_complex.numel(), complex_offsets, complex_sizes, n_values, d_work, d_out,
+                                                d_out.numel(), d_rec, d_table, d_res, d_cx), "aec_gpu_grib_complex_to_ccsds_async")
+        if n and d_res.cpu().numpy().view(gpu.ENC_RESULT_DTYPE)[0]["overflow"]:
+            raise RuntimeError("encode overflow")
+        rec = d_rec.cpu().numpy().view(np.uint64).view(BATCH_CHUNK_DTYPE)[:n]
+        return d_out, [(int(r["base_bits"]) // 8, (int(r["bits"]) + 7) // 8) for r in rec], d_table, d_cx.cpu().numpy().view(CX_DTYPE)[:n]
+
+    def complex_to_simple(self, d_complex, complex_offsets, complex_sizes, fields, n_values):
+        """template 7.2 / 7.3 streams -> (d_simple, simple_offsets, the CX_DTYPE records): complex_expand, then bits_pack"""
+        d_work, pl, cx = self.complex_expand(d_complex, complex_offsets, complex_sizes, fields, n_values)
+        d_simple, simple_offsets = self.bits_pack(d_work, n_values)
+        return d_simple, simple_offsets, cx
+
     def _simple_plan_or_raise(self, n_values, elem=F32):
         pl = self.simple_plan(n_values, elem)
         if pl is None:
