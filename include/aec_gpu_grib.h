@@ -1,7 +1,8 @@
 /*
  * aec_gpu_grib.h -- GRIB2 CCSDS packing (data representation template 5.42 / 7.42, ecCodes' grid_ccsds) and simple packing
  * (template 5.0 / 7.0, grid_simple) that stay on the device: float fields to section-7 streams and back, and one kind of
- * stream to the other; and complex packing (templates 5.2 / 5.3), read into floats or into either kind of stream.
+ * stream to the other; and complex packing (templates 5.2 / 5.3), read into floats or into either kind of stream and written
+ * from floats or from either kind of stream.
  *
  * Between a field of floats and the coder (aec_gpu.h) sits GRIB2's simple packing, WMO regulation 92.9.4:
  *       Y * 10^D = R + X * 2^E
@@ -68,9 +69,10 @@
  * bitmaps -- these need no entry point of their own.
  *
  * COMPLEX PACKING (templates 5.2 / 7.2 and, with spatial differencing, 5.3 / 7.3 -- what NCEP writes GFS, NAM, HRRR and RAP
- * in; the *_complex_* calls at the end of this header).  READING only: streams to X rooms, and from there to floats, to 5.42
- * streams or (through aec_gpu_grib_bits_pack_async) to 5.0 streams.  R, E and D pass from one section 5 to the other
- * unchanged and only the integers X move from one container to the other, so the conversions are lossless.
+ * in; the *_complex_* calls at the end of this header).  READING: streams to X rooms, and from there to floats, to 5.42
+ * streams or (through aec_gpu_grib_bits_pack_async) to 5.0 streams.  WRITING (THE WRITER'S RULE below): X rooms to streams with
+ * groups of a fixed length, from floats, from 5.42 streams or from 5.0 streams.  R, E and D pass from one section 5 to the
+ * other unchanged and only the integers X move from one container to the other, so the conversions are lossless.
  * Bits are counted as in simple packing (bit b of a stream is bit 7 - b % 8 of byte b / 8; an integer of w bits is
  * big-endian).  What section 5 says comes per field in a HOST aec_gpu_grib_complex_field.  Section 7 of field i is the
  * complex_bytes_each[i] bytes at d_complex + complex_offsets[i] (HOST arrays; any byte, neighbours may touch, any order):
@@ -105,14 +107,44 @@
  * missing != 0; order > 2; extra_octets > 8 (order >= 1); a bit count above 32; n_groups == 0 or n_groups > n_values[i];
  * complex_bytes_each[i] smaller than the extra descriptors plus the three tables, or 2^35 and more; a stream that leaves
  * [0, complex_bytes); more than 2^31 - 1 groups or 2^25 tiles of 64 groups in a batch.
+ * THE WRITER'S RULE.  Writing shares the stream definition above (items 1 - 5) and fixes every bit of the output.  A batch is
+ * written under one aec_gpu_grib_complex_write: the order o (0: template 5.2; 1 or 2: template 5.3) and the group length G (16,
+ * 32, 64, 128 or 256).  The input is X_0 .. X_(n-1), the field's room taken modulo 2^nbits as aec_gpu_grib_bits_pack_async takes
+ * it; the samples that pad the last block are never used.
+ *   differences  d_j for j >= o is X_j (o = 0), X_j - X_(j-1) (o = 1) or X_j - 2 X_(j-1) + X_(j-2) (o = 2), exact signed integers.
+ *                minsd is the smallest d_j, j >= o, for o >= 1; 0 for o = 0 and where there is no such j (n <= o).
+ *                s_j = d_j - minsd, so 0 <= s_j < 2^(nbits + o).
+ *   groups       NG = ceil(n / G); group g holds the values [g G, min(n, (g + 1) G)), its COUNTED values are those with j >= o.
+ *                ref_g is the smallest s_j of the counted values, width_g the bit length of (largest s_j - ref_g); both are 0
+ *                for a group without a counted value.  packed_j = s_j - ref_g for counted values and 0 for the first o values,
+ *                which a reader parses and ignores.
+ *   section 5    ref_bits is the bit length of the largest ref_g, width_ref the smallest width_g, width_bits the bit length of
+ *                (largest width_g - width_ref); length_ref = G, length_inc = 1, length_bits = 0 (the lengths table is empty),
+ *                last_length = n - (NG - 1) G; extra_octets = ceil((nbits + o) / 8) for o >= 1, else 0 -- a function of the
+ *                template alone; missing = 0; ival1 = X_0, ival2 = X_1 (0 when n = 1); minsd in sign and magnitude, zero
+ *                written as plus zero.
+ * The host refuses nbits + o > 32: that keeps every s_j, reference and width within 32 bits, so the writer has no status bit.
+ * The stream of field i is S_i bytes, a number only the device knows; B_i = head + ceil(NG (nbits + o) / 8) + ceil(6 NG / 8) +
+ * ceil(n (nbits + o) / 8), head = (o + 1) * extra_octets for o >= 1 and else 0, is host arithmetic and S_i <= B_i always.
+ * Streams go to d_complex + complex_offsets[i] (a HOST array: any byte, any order); the host checks that every range
+ * [complex_offsets[i], + B_i) lies inside [0, complex_cap) and that no two of them overlap.  EXACTLY S_i BYTES ARE WRITTEN, EACH
+ * ONCE: the bytes from S_i to B_i are not touched, nothing else is written except d_cxw and the context's workspace, and S_i
+ * may be 0 (a field of zeros at order 0 has no head, no reference bits and no width bits).  d_cxw (n_fields aec_gpu_grib_cxw on
+ * the device, 8-byte aligned) receives per field what goes into section 5 -- what the reading calls take back as their
+ * aec_gpu_grib_complex_field -- and S_i.  No load leaves the n values of a field's room.
+ * The host answers AEC_CONF_ERROR with nothing enqueued for: whatever aec_gpu_grib_plan refuses; order > 2; a group_length
+ * outside the five values; nbits + order > 32; a d_work off its 16 bytes or a d_cxw off its 8; a range [off_i, off_i + B_i) that
+ * leaves complex_cap or overlaps another; more than 2^31 - 1 groups in a batch or more than 2^25 wavefronts in a launch.
  * Out of scope: missing-value management 1 and 2 (it needs the present-point count back on the host; a follow-up that maps
- * onto the bitmap calls); NG = 0 (constant fields); WRITING complex packing (it needs a group-splitting heuristic); the
- * row-by-row packings 5.50 and up.  Fields with a section 6 bitmap compose through d_work with
- * aec_gpu_grib_dequantise_bitmap_async, as for simple packing.
+ * onto the bitmap calls); NG = 0 (constant fields); adaptive or variable-length grouping and groups shorter than 16 (every
+ * grouping is a valid stream: fixed groups cost about (ref_bits + width_bits) / G bits a value over the ideal); placing the
+ * written streams back to back (it needs a scan across fields); the row-by-row packings 5.50 and up.  Fields with a section
+ * 6 bitmap compose through d_work with aec_gpu_grib_dequantise_bitmap_async and aec_gpu_grib_quantise_bitmap_async, as for
+ * simple packing.
  *
  * OUT OF SCOPE: fields without a present point (a writer sets nbits 0 and drops section 7), bitmap indicator 254 and
- * predefined bitmaps (the caller hands over whichever bitmap applies); writing complex packing, complex packing with
- * missing-value management or without a group, the row-by-row (second-order) packings 5.50 and up and the JPEG and PNG
+ * predefined bitmaps (the caller hands over whichever bitmap applies); adaptive grouping in written complex packing, complex
+ * packing with missing-value management or without a group, the row-by-row (second-order) packings 5.50 and up and the JPEG and PNG
  * packings; parsing or writing GRIB messages themselves; a quantiser fused into the encoder or into the bit packer.
  */
 #ifndef AEC_GPU_GRIB_H
@@ -462,6 +494,83 @@ AEC_GPU_API int aec_gpu_grib_complex_to_ccsds_async(aec_gpu_ctx *ctx, const aec_
                                                     void *d_work, void *d_out, size_t out_cap, aec_gpu_batch_chunk *d_chunks,
                                                     uint64_t *d_rsi_bit_offsets, aec_gpu_enc_result *d_result,
                                                     aec_gpu_grib_cx *d_cx, void *stream);
+
+/*
+ * ---- complex packing (templates 5.2 / 5.3), writing -----------------------------------------------------------------------
+ * What a batch is written under (HOST; the contract is THE WRITER'S RULE at the head of this file).
+ */
+typedef struct aec_gpu_grib_complex_write_s {
+    uint32_t order;          /* 0: template 5.2;  1 or 2: template 5.3 */
+    uint32_t group_length;   /* G: 16, 32, 64, 128 or 256 */
+} aec_gpu_grib_complex_write;
+
+/* the per-field record of a write, on the device (d_cxw), 56 bytes */
+typedef struct aec_gpu_grib_cxw_s {
+    aec_gpu_grib_complex_field desc;   /* 44 bytes: what goes into section 5, and what the reader calls take back */
+    uint32_t pad;                      /* written as 0 */
+    uint64_t bytes;                    /* S_i: section 7's data length */
+} aec_gpu_grib_cxw;
+
+/*
+ * Host arithmetic only (1 = taken, 0 = refused: whatever aec_gpu_grib_plan refuses, and what the writer's rule lists).  plan is
+ * what aec_gpu_grib_plan gives for t and n_values, its workspace_bytes grown by this layer's descriptors, per-field records,
+ * tile totals (32 bytes a value tile) and group tables (12 bytes a group).  complex_bound is the sum of B_i; complex_offsets
+ * (optional, n_fields entries) receives their running sum.  tile_values = 1024 / container and value_tiles are those of
+ * aec_gpu_grib_complex_plan, group_tiles the sum of ceil(NG_i / 256) (a wavefront of the table kernel owns 256 groups),
+ * out_tiles the sum of ceil(ceil(n_i (nbits + order) / 8) / 1024) (a wavefront of the value kernel owns 1 KiB of the packed
+ * string at its longest).
+ */
+typedef struct aec_gpu_grib_complex_write_plan_s {
+    aec_gpu_grib_plan_t plan;
+    size_t   complex_bound;
+    uint64_t tile_values;
+    uint64_t value_tiles;
+    uint64_t group_tiles;
+    uint64_t out_tiles;
+} aec_gpu_grib_complex_write_plan_t;
+AEC_GPU_API int aec_gpu_grib_complex_write_plan(const aec_gpu_grib_template *t, const aec_gpu_grib_complex_write *w, int elem,
+                                                const uint64_t *n_values, uint64_t n_fields,
+                                                aec_gpu_grib_complex_write_plan_t *plan, uint64_t *work_offsets,
+                                                uint64_t *complex_offsets);
+
+/* Rooms to streams: the X of field i, in the plan's room at d_work + work_offsets[i], to S_i bytes at d_complex +
+ * complex_offsets[i], and its record to d_cxw.  d_work is only read.  n_fields == 0: AEC_OK, nothing is enqueued (so for the
+ * three calls below). */
+AEC_GPU_API int aec_gpu_grib_complex_write_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t,
+                                                 const aec_gpu_grib_complex_write *w, const uint64_t *n_values, uint64_t n_fields,
+                                                 const void *d_work, void *d_complex, size_t complex_cap,
+                                                 const uint64_t *complex_offsets, aec_gpu_grib_cxw *d_cxw, void *stream);
+
+/* Floats to 5.2 / 5.3 streams: aec_gpu_grib_quantise_async (same arguments, same refusals, have_params as there; d_work and
+ * d_fields come out exactly as it leaves them), then the writer.  The stream of a field whose record in d_fields says bad is
+ * unspecified, at most B_i bytes inside its own range, and its d_cxw record says how many. */
+AEC_GPU_API int aec_gpu_grib_complex_pack_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t,
+                                                const aec_gpu_grib_complex_write *w, int elem, const void *d_src,
+                                                const uint64_t *src_offsets, const uint64_t *n_values, const int32_t *D,
+                                                int have_params, const aec_gpu_grib_field *params, uint64_t n_fields, void *d_work,
+                                                aec_gpu_grib_field *d_fields, void *d_complex, size_t complex_cap,
+                                                const uint64_t *complex_offsets, aec_gpu_grib_cxw *d_cxw, void *stream);
+
+/* grid_ccsds to 5.2 / 5.3: aec_gpu_decode_chunks_async into d_work (with the pack's table, or bare with have_table == 0; d_in ..
+ * have_table, d_results and d_result as in aec_gpu_grib_ccsds_to_simple_async), then the writer.  A field whose record in
+ * d_results is not clean gets an unspecified stream of at most B_i bytes inside its own range and a record whose bytes <= B_i;
+ * every other field is exact. */
+AEC_GPU_API int aec_gpu_grib_ccsds_to_complex_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t,
+                                                    const aec_gpu_grib_complex_write *w, const void *d_in, size_t in_bytes,
+                                                    const uint64_t *in_offsets, const uint64_t *in_bytes_each,
+                                                    const uint64_t *n_values, uint64_t n_fields, uint64_t *d_rsi_bit_offsets,
+                                                    int have_table, void *d_work, aec_gpu_dec_result *d_results,
+                                                    aec_gpu_dec_result *d_result, void *d_complex, size_t complex_cap,
+                                                    const uint64_t *complex_offsets, aec_gpu_grib_cxw *d_cxw, void *stream);
+
+/* grid_simple to 5.2 / 5.3: aec_gpu_grib_bits_unpack_async (d_simple .. simple_bytes_each and its refusals as there), then the
+ * writer. */
+AEC_GPU_API int aec_gpu_grib_simple_to_complex_async(aec_gpu_ctx *ctx, const aec_gpu_grib_template *t,
+                                                     const aec_gpu_grib_complex_write *w, const void *d_simple, size_t simple_bytes,
+                                                     const uint64_t *simple_offsets, const uint64_t *simple_bytes_each,
+                                                     const uint64_t *n_values, uint64_t n_fields, void *d_work, void *d_complex,
+                                                     size_t complex_cap, const uint64_t *complex_offsets, aec_gpu_grib_cxw *d_cxw,
+                                                     void *stream);
 
 #ifdef __cplusplus
 }

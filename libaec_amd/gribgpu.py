@@ -1,6 +1,6 @@
 """GRIB2 CCSDS packing and simple packing that stay on the device (include/aec_gpu_grib.h) for torch tensors living in HBM:
 float fields to section-7 streams and back, template 5.0 streams to template 5.42 streams and back, and complex packing
-(templates 5.2 / 5.3) read into floats, template 5.42 streams or template 5.0 streams.
+(templates 5.2 / 5.3) read into floats, template 5.42 streams or template 5.0 streams, and written from any of the three.
 
 torch is used for device memory and streams only; the minimum / maximum, the parameters, the quantisation and the coder are
 kernels launched by libaec.so.0 through the C entry points declared in aec_gpu_grib.h.
@@ -56,6 +56,19 @@ class ComplexPlan(C.Structure):
     _fields_ = [("plan", Plan), ("tile_values", C.c_uint64), ("value_tiles", C.c_uint64), ("group_tiles", C.c_uint64)]
 
 
+class ComplexWrite(C.Structure):
+    """aec_gpu_grib_complex_write: what a batch of template 5.2 / 5.3 streams is written under"""
+    _fields_ = [("order", C.c_uint32), ("group_length", C.c_uint32)]
+
+
+class ComplexWritePlan(C.Structure):
+    """aec_gpu_grib_complex_write_plan_t"""
+    _fields_ = [("plan", Plan), ("complex_bound", C.c_size_t), ("tile_values", C.c_uint64), ("value_tiles", C.c_uint64),
+                ("group_tiles", C.c_uint64), ("out_tiles", C.c_uint64)]
+
+
+COMPLEX_KEYS = [k for k, _ in ComplexField._fields_]
+CXW_DTYPE = np.dtype([(k, "<u4") for k in COMPLEX_KEYS] + [("pad", "<u4"), ("bytes", "<u8")])     # aec_gpu_grib_cxw
 CX_DTYPE = np.dtype([("x_min", "<i8"), ("x_max", "<i8"), ("status", "<u4"), ("pad", "<u4")])     # aec_gpu_grib_cx
 FIELD_DTYPE = np.dtype([("R", "<f4"), ("E", "<i4"), ("D", "<i4"), ("status", "<u4")])      # aec_gpu_grib_field
 BATCH_CHUNK_DTYPE = np.dtype([("base_bits", "<u8"), ("bits", "<u8")])
@@ -123,6 +136,19 @@ def _lib():
         lib.aec_gpu_grib_complex_unpack_async.argtypes = [vp, pt, C.c_int, vp, vp, sz, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]
         lib.aec_gpu_grib_complex_to_ccsds_async.restype = C.c_int
         lib.aec_gpu_grib_complex_to_ccsds_async.argtypes = [vp, pt, vp, vp, sz, vp, vp, vp, u64, vp, vp, sz, vp, vp, vp, vp, vp]
+        if not hasattr(lib, "aec_gpu_grib_complex_write_async"):
+            raise RuntimeError("this libaec.so.0 writes no complex packing (aec_gpu_grib_complex_write_*): rebuild it")
+        pw = C.POINTER(ComplexWrite)
+        lib.aec_gpu_grib_complex_write_plan.restype = C.c_int
+        lib.aec_gpu_grib_complex_write_plan.argtypes = [pt, pw, C.c_int, vp, u64, C.POINTER(ComplexWritePlan), vp, vp]
+        lib.aec_gpu_grib_complex_write_async.restype = C.c_int
+        lib.aec_gpu_grib_complex_write_async.argtypes = [vp, pt, pw, vp, u64, vp, vp, sz, vp, vp, vp]
+        lib.aec_gpu_grib_complex_pack_async.restype = C.c_int
+        lib.aec_gpu_grib_complex_pack_async.argtypes = [vp, pt, pw, C.c_int, vp, vp, vp, vp, C.c_int, vp, u64, vp, vp, vp, sz, vp, vp, vp]
+        lib.aec_gpu_grib_ccsds_to_complex_async.restype = C.c_int
+        lib.aec_gpu_grib_ccsds_to_complex_async.argtypes = [vp, pt, pw, vp, sz, vp, vp, vp, u64, vp, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp]
+        lib.aec_gpu_grib_simple_to_complex_async.restype = C.c_int
+        lib.aec_gpu_grib_simple_to_complex_async.argtypes = [vp, pt, pw, vp, sz, vp, vp, vp, u64, vp, vp, sz, vp, vp, vp]
         _bound = True
     return lib
 
@@ -235,6 +261,33 @@ def complex_plan(nbits, options, block_size, rsi, elem, n_values, fields):
                 out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
                 work_offsets=offs[:n_values.size], tile_values=int(cp.tile_values), value_tiles=int(cp.value_tiles),
                 group_tiles=int(cp.group_tiles))
+
+
+def complex_write_plan(nbits, options, block_size, rsi, elem, n_values, order, group_length):
+    """aec_gpu_grib_complex_write_plan (host arithmetic, no device needed): the dict of plan() plus complex_bound (the sum of the
+    B_i), complex_offsets (their running sum), tile_values, value_tiles, group_tiles and out_tiles, or None where the batch would
+    be refused"""
+    t = Template(nbits, options, block_size, rsi)
+    w = ComplexWrite(order, group_length)
+    n_values = _u64(n_values)
+    offs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    coffs = np.zeros(max(1, n_values.size), dtype=np.uint64)
+    wp = ComplexWritePlan()
+    if not _lib().aec_gpu_grib_complex_write_plan(C.byref(t), C.byref(w), elem, _host(n_values), n_values.size, C.byref(wp), _host(offs),
+                                                  _host(coffs)):
+        return None
+    p = wp.plan
+    return dict(coder=(p.coder.bits_per_sample, p.coder.block_size, p.coder.rsi, p.coder.flags), work_bytes=int(p.work_bytes),
+                out_bound=int(p.out_bound), rsi_entries=int(p.rsi_entries), workspace_bytes=int(p.workspace_bytes),
+                work_offsets=offs[:n_values.size], complex_bound=int(wp.complex_bound), complex_offsets=coffs[:n_values.size],
+                tile_values=int(wp.tile_values), value_tiles=int(wp.value_tiles), group_tiles=int(wp.group_tiles),
+                out_tiles=int(wp.out_tiles))
+
+
+def complex_fields_of(cxw):
+    """the records of a write (a CXW_DTYPE array) as (what complex_fields() takes, complex_sizes): a writer's output feeds the
+    reading calls directly"""
+    return [{k: int(r[k]) for k in COMPLEX_KEYS} for r in cxw], np.array([int(r["bytes"]) for r in cxw], np.uint64)
 
 
 def _elem_of(t):
@@ -462,7 +515,123 @@ class GribCodec:
                                                             _host(co), _host(cs), _host(nv), nv.size, _ptr(d_work), _ptr(d_out), out_cap,
                                                             _ptr(d_chunks), _ptr(d_table), _ptr(d_result), _ptr(d_cx), self._stream(stream))
 
+    # ---- enqueue, complex packing (templates 5.2 / 5.3), writing ---------------------------------------
+    def complex_write_plan(self, n_values, order, group_length, elem=F32):
+        t = self.t
+        return complex_write_plan(t.nbits, t.options, t.block_size, t.rsi, elem, n_values, order, group_length)
+
+    def complex_write_async(self, order, group_length, n_values, d_work, d_complex, complex_cap, complex_offsets, d_cxw, stream=None):
+        """rooms to streams under the writer's rule: at most B_i bytes at d_complex + complex_offsets[i] (bytes, a uint64 array on
+        the host); d_cxw: n * 56 bytes (CXW_DTYPE)"""
+        nv, co = _u64(n_values), _u64(complex_offsets)
+        w = ComplexWrite(order, group_length)
+        return self.lib.aec_gpu_grib_complex_write_async(self.ctx, C.byref(self.t), C.byref(w), _host(nv), nv.size, _ptr(d_work),
+                                                         _ptr(d_complex), complex_cap, _host(co), _ptr(d_cxw), self._stream(stream))
+
+    def complex_pack_async(self, order, group_length, elem, d_src, src_offsets, n_values, D, params, d_work, d_fields, d_complex, complex_cap,
+                           complex_offsets, d_cxw, stream=None):
+        """quantise_async, then complex_write_async"""
+        offs, nv, co = _u64(src_offsets), _u64(n_values), _u64(complex_offsets)
+        Dh = None if D is None else np.ascontiguousarray(D, dtype=np.int32)
+        ph = None if params is None else np.ascontiguousarray(params, dtype=FIELD_DTYPE)
+        w = ComplexWrite(order, group_length)
+        return self.lib.aec_gpu_grib_complex_pack_async(self.ctx, C.byref(self.t), C.byref(w), elem, _ptr(d_src), _host(offs), _host(nv),
+                                                        _host(Dh), int(ph is not None), _host(ph), nv.size, _ptr(d_work), _ptr(d_fields),
+                                                        _ptr(d_complex), complex_cap, _host(co), _ptr(d_cxw), self._stream(stream))
+
+    def ccsds_to_complex_async(self, order, group_length, d_in, in_bytes, in_offsets, in_sizes, n_values, d_table, have_table, d_work,
+                               d_results, d_result, d_complex, complex_cap, complex_offsets, d_cxw, stream=None):
+        """template 5.42 streams to template 5.2 / 5.3 streams: the chunk decoder (with the pack's table, or bare), then
+        complex_write_async"""
+        ino, ins, nv, co = _u64(in_offsets), _u64(in_sizes), _u64(n_values), _u64(complex_offsets)
+        w = ComplexWrite(order, group_length)
+        return self.lib.aec_gpu_grib_ccsds_to_complex_async(self.ctx, C.byref(self.t), C.byref(w), _ptr(d_in), in_bytes, _host(ino), _host(ins),
+                                                            _host(nv), nv.size, _ptr(d_table), int(bool(have_table)), _ptr(d_work),
+                                                            _ptr(d_results), _ptr(d_result), _ptr(d_complex), complex_cap, _host(co),
+                                                            _ptr(d_cxw), self._stream(stream))
+
+    def simple_to_complex_async(self, order, group_length, d_simple, simple_bytes, simple_offsets, simple_sizes, n_values, d_work, d_complex,
+                                complex_cap, complex_offsets, d_cxw, stream=None):
+        """template 5.0 streams to template 5.2 / 5.3 streams: bits_unpack_async, then complex_write_async"""
+        so, ss, nv, co = _u64(simple_offsets), _u64(simple_sizes), _u64(n_values), _u64(complex_offsets)
+        w = ComplexWrite(order, group_length)
+        return self.lib.aec_gpu_grib_simple_to_complex_async(self.ctx, C.byref(self.t), C.byref(w), _ptr(d_simple), simple_bytes, _host(so),
+                                                             _host(ss), _host(nv), nv.size, _ptr(d_work), _ptr(d_complex), complex_cap,
+                                                             _host(co), _ptr(d_cxw), self._stream(stream))
+
     # ---- convenience (synchronising) -------------------------------------------------------------
+    def _complex_write_plan_or_raise(self, n_values, order, group_length, elem=F32):
+        pl = self.complex_write_plan(n_values, order, group_length, elem)
+        if pl is None:
+            raise ValueError("not a batch for one call (aec_gpu_grib_complex_write_plan)")
+        return pl
+
+    def _complex_out(self, pl, n, dev):
+        torch = self.torch
+        return (torch.empty(max(1, pl["complex_bound"]), dtype=torch.uint8, device=dev),
+                torch.zeros(max(1, n) * CXW_DTYPE.itemsize, dtype=torch.uint8, device=dev))
+
+    def complex_write(self, d_work, n_values, order, group_length):
+        """X in the plan's rooms of d_work -> (d_complex, complex_offsets, the CXW_DTYPE records): section 7 of field i under template
+        5.2 (order 0) or 5.3 is d_complex[complex_offsets[i]:][:records[i]["bytes"]], the record's other members go into section 5
+        (complex_fields_of() turns them into what the reading calls take)"""
+        pl = self._complex_write_plan_or_raise(n_values, order, group_length)
+        n = len(n_values)
+        d_complex, d_cxw = self._complex_out(pl, n, d_work.device)
+        self._check(self.complex_write_async(order, group_length, n_values, d_work, d_complex, d_complex.numel(), pl["complex_offsets"], d_cxw),
+                    "aec_gpu_grib_complex_write_async")
+        return d_complex, pl["complex_offsets"], d_cxw.cpu().numpy().view(CXW_DTYPE)[:n]
+
+    def complex_pack(self, d_values, offsets, n_values, D, order, group_length, params=None):
+        """fields of n_values[i] elements at ELEMENT offsets[i] of the float tensor d_values -> (d_complex, complex_offsets, the
+        CXW_DTYPE records, the FIELD_DTYPE records (R, E, D, status) of section 5)"""
+        torch = self.torch
+        elem = _elem_of(d_values)
+        pl = self._complex_write_plan_or_raise(n_values, order, group_length, elem)
+        n, dev = len(n_values), d_values.device
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_fields = torch.zeros(max(1, n) * FIELD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_complex, d_cxw = self._complex_out(pl, n, dev)
+        Dh = np.broadcast_to(np.asarray(D, dtype=np.int32), (n,))
+        self._check(self.complex_pack_async(order, group_length, elem, d_values, _u64(offsets) * np.uint64(elem), n_values, Dh, params, d_work,
+                                            d_fields, d_complex, d_complex.numel(), pl["complex_offsets"], d_cxw),
+                    "aec_gpu_grib_complex_pack_async")
+        return d_complex, pl["complex_offsets"], d_cxw.cpu().numpy().view(CXW_DTYPE)[:n], d_fields.cpu().numpy().view(FIELD_DTYPE)[:n]
+
+    def ccsds_to_complex(self, d_streams, spans, n_values, order, group_length, d_table=None):
+        """template 7.42 streams (spans[i] = (start, bytes) of the uint8 tensor d_streams; with d_table no index pass runs) ->
+        (d_complex, complex_offsets, the CXW_DTYPE records, per-field decode records)"""
+        torch = self.torch
+        pl = self._complex_write_plan_or_raise(n_values, order, group_length)
+        n, dev = len(n_values), d_streams.device
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_complex, d_cxw = self._complex_out(pl, n, dev)
+        have = d_table is not None
+        if not have:
+            d_table = torch.zeros(max(1, pl["rsi_entries"]), dtype=torch.int64, device=dev)
+        d_results = torch.zeros(max(1, n) * gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_result = torch.zeros(gpu.DEC_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        in_offs = None if have else [s for s, _ in spans]
+        in_sizes = None if have else [b for _, b in spans]
+        self._check(self.ccsds_to_complex_async(order, group_length, d_streams, d_streams.numel(), in_offs, in_sizes, n_values, d_table, have,
+                                                d_work, d_results, d_result, d_complex, d_complex.numel(), pl["complex_offsets"], d_cxw),
+                    "aec_gpu_grib_ccsds_to_complex_async")
+        return (d_complex, pl["complex_offsets"], d_cxw.cpu().numpy().view(CXW_DTYPE)[:n],
+                d_results.cpu().numpy().view(gpu.DEC_RESULT_DTYPE)[:n])
+
+    def simple_to_complex(self, d_simple, simple_offsets, n_values, order, group_length, simple_sizes=None):
+        """template 7.0 streams at simple_offsets (bytes) of the uint8 tensor d_simple -> (d_complex, complex_offsets, the CXW_DTYPE
+        records)"""
+        torch = self.torch
+        pl = self._complex_write_plan_or_raise(n_values, order, group_length)
+        n, dev = len(n_values), d_simple.device
+        d_work = torch.empty(pl["work_bytes"] + 16, dtype=torch.uint8, device=dev)
+        d_complex, d_cxw = self._complex_out(pl, n, dev)
+        self._check(self.simple_to_complex_async(order, group_length, d_simple, d_simple.numel(), simple_offsets, simple_sizes, n_values, d_work,
+                                                 d_complex, d_complex.numel(), pl["complex_offsets"], d_cxw),
+                    "aec_gpu_grib_simple_to_complex_async")
+        return d_complex, pl["complex_offsets"], d_cxw.cpu().numpy().view(CXW_DTYPE)[:n]
+
     def _complex_plan_or_raise(self, n_values, fields, elem=F32):
         pl = self.complex_plan(n_values, fields, elem)
         if pl is None:
